@@ -3,6 +3,11 @@
 
     python bench.py --gpus N --steps K --warmup W        (N > 1 without a launcher: re-executes itself under torch.distributed.run)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
+    python bench.py --full ...                           (also every other leg: roofline step, frame, paths B / C, other modes, baselines)
+    python bench.py --dump-outputs DIR ...               (also the last timed step's outputs as DIR/<name>.npy)
+
+A plain run sets up, warms up, times the K steps and prints the headline line; everything else is behind --full.
+The warm-up trains deterministically and the last timed step restarts from the parameters it reached, so its outputs repeat from run to run.
 
 A "step" is one training step of the live S-NeRF renderer (path A, MipNerfModel) on one batch of synthetic
 nuScenes-like rays: sample -> IPE encode -> proposal MLP -> composite -> resample -> IPE encode -> NeRF MLP
@@ -795,7 +800,8 @@ def compact_line(out, limit=7900):
             return float(f"{v:.6g}")
         return v
     c = {k: (strip(v) if k != "config" else {kk: (vv if kk == "workload" else strip(vv)) for kk, vv in v.items() if kk not in PROSE_KEYS}) for k, v in out.items()}
-    c["roofline"] = dict(c["roofline"], kernel=out["roofline"]["kernel"].split(" ")[0])
+    if "roofline" in c:
+        c["roofline"] = dict(c["roofline"], kernel=out["roofline"]["kernel"].split(" ")[0])
     ordered = {k: v for k, v in c.items() if k not in LAST_LEGS}
     for k in LAST_LEGS:
         if k in c:
@@ -805,6 +811,27 @@ def compact_line(out, limit=7900):
     if n > limit:                                          # (never cut a number silently: say so in the line)
         ordered_final = {"line_bytes_over_limit": n, **ordered}
     return ordered_final
+
+
+OUT_NAMES = ("dist0", "acc0", "s0", "w0", "rgb1", "dist1", "acc1", "s1", "w1", "sem1")     # MipNerfModel._run's outs, in order
+DUMP_LIMIT = 64 << 20
+
+
+def dump_outputs(path, loss, outs, limit=DUMP_LIMIT):
+    """--dump-outputs: what the last timed step returned to its caller (MipTrainer.step -> loss, outs) as float32 .npy files.
+    An array larger than its share of `limit` is written as a fixed sample (seed 0, sorted flat indices) with the indices beside it."""
+    arrays = {"loss": loss.reshape(1)}
+    arrays.update({k: v for k, v in zip(OUT_NAMES, outs) if v is not None})
+    arrays = {k: v.detach().to(torch.float32).cpu().numpy() for k, v in arrays.items()}
+    os.makedirs(path, exist_ok=True)
+    share = limit // len(arrays) // 12 - 32                  # elements per sampled array: a float32 value + a float64 index each, 2 headers
+    total = sum(a.nbytes for a in arrays.values())
+    for k, a in arrays.items():
+        if total > limit and a.size > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=share, replace=False))
+            np.save(os.path.join(path, k + "_sample_index.npy"), idx.astype(np.float64))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, k + ".npy"), a)
 
 
 def main():
@@ -842,6 +869,13 @@ def main():
     ap.add_argument("--graph", action="store_true",
                     help="time the hipGraph-captured step (MipTrainer.capture / replay: forward + loss tail + backward as one graph launch; "
                          "N > 1: the all-reduce and Adam follow outside the graph) -- the small-batch / strong-scaling step")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run every other leg: the GEMM roofline step, the frame render, paths B / C, the ERT and precision legs, "
+                         "drop-in / pose-refine / small-step legs, the other compute modes, the CPU and eager baselines, N > 1 comm and strong scaling "
+                         "(the --no-* switches select among them); without it the line carries the headline train step only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (loss, both levels' outputs) as DIR/<name>.npy "
+                         "(float32, at most 64 MB in all: a fixed, seeded sample of anything larger)")
     args = ap.parse_args()
     global S0, P1
     if args.shape == "shipped":
@@ -887,19 +921,37 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
+    # The weight- and bias-gradient reductions add fp32 partials with atomics (order-dependent last bits), and Adam turns such bits of
+    # near-zero gradients into lr-sized steps: parameters carried over the timed steps differ from run to run.  So the warm-up trains in the
+    # deterministic mode (partials folded in a fixed order: the same trajectory every run; bf16x3 has no such fold), the timed steps train on
+    # from there as before, and the LAST timed step starts again from the parameters the warm-up reached: its outputs (--dump-outputs) come
+    # from the same inputs every run.
+    model.set_deterministic(args.compute != "bf16x3")
+    for _ in range(args.warmup):
+        trainer.step(rays, tgt, depth, conf)
+    model.set_deterministic(False)
+    params_w = model.arena.flat.clone()
+
+    def reset_params():
+        with torch.no_grad():
+            model.arena.flat.copy_(params_w)
+        model.arena.bump()
+
     if args.graph:
         trainer.capture(rays, tgt, depth, conf, warmup=max(args.warmup, 1))
         step_fn = trainer.replay
     else:
         step_fn = lambda: trainer.step(rays, tgt, depth, conf)
-    for _ in range(args.warmup):
-        step_fn()
+    step_fn()                                                # one untimed step in the timed mode (first use of its kernels and plans)
+    reset_params()
     barrier()
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
     t0 = time.perf_counter()
     ev[0].record()
     for i in range(args.steps):
-        loss, _ = step_fn()
+        if i == args.steps - 1:
+            reset_params()
+        loss, outs = step_fn()
         ev[i + 1].record()                                   # per-step device timestamps (no sync inside the timed region)
     barrier()
     elapsed = time.perf_counter() - t0
@@ -910,13 +962,16 @@ def main():
     final_loss = float(loss)
     per_step = sorted(ev[i].elapsed_time(ev[i + 1]) for i in range(args.steps))
     ms_median = per_step[len(per_step) // 2] if len(per_step) % 2 else 0.5 * (per_step[len(per_step) // 2 - 1] + per_step[len(per_step) // 2])
+    if args.dump_outputs and rank == 0:                      # before any other leg steps the model again
+        dump_outputs(args.dump_outputs, loss, outs)
 
     # ---- roofline of the dominant kernel (NT MFMA GEMM: all forward + data-gradient layers); the instrumented step contains
     # the gradient all-reduce, so EVERY rank runs it
-    launches, gemm_ms, padded_flops, alg_nt = measure_gemm_kernel(trainer, rays, tgt, depth, conf)
-    barrier()
+    if args.full:
+        launches, gemm_ms, padded_flops, alg_nt = measure_gemm_kernel(trainer, rays, tgt, depth, conf)
+        barrier()
     comm = None
-    if world > 1:                                            # the step's one exchange, timed alone: all-reduce of the flat gradient arena
+    if world > 1 and args.full:                              # the step's one exchange, timed alone: all-reduce of the flat gradient arena
         buf = torch.zeros_like(model.arena.grad)
         for _ in range(2):
             dist.all_reduce(buf)
@@ -932,7 +987,7 @@ def main():
     # ---- N > 1: the STRONG-scaling step beside the weak-scaling headline (north_star / SURVEY 8e: the reference's 4096-ray batch split
     # across the ranks, 512 rays per GPU at N = 8) -- a second trainer on the same model, launched per kernel and as a hipGraph
     strong = None
-    if world > 1 and args.scaling == "weak":
+    if world > 1 and args.scaling == "weak" and args.full:
         try:
             ns = max(args.rays // world, 1)
             rs = synth_rays(ns, 3000 + rank, device)
@@ -969,15 +1024,6 @@ def main():
     if rank == 0:
         ms_step = elapsed / args.steps * 1e3
         rays_per_s = world * n * args.steps / elapsed
-        achieved = alg_nt / (gemm_ms * 1e-3) / 1e12
-        peak = 157.3 if args.compute == "f32" else PEAK_BF16_TFLOPS
-        traffic, traffic_src = roofline_traffic(args.compute, args.variant)
-        roofline = {"bound": "mfma", "kernel": {8: "gemm_nt8p_kernel (bf16, 256x256 persistent 8-phase)", 4: "gemm_nt8_kernel (bf16, 256x256 8-phase)", 1: "gemm_nt_kernel<bf16,256,256,2,4>"}.get(args.variant, "gemm_nt_kernel<bf16,128,128,2,2>") if args.compute == "bf16" else ("gemm_nt_kernel<f32,128,128,2,2>" if args.compute == "f32" else "gemm_nt8p_kernel<.., SPLIT> (three bf16 MFMA passes per product; executed work)"),
-                    "achieved": round(achieved, 2), "peak": peak, "unit": "TFLOP/s", "frac": round(achieved / peak, 4),
-                    "traffic": traffic, "traffic_source": traffic_src,
-                    "launches_per_step": launches, "avg_launch_ms": round(gemm_ms / launches, 4), "kernel_ms_per_step": round(gemm_ms, 3),
-                    "algorithmic_flops_per_step": alg_nt, "padded_flops_per_step": padded_flops,
-                    "whole_step_tflops": round(3 * fwd * n / (ms_step * 1e-3) / 1e12, 1)}
         out = {"metric": "rays/sec (train step)", "value": round(rays_per_s, 1), "unit": "rays/s", "n_gpus": world, "steps": args.steps,
                "warmup": args.warmup, "ms_per_step": round(ms_step, 3), "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None,
                "dtype": args.compute, "data": "synthetic",
@@ -985,7 +1031,17 @@ def main():
                                       f"({S0 + P1 - 1} spp), hidden 1024, rgb_layer 3, cone + contraction + IPE-96",
                           "rays_per_gpu_per_step": n, "global_rays_per_step": n * world, "parallelism": f"dp{world} (ray-sharded, flat-arena RCCL all-reduce overlapped with the backward)",
                           "train_flops_per_ray": 3 * fwd},
-               "roofline": roofline, "final_loss": final_loss, "ms_per_step_median": round(ms_median, 3)}
+               "final_loss": final_loss, "ms_per_step_median": round(ms_median, 3)}
+        if args.full:
+            achieved = alg_nt / (gemm_ms * 1e-3) / 1e12
+            peak = 157.3 if args.compute == "f32" else PEAK_BF16_TFLOPS
+            traffic, traffic_src = roofline_traffic(args.compute, args.variant)
+            out["roofline"] = {"bound": "mfma", "kernel": {8: "gemm_nt8p_kernel (bf16, 256x256 persistent 8-phase)", 4: "gemm_nt8_kernel (bf16, 256x256 8-phase)", 1: "gemm_nt_kernel<bf16,256,256,2,4>"}.get(args.variant, "gemm_nt_kernel<bf16,128,128,2,2>") if args.compute == "bf16" else ("gemm_nt_kernel<f32,128,128,2,2>" if args.compute == "f32" else "gemm_nt8p_kernel<.., SPLIT> (three bf16 MFMA passes per product; executed work)"),
+                               "achieved": round(achieved, 2), "peak": peak, "unit": "TFLOP/s", "frac": round(achieved / peak, 4),
+                               "traffic": traffic, "traffic_source": traffic_src,
+                               "launches_per_step": launches, "avg_launch_ms": round(gemm_ms / launches, 4), "kernel_ms_per_step": round(gemm_ms, 3),
+                               "algorithmic_flops_per_step": alg_nt, "padded_flops_per_step": padded_flops,
+                               "whole_step_tflops": round(3 * fwd * n / (ms_step * 1e-3) / 1e12, 1)}
         if args.graph:
             out["config"]["step"] = "hipGraph-captured (MipTrainer.capture / replay)"
         if comm is not None:
@@ -995,7 +1051,7 @@ def main():
 
     # ---- full-frame inference (forward only): 1600 x 900 rays through the drop-in render_image (models.py:328-360; eval.py:146),
     # one contiguous block of the frame per rank + one all-gather per output buffer
-    if not args.no_frame:
+    if args.full and not args.no_frame:
         H, W = 900, 1600
         chunk = args.frame_chunk
         render_fn = lambda r: model(r, False, False, 0.)
@@ -1041,7 +1097,7 @@ def main():
 
     # ---- the other two renderers of the reference on the same GPU (BASELINE configs 4-5 = path C, the classic render_rays = path B):
     # compact legs so that every config has a driver-timed number; the headline above stays path A (configs[1])
-    if rank == 0 and world == 1 and not args.no_paths and args.compute == "bf16":
+    if args.full and rank == 0 and world == 1 and not args.no_paths and args.compute == "bf16":
         torch.cuda.empty_cache()
         t0 = time.perf_counter()
         out["path_c"] = path_c_leg(device)
@@ -1074,7 +1130,7 @@ def main():
     # a fresh model fitted for 200 steps to an analytic street scene (tools/ert_scene.py), its 1600 x 900 frame rendered plain and with
     # the front-to-back termination inside north_star's tolerance (eps_t = 1e-4: an exact bound on acc / rgb).  A labelled extra: the
     # headline frame above stays un-skipped.
-    if rank == 0 and world == 1 and not args.no_ert_scene and args.compute == "bf16":
+    if args.full and rank == 0 and world == 1 and not args.no_ert_scene and args.compute == "bf16":
         sys.path.insert(0, os.path.join(REPO, "tools"))
         import ert_scene
         torch.cuda.empty_cache()
@@ -1092,7 +1148,7 @@ def main():
     # ---- the two routes a user of the reference takes besides MipTrainer.step: the unmodified train.py loop (autograd + torch losses +
     # torch.optim.Adam) and the shipped config's pose_refine = True (configs/nuScenes_depth_6cams:31: the step also back-propagates to
     # the rays, MipTrainer.step(..., ray_grads=True))
-    if rank == 0 and world == 1 and not args.no_dropin and args.compute == "bf16":
+    if args.full and rank == 0 and world == 1 and not args.no_dropin and args.compute == "bf16":
         sd0 = {k: v.clone() for k, v in model.state_dict().items()}
         dt_d, loss_d = dropin_autograd_leg(sd0, rays, tgt, depth, conf, device, 5)
         out["dropin_autograd"] = {"rays_per_s": round(n / dt_d, 1), "ms_per_step": round(dt_d * 1e3, 3), "steps": 5, "final_loss": loss_d,
@@ -1110,13 +1166,13 @@ def main():
                               "what": "MipTrainer.step(..., ray_grads=True): the train step + d loss / d (origins, directions, viewdirs) for the pose optimiser"}
         torch.cuda.empty_cache()
 
-    if rank == 0 and world == 1 and not args.no_dropin and args.compute == "bf16" and args.shape == "baseline":
+    if args.full and rank == 0 and world == 1 and not args.no_dropin and args.compute == "bf16" and args.shape == "baseline":
         out["small_step"] = small_step_leg(device)
         out["small_step"]["strong_scaling_ceiling_at_8_gpus"] = round(out["ms_per_step"] / out["small_step"]["ms"], 2)
         out["shipped_shape"] = shipped_shape_leg(device)
 
     # ---- the fp32-parity mode's speed (north_star's 1e-4-relative contract holds in compute="f32": exact-fp32 MFMA 32x32x2, 157.3 TF peak)
-    if rank == 0 and world == 1 and not args.no_f32 and args.compute == "bf16":
+    if args.full and rank == 0 and world == 1 and not args.no_f32 and args.compute == "bf16":
         m32 = build_model("f32", device)
         m32.load_state_dict({k: v.clone() for k, v in model.state_dict().items()})
         t32 = MipTrainer(m32, lr=5e-4)
@@ -1237,7 +1293,7 @@ def main():
         torch.cuda.empty_cache()
 
     # ---- parity read-out + host-CPU baseline (rank 0, N = 1 only)
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         ncpu = min(args.cpu_rays, n)
         sd = {k: v.clone() for k, v in model.state_dict().items()}
         cpu_rps, cpu_s, rgb_ref, dist_ref, cpu_fwd_rps = cpu_baseline(ncpu, sd, rays)
@@ -1272,7 +1328,7 @@ def main():
                          "psnr_f32_kernels_vs_cpu_oracle_db": psnr(r32[1][0].cpu(), rgb_ref),
                          "psnr_bf16_kernels_vs_cpu_oracle_db": psnr(rb[1][0].cpu(), rgb_ref)}
         del m32
-    if rank == 0 and world == 1 and not args.no_eager:
+    if args.full and rank == 0 and world == 1 and not args.no_eager:
         sd = {k: v.clone() for k, v in model.state_dict().items()}
         e32, ms32, f32_fwd = eager_baseline(sd, rays, n, 3, False)
         e16, ms16, f16_fwd = eager_baseline(sd, rays, n, 3, True)

@@ -104,6 +104,29 @@ def test_bench_relaunches_itself_for_multi_gpu_without_a_launcher(monkeypatch):
     assert seen["env"]["HSA_ENABLE_IPC_MODE_LEGACY"] == "0"
 
 
+def test_dump_outputs_writes_float32_arrays_within_the_limit(tmp_path):
+    """bench.py --dump-outputs: one float32 .npy per array the step returned; over the byte limit, a fixed seeded sample (the same
+    indices every run) with its index file beside it, the whole directory inside the limit."""
+    import sys
+    import numpy as np
+    import torch
+    sys.path.insert(0, REPO)
+    import bench
+    outs = tuple(torch.randn(4096, 8, dtype=torch.float64) for _ in range(9))
+    full, small, again = tmp_path / "full", tmp_path / "small", tmp_path / "again"
+    bench.dump_outputs(str(full), torch.tensor(1.5), outs)
+    assert sorted(p.name for p in full.iterdir()) == sorted([k + ".npy" for k in bench.OUT_NAMES[:9]] + ["loss.npy"])
+    assert np.load(full / "loss.npy").tolist() == [1.5] and np.load(full / "rgb1.npy").dtype == np.float32
+    assert np.array_equal(np.load(full / "w1.npy"), outs[8].float().numpy())
+    limit = 200000
+    for d in (small, again):
+        bench.dump_outputs(str(d), torch.tensor(1.5), outs, limit=limit)
+    assert sum(p.stat().st_size for p in small.iterdir()) <= limit
+    idx = np.load(small / "w1_sample_index.npy").astype(np.int64)
+    assert np.array_equal(np.load(small / "w1.npy"), outs[8].float().numpy().reshape(-1)[idx])
+    assert all(np.array_equal(np.load(p), np.load(again / p.name)) for p in small.iterdir())
+
+
 import pytest  # noqa: E402
 
 
@@ -115,7 +138,7 @@ def test_bench_two_ranks_on_one_gpu_without_a_launcher():
     import subprocess
     import sys
     cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--backend", "gloo", "--same-device", "--steps", "2", "--warmup", "1",
-           "--rays", "512", "--scaling", "strong", "--no-cpu", "--no-eager", "--no-f32", "--frame-chunk", "16384"]
+           "--rays", "512", "--scaling", "strong", "--full", "--no-cpu", "--no-eager", "--no-f32", "--frame-chunk", "16384"]
     env = dict(os.environ)
     env.pop("WORLD_SIZE", None)
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=850, env=env)
@@ -135,7 +158,7 @@ def test_bench_two_ranks_weak_scaling_line_carries_the_strong_scaling_step():
     import subprocess
     import sys
     cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--backend", "gloo", "--same-device", "--steps", "2", "--warmup", "1",
-           "--rays", "512", "--no-cpu", "--no-eager", "--no-f32", "--no-frame", "--no-dropin", "--no-paths", "--no-ert-scene"]
+           "--rays", "512", "--full", "--no-cpu", "--no-eager", "--no-f32", "--no-frame", "--no-dropin", "--no-paths", "--no-ert-scene"]
     env = dict(os.environ)
     env.pop("WORLD_SIZE", None)
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=850, env=env)
@@ -156,7 +179,7 @@ def test_bench_eight_ranks_strong_scaling_on_one_gpu():
     import subprocess
     import sys
     cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "8", "--backend", "gloo", "--same-device", "--steps", "2", "--warmup", "1",
-           "--rays", "4096", "--scaling", "strong", "--graph", "--no-cpu", "--no-eager", "--no-f32", "--no-frame", "--no-dropin", "--no-paths",
+           "--rays", "4096", "--scaling", "strong", "--graph", "--full", "--no-cpu", "--no-eager", "--no-f32", "--no-frame", "--no-dropin", "--no-paths",
            "--no-ert-scene"]
     env = dict(os.environ)
     env.pop("WORLD_SIZE", None)
@@ -168,3 +191,38 @@ def test_bench_eight_ranks_strong_scaling_on_one_gpu():
     assert d["n_gpus"] == 8 and d["scaling"] == "strong" and d["config"]["rays_per_gpu_per_step"] == 512 and d["config"]["global_rays_per_step"] == 4096
     assert d["comm"]["ranks"] == 8 and d["comm"]["bytes"] > 3.5e7 and d["value"] > 0 and "roofline" in d
     assert d["roofline"]["algorithmic_flops_per_step"] <= d["roofline"]["padded_flops_per_step"]
+
+
+@pytest.mark.gpu
+@pytest.mark.timeout(400)
+def test_bench_plain_run_is_the_headline_only_and_its_outputs_repeat(tmp_path):
+    """`bench.py --steps K --warmup W` without --full: one line with the headline fields and none of the other legs; --dump-outputs
+    writes the last timed step's loss and outputs (finite, float32, <= 64 MB), and a second run with the same arguments writes the
+    same arrays (every step starts from the same state: only the last bits of the atomic gradient sums may differ, and they do not
+    reach the forward outputs)."""
+    import subprocess
+    import sys
+    import numpy as np
+    runs = []
+    for k in range(2):
+        out = tmp_path / f"run{k}"
+        cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2", "--rays", "1024", "--dump-outputs", str(out)]
+        p = subprocess.run(cmd, capture_output=True, text=True, timeout=180)
+        assert p.returncode == 0, p.stderr[-2000:]
+        lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, p.stdout[-2000:]
+        runs.append((json.loads(lines[0]), {f.name: np.load(f) for f in out.iterdir()}, out))
+    d, files, out = runs[0]
+    assert d["steps"] == 3 and d["warmup"] == 2 and d["dtype"] == "bf16" and d["unit"] == "rays/s" and d["higher_is_better"] is True
+    assert d["ms_per_step"] > 0 and abs(d["value"] - 1024 / (d["ms_per_step"] * 1e-3)) <= 1e-3 * d["value"]
+    for leg in ("roofline", "cpu_baseline", "eager_baseline", "f32_mode", "frame", "path_c", "path_b", "dropin_autograd", "small_step"):
+        assert leg not in d, leg
+    assert {"loss.npy", "rgb1.npy", "dist1.npy", "s1.npy", "w1.npy"} <= set(files)
+    assert sum(f.stat().st_size for f in out.iterdir()) <= 64 << 20
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in files.values())
+    assert files["rgb1.npy"].shape == (1024, 3) and abs(float(files["loss.npy"][0]) - d["final_loss"]) <= 1e-5 * abs(d["final_loss"])   # (the line rounds to 6 digits)
+    other = runs[1][1]
+    assert set(other) == set(files)
+    for k, a in files.items():
+        b = other[k]
+        assert a.shape == b.shape and np.allclose(a, b, rtol=1e-5, atol=1e-6 * float(np.abs(a).max() + 1e-30)), (k, float(np.abs(a - b).max()))

@@ -1,5 +1,5 @@
 #!/bin/bash
-# Round-end recipe on the GPU box (gpurun -- 'bash tools/round_end_validation.sh'): the full GPU suite, smoke(), the default bench line
+# Round-end recipe on the GPU box (bash tools/round_end_validation.sh from the repository root): the full GPU suite, smoke(), the `bench.py --full` line
 # (incl. its path-C / path-B / ERT legs), its rocprofv3 kernel-trace summary, the per-step launch lists, the GEMM step breakdown, the
 # stand-alone path-B / path-C benches and the HBM-traffic PMC passes.  Everything lands in gpurun_out/final/; the files that are judged
 # are then copied into profiles/ (profiles/README.md says which).
@@ -8,7 +8,7 @@ ROOT=$PWD
 O=gpurun_out/final; mkdir -p $O
 timeout -k 5 900 python -m pytest tests -x -q -m gpu 2>&1 | grep -v "^Extension" | tail -2 | tee $O/pytest.txt
 timeout -k 5 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -1 | tee $O/smoke.txt
-timeout -k 5 400 python bench.py 2>$O/bench.err | tail -1 > $O/bench_default.json.log; cut -c1-200 $O/bench_default.json.log
+timeout -k 5 400 python bench.py --full 2>$O/bench.err | tail -1 > $O/bench_default.json.log; cut -c1-200 $O/bench_default.json.log
 tr() { tag=$1; shift; ( cd /tmp && export TMPDIR=/tmp && timeout -k 5 300 rocprofv3 --kernel-trace --output-format csv -d $ROOT/$O/prof_$tag -o b -- python $ROOT/bench.py "$@" --no-frame --no-cpu --no-eager --no-f32 --no-dropin --no-paths --no-ert-scene > /dev/null 2>&1 < /dev/null ); }
 tr a4 --steps 4 --warmup 2; tr a14 --steps 14 --warmup 2
 python tools/rocprof_summary.py $(find $O/prof_a14 -name "b_kernel_trace.csv") > $O/bench_train_kernel_stats.txt; head -8 $O/bench_train_kernel_stats.txt | cut -c1-160
