@@ -314,6 +314,12 @@ int snerf_split8_cast(const float* src, long ld_src, long M, int C, int Cpad, vo
 
 int snerf_colsum_f32(const float* x, long ld, long M, int C, float* out, void* stream);
 int snerf_cast_pad(const float* src, long ld_src, long M, int C, int Cpad, void* dst, long ld_dst, int dtype, void* stream);
+/* Gradient w.r.t. the pre-embedded input x = [embedded pts (ic) | embedded views (icv)] of the classic NeRF (autograd of NeRF.forward(x),
+ * s-nerf/model/run_nerf_helpers.py:103-126): g0 [M, ld0] / g5 [M, ld5] = the fp32 data gradients that reach the point block through
+ * pts_linears.0 and (skip connection) pts_linears.5, gv [M, ldv] the one through views_linears.0 (null when icv = 0) ->
+ * dx [M, ld_dx >= ic + icv] fp32: dx[:, :ic] = g0 + g5, dx[:, ic:] = gv.  Any row strides, 4-byte alignment. */
+int snerf_classic_x_grad(const float* g0, long ld0, const float* g5, long ld5, const float* gv, long ldv, long M, int ic, int icv,
+                         float* dx, long ld_dx, void* stream);
 /* Refresh of the packed GEMM / fused-MLP operands after an optimiser step (the reference has no counterpart: torch.nn.Linear reads its
  * weights in place): dst[i] = flat[idx[i]] rounded to `dtype` (0 = fp32, 1 = bf16); idx -1 -> 0 (padding), -2 -> 1 (identity rows).  flat =
  * the fp32 parameter arena; idx (16-byte aligned) is built once per network by the host from the same slicing code that defines the
@@ -504,6 +510,20 @@ int snerf_fmlp_proposal_fwd(const void* E, long ldE, const void* wstream, long n
  * like the output of snerf_classic_embed, which remains the bit-exact fp32 statement of the encoding.  M < 2^31. */
 int snerf_fmlp_classic_pts_fwd(const float* pts, const float* viewdirs, long ldvd, int S, const void* wstream, long n_frags,
                                const float* bias, int n_blocks, float* raw, long M, void* stream);
+/* snerf_fmlp_classic_fwd on the caller's pre-embedded fp32 rows (NeRF.forward(x), run_nerf_helpers.py:103-126, as batchify(fn, netchunk)
+ * calls it, :450-474): x [M, ldx >= 90], columns [0, 63) = embedded points, [63, 90) = embedded view directions, any row stride, 4-byte
+ * alignment (a row- or column-sliced view of a wider tensor).  Rounded to bf16 in registers exactly as snerf_cast_pad rounds (nearest
+ * even): bit-identical to snerf_cast_pad into E / VE followed by snerf_fmlp_classic_fwd.  M < 2^31. */
+int snerf_fmlp_classic_x_fwd(const float* x, long ldx, const void* wstream, long n_frags, const float* bias, int n_blocks, float* raw,
+                             long M, void* stream);
+/* Its training forward: the stores of snerf_fmlp_classic_train_fwd (acts / act_ld / bits, same layout) plus the rounded inputs where the
+ * per-layer backward reads them -- xin / xin_ld: HOST arrays of 3 device pointers / row strides (elements): the operand of pts_linears.0
+ * ([M, >= 64] bf16), the head of the skip buffer ([M, >= 64]) and the view tail of [feature | views] ([M, >= 32]); pad columns written
+ * as zeros; pointers 16-byte aligned, strides multiples of 8.  Bit-identical to snerf_cast_pad into those three buffers followed by
+ * snerf_fmlp_classic_train_fwd.  M < 2^31. */
+int snerf_fmlp_classic_x_train_fwd(const float* x, long ldx, const void* wstream, long n_frags, const float* bias, int n_blocks,
+                                   float* raw, void* const* xin, const long* xin_ld, void* const* acts, const long* act_ld,
+                                   void* const* bits, long M, void* stream);
 /* Training forward of the two networks (autograd of NeRF.forward / proposal.forward in the reference): the same launch, which also
  * stores what the backward pass reads -- the bf16 outputs of the hidden layers and the ReLU bit masks of the 256-wide ones.
  * acts / act_ld: HOST arrays of device pointers / row strides (elements) -- classic: 10 = pts_linears.0 .. .7 (256 wide),

@@ -155,8 +155,11 @@ class NeRF(_ArenaModule):
         nn.init.uniform_(b, -bound, bound)
 
     def forward(self, x):
-        raise NotImplementedError("call run_network(inputs, viewdirs, model, embed_fn, embeddirs_fn): the encoding is fused "
-                                  "with the first layer, pre-embedded inputs never exist on this path")
+        """x [..., input_ch + input_ch_views] pre-embedded rows (run_nerf_helpers.py:103-126, as batchify(fn, netchunk) hands them over,
+        :450-474) -> [..., 4] = cat([rgb, alpha]) ([..., output_ch] with use_viewdirs=False), in the module's compute mode.  Parameter
+        gradients flow through autograd; so does the fp32 gradient w.r.t. x when x requires one.  run_network, which embeds inside the
+        first kernel, stays the faster route for callers that hold the points."""
+        return _forward_embedded(self, x)
 
 
 class NeRF_RGB(NeRF):
@@ -199,6 +202,68 @@ class _RunNetworkFn(torch.autograd.Function):
         grads = tuple(m.arena.g[n].clone() for n in m._pnames)
         m.arena.grad.zero_()      # leave the arena clean for whoever accumulates into it next
         return (None, None, None, None, None) + grads
+
+
+class _ForwardEmbeddedFn(torch.autograd.Function):
+    """NeRF.forward(x) / NeRF_RGB.forward(x) on rows x [M, ic + icv] fp32 (any row stride): the parameter gradients as _RunNetworkFn
+    returns them, plus d loss / d x when `want_dx`."""
+
+    @staticmethod
+    def forward(ctx, model: NeRF, x, keep, want_dx, *params):
+        M = x.shape[0]
+        saved = None
+        if M == 0:
+            raw = torch.zeros(0, 4 if model.use_viewdirs else model.output_ch, dtype=torch.float32, device=x.device)
+        else:
+            raw, saved = model.net.forward_embedded(x, keep)
+            if not model._alpha_head:
+                # NeRF_RGB: column 3 is the frozen alpha model's density on the same x (run_nerf_helpers.py:198-199, under no_grad)
+                raw_a, _ = model.alpha_model.net.forward_embedded(x, False)
+                raw[:, 3] = raw_a[:, 3]
+        ctx.model, ctx.saved, ctx.keep, ctx.want_dx, ctx.xshape = model, saved, keep, want_dx, tuple(x.shape)
+        return raw
+
+    @staticmethod
+    def backward(ctx, d_raw):
+        if not ctx.keep:
+            raise RuntimeError("NeRF.forward was executed without saved activations")
+        m = ctx.model
+        m.arena.grad.zero_()
+        dx = None
+        if ctx.saved is not None:
+            dx = m.net.backward(d_raw.contiguous(), ctx.saved, want_input_grad=ctx.want_dx)
+        elif ctx.want_dx:
+            dx = torch.zeros(ctx.xshape, dtype=torch.float32, device=d_raw.device)
+        ctx.saved = None
+        grads = tuple(m.arena.g[n].clone() for n in m._pnames)
+        m.arena.grad.zero_()      # leave the arena clean for whoever accumulates into it next
+        return (None, dx, None, None) + grads
+
+
+def _forward_embedded(model: NeRF, x):
+    C = model.input_ch + model.input_ch_views
+    if x.dim() == 0 or x.shape[-1] != C:
+        # (the reference fails in torch.split(x, [input_ch, input_ch_views], -1) the same way)
+        raise RuntimeError(f"NeRF.forward: the last dimension of x must be input_ch + input_ch_views = {C}, got {tuple(x.shape)}")
+    if not model._alpha_head:
+        a = model.alpha_model
+        if a is None:
+            raise RuntimeError("NeRF_RGB without an alpha_model cannot be evaluated (the reference raises TypeError here)")
+        if a.input_ch + a.input_ch_views != C:
+            raise RuntimeError(f"NeRF_RGB: the alpha model takes rows of {a.input_ch + a.input_ch_views} columns, x has {C}")
+        a._check_arena()
+    model._check_arena()
+    lead = x.shape[:-1]
+    rows = x.reshape(-1, C)
+    if rows.dtype != torch.float32:
+        rows = rows.float()                               # (as run_network does with its inputs)
+    if rows.stride(-1) != 1 or (rows.shape[0] > 1 and rows.stride(0) < C):
+        rows = rows.contiguous()
+    params = model.param_list()
+    want_dx = torch.is_grad_enabled() and rows.requires_grad
+    keep = torch.is_grad_enabled() and (want_dx or any(p.requires_grad for p in params))   # grad mode is off inside Function.forward
+    raw = _ForwardEmbeddedFn.apply(model, rows, keep, want_dx, *params)
+    return raw.reshape(*lead, raw.shape[-1])
 
 
 def run_network(inputs, viewdirs, fn, embed_fn, embeddirs_fn, netchunk=1024 * 64):

@@ -311,6 +311,33 @@ extern "C" int snerf_cast_pad(const float* src, long ld_src, long M, int C, int 
   return snerf_check_launch();
 }
 
+// Gradient w.r.t. the pre-embedded input of the classic NeRF (NeRF.forward(x), x = [embedded pts (ic) | embedded views (icv)]): the
+// point block reaches the network twice (pts_linears.0 and, through the skip, pts_linears.5), the view block once (views_linears.0).
+// dx[m, c] = g0[m, c] + g5[m, c] (c < ic), dx[m, ic + c] = gv[m, c] (c < icv; gv may be null when icv == 0).  One thread per element.
+__global__ __launch_bounds__(256) void classic_x_grad_kernel(const float* __restrict__ g0, long ld0, const float* __restrict__ g5, long ld5,
+                                                             const float* __restrict__ gv, long ldv, long M, int ic, int icv,
+                                                             float* __restrict__ dx, long ld_dx) {
+  const int C = ic + icv;
+  const long total = M * C;
+  for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
+    const long m = e / C;
+    const int c = (int)(e - m * C);
+    dx[m * ld_dx + c] = c < ic ? g0[m * ld0 + c] + g5[m * ld5 + c] : gv[m * ldv + (c - ic)];
+  }
+}
+
+extern "C" int snerf_classic_x_grad(const float* g0, long ld0, const float* g5, long ld5, const float* gv, long ldv, long M, int ic, int icv,
+                                    float* dx, long ld_dx, void* stream) {
+  if (M <= 0) return SNERF_OK;
+  if (g0 == nullptr || g5 == nullptr || dx == nullptr || ic < 1 || icv < 0 || (icv > 0 && gv == nullptr) || ld0 < ic || ld5 < ic ||
+      (icv > 0 && ldv < icv) || ld_dx < ic + icv)
+    return SNERF_ERR_ARG;
+  const long total = M * (ic + icv);
+  const int blocks = (int)((total + 255) / 256 < 65536 ? (total + 255) / 256 : 65536);
+  hipLaunchKernelGGL(classic_x_grad_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, g0, ld0, g5, ld5, gv, ldv, M, ic, icv, dx, ld_dx);
+  return snerf_check_launch();
+}
+
 // Appearance embedding of the live mip path (s-nerf/model/models.py:63-64 `emb = Embedding(N_vocab, 48)`, :153-159: condition =
 // cat([view encoding, emb(rays.app.long())]), tiled per sample like the view encoding, models.py:285-287): row m of the condition block
 // gets the embedding row of its ray's image index.  One thread per output element; sample_id as in snerf_mip_viewenc.

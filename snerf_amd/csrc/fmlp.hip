@@ -56,6 +56,8 @@ struct FmlpArgs {
   const float* pts;                 // classic network, in-kernel embedding: sample positions [M,3] ...
   const float* viewdirs; long ldvd; // ... and per-ray view directions [M / S, ldvd]
   int S;                            // samples per ray
+  const float* X; long ldX;         // classic network, pre-embedded inputs: fp32 rows [M, ldX] = [embedded pts (63) | embedded views (27)]
+  __bf16* xin[3]; long xin_ld[3];   // ... training forward: where the rounded inputs go (E [M, 64], SK[:, :64], V[:, 256:288])
   __bf16* act[12]; long act_ld[12]; // training forward: where the output of layer i is stored (bf16 [M, >= width], row stride act_ld)
   unsigned* bits[9];                // ... and the ReLU bit masks of the 256-wide layers (layout of ACT_RELU_BITS in gemm.hip); classic: [8] = views_linears.0 (128 wide)
   const char* wstream;              // n_chunks x 16 KiB of MFMA fragments in consumption order
@@ -372,6 +374,32 @@ __device__ __forceinline__ void embed_frags(const Vec3& x, bool hi_half, bf16x8 
 }
 
 struct ClassicInputs { bf16x8 e[4], ve[2]; };
+
+// ---- pre-embedded fp32 inputs (NeRF.forward(x), run_nerf_helpers.py:103-104: torch.split(x, [63, 27], -1)) -----------------------
+// Lane (row, half) reads the features k = 16 s + 8 half + e of its row: x[k] for the embedding fragments e[s], x[63 + k] (k < 27) for
+// the view fragments ve[s]; the pad features are zero.  A row of 90 floats is only 8-byte aligned, the view block (offset 63) only
+// 4-byte aligned, and a column slice of a wider tensor (any ldX) not even that: dword loads, no 16-byte vectors.  The round to bf16 is
+// the conversion snerf_cast_pad applies (round to nearest even), so this input flavour is bit-identical to snerf_cast_pad into bf16
+// buffers followed by the buffer-reading flavour.
+template <int K0, int N>
+__device__ __forceinline__ bf16x8 x_frag(const float* r) {      // features K0 .. K0 + 7 of a block of N (r: the block's first column)
+  typedef __attribute__((ext_vector_type(8))) float f32x8;
+  f32x8 v;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) v[e] = K0 + e < N ? r[K0 + e] : 0.f;
+  return __builtin_convertvector(v, bf16x8);
+}
+__device__ __forceinline__ ClassicInputs classic_x_inputs(const float* r, bool hi_half) {
+  ClassicInputs in;
+  if (hi_half) {
+    in.e[0] = x_frag<8, 63>(r); in.e[1] = x_frag<24, 63>(r); in.e[2] = x_frag<40, 63>(r); in.e[3] = x_frag<56, 63>(r);
+    in.ve[0] = x_frag<8, 27>(r + 63); in.ve[1] = x_frag<24, 27>(r + 63);
+  } else {
+    in.e[0] = x_frag<0, 63>(r); in.e[1] = x_frag<16, 63>(r); in.e[2] = x_frag<32, 63>(r); in.e[3] = x_frag<48, 63>(r);
+    in.ve[0] = x_frag<0, 27>(r + 63); in.ve[1] = x_frag<16, 27>(r + 63);
+  }
+  return in;
+}
 __device__ __forceinline__ ClassicInputs classic_embed_inputs(const float* pp, const float* vp, bool hi_half) {
   const Vec3 x{pp[0], pp[1], pp[2]}, v{vp[0], vp[1], vp[2]};
   ClassicInputs r;
@@ -412,8 +440,12 @@ __device__ __forceinline__ void ctx_start(C& c, char* smem, const char* wstream,
 #define FMLP_CLASSIC_BLOCKS 78
 #define FMLP_CLASSIC 0
 #define FMLP_PROPOSAL 1
+// where the classic network's inputs come from: bf16 operand rows (E, VE), the sample positions (in-kernel encoding), fp32 rows x
+#define FM_IN_ROWS 0
+#define FM_IN_PTS 1
+#define FM_IN_X 2
 
-template <int NET, bool EMBED, bool STORE>
+template <int NET, int IN, bool STORE>
 __global__ __launch_bounds__(64 * FM_WAVES, 2) void fmlp_kernel(FmlpArgs a) {   // (second argument: waves per SIMD -> at most 256 VGPRs)
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -430,11 +462,30 @@ __global__ __launch_bounds__(64 * FM_WAVES, 2) void fmlp_kernel(FmlpArgs a) {   
 
     if constexpr (NET == FMLP_CLASSIC) {
       bf16x8 e[4], ve[2], p[16], q[16];
-      if constexpr (EMBED) {
+      if constexpr (IN == FM_IN_PTS) {
         const ClassicInputs in = classic_embed_inputs(a.pts + row * 3, a.viewdirs + (long)((unsigned)row / (unsigned)a.S) * a.ldvd, half != 0);   // (M < 2^31 rows, checked by the launcher)
 #pragma unroll
         for (int i = 0; i < 4; ++i) e[i] = in.e[i];
         ve[0] = in.ve[0]; ve[1] = in.ve[1];
+      } else if constexpr (IN == FM_IN_X) {
+        const ClassicInputs in = classic_x_inputs(a.X + row * a.ldX, half != 0);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) e[i] = in.e[i];
+        ve[0] = in.ve[0]; ve[1] = in.ve[1];
+        if constexpr (STORE) {
+          // the rounded inputs where the per-layer backward reads them (weight gradients of pts_linears.0 / .5 / views_linears.0):
+          // lane (row, half) holds columns 16 s + 8 half .. + 7 of its row -- 16-byte streaming stores, as the layer outputs
+          if (row_ok) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+              __builtin_nontemporal_store(__builtin_bit_cast(fm_u32x4, e[i]), (fm_u32x4*)(a.xin[0] + row * a.xin_ld[0] + 16 * i + 8 * half));
+              __builtin_nontemporal_store(__builtin_bit_cast(fm_u32x4, e[i]), (fm_u32x4*)(a.xin[1] + row * a.xin_ld[1] + 16 * i + 8 * half));
+            }
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+              __builtin_nontemporal_store(__builtin_bit_cast(fm_u32x4, ve[i]), (fm_u32x4*)(a.xin[2] + row * a.xin_ld[2] + 16 * i + 8 * half));
+          }
+        }
       } else {
         load_rows<4>(a.E, a.ldE, row, half, e);
         load_rows<2>(a.VE, a.ldVE, row, half, ve);
@@ -1272,17 +1323,17 @@ __global__ __launch_bounds__(256) void fcolour_colsum_fold_kernel(const float* _
   }
 }
 
-template <int NET, bool EMBED, bool STORE = false>
+template <int NET, int IN, bool STORE = false>
 static int fmlp_launch(const FmlpArgs& a, int expect_frags, int expect_blocks, long n_frags, void* stream) {
   if (a.M <= 0) return SNERF_OK;
   if (n_frags != expect_frags || a.n_blocks != expect_blocks || a.n_blocks > FM_BIAS_MAX || (n_frags % FM_CHUNK) != 0) return SNERF_ERR_ARG;
   if (a.wstream == nullptr || a.bias == nullptr || a.out == nullptr || (((uintptr_t)a.wstream) & 15)) return SNERF_ERR_ARG;
-  if (!EMBED && (a.E == nullptr || (a.ldE % 8) != 0 || (((uintptr_t)a.E) & 15))) return SNERF_ERR_ARG;
+  if (IN == FM_IN_ROWS && (a.E == nullptr || (a.ldE % 8) != 0 || (((uintptr_t)a.E) & 15))) return SNERF_ERR_ARG;
   constexpr int LDS = FM_RING * FM_SLOT + FM_BIAS_MAX * 128 + (STORE ? FM_WAVES * 4096 : 0);   // + the transposition slabs of the training stores
   static bool attr_set = false;
   static int n_cu = 256;
   if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)fmlp_kernel<NET, EMBED, STORE>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+    (void)hipFuncSetAttribute((const void*)fmlp_kernel<NET, IN, STORE>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
     int dev = 0;
     hipDeviceProp_t prop;
     if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
@@ -1290,7 +1341,7 @@ static int fmlp_launch(const FmlpArgs& a, int expect_frags, int expect_blocks, l
     attr_set = true;
   }
   const int grid = a.tiles < n_cu * FM_WG_PER_CU ? a.tiles : n_cu * FM_WG_PER_CU;
-  hipLaunchKernelGGL((fmlp_kernel<NET, EMBED, STORE>), dim3(grid), dim3(64 * FM_WAVES), LDS, (hipStream_t)stream, a);
+  hipLaunchKernelGGL((fmlp_kernel<NET, IN, STORE>), dim3(grid), dim3(64 * FM_WAVES), LDS, (hipStream_t)stream, a);
   return snerf_check_launch();
 }
 
@@ -1301,7 +1352,7 @@ extern "C" int snerf_fmlp_classic_fwd(const void* E, long ldE, const void* VE, l
   FmlpArgs a{};
   a.E = (const __bf16*)E; a.ldE = ldE; a.VE = (const __bf16*)VE; a.ldVE = ldVE; a.S = 1; a.wstream = (const char*)wstream; a.bias = bias; a.out = raw;
   a.M = M; a.tiles = (int)((M + FM_TILE_ROWS - 1) / FM_TILE_ROWS); a.n_chunks = (int)(n_frags / FM_CHUNK); a.n_blocks = n_blocks;
-  return fmlp_launch<FMLP_CLASSIC, false>(a, FMLP_CLASSIC_FRAGS, FMLP_CLASSIC_BLOCKS, n_frags, stream);
+  return fmlp_launch<FMLP_CLASSIC, FM_IN_ROWS>(a, FMLP_CLASSIC_FRAGS, FMLP_CLASSIC_BLOCKS, n_frags, stream);
 }
 
 // Training forward of the same network: additionally stores the outputs of the ten hidden layers for the backward pass --
@@ -1326,7 +1377,7 @@ extern "C" int snerf_fmlp_classic_train_fwd(const void* E, long ldE, const void*
       a.bits[i] = (unsigned*)bits[i];
     }
   }
-  return fmlp_launch<FMLP_CLASSIC, false, true>(a, FMLP_CLASSIC_FRAGS, FMLP_CLASSIC_BLOCKS, n_frags, stream);
+  return fmlp_launch<FMLP_CLASSIC, FM_IN_ROWS, true>(a, FMLP_CLASSIC_FRAGS, FMLP_CLASSIC_BLOCKS, n_frags, stream);
 }
 
 // the same network with the positional encodings computed in the kernel: pts [M,3] fp32 sample positions, viewdirs [M / S, ldvd]
@@ -1337,7 +1388,51 @@ extern "C" int snerf_fmlp_classic_pts_fwd(const float* pts, const float* viewdir
   FmlpArgs a{};
   a.pts = pts; a.viewdirs = viewdirs; a.ldvd = ldvd; a.S = S; a.wstream = (const char*)wstream; a.bias = bias; a.out = raw;
   a.M = M; a.tiles = (int)((M + FM_TILE_ROWS - 1) / FM_TILE_ROWS); a.n_chunks = (int)(n_frags / FM_CHUNK); a.n_blocks = n_blocks;
-  return fmlp_launch<FMLP_CLASSIC, true>(a, FMLP_CLASSIC_FRAGS, FMLP_CLASSIC_BLOCKS, n_frags, stream);
+  return fmlp_launch<FMLP_CLASSIC, FM_IN_PTS>(a, FMLP_CLASSIC_FRAGS, FMLP_CLASSIC_BLOCKS, n_frags, stream);
+}
+
+// the same network on pre-embedded fp32 rows x [M, ldX >= 90] (NeRF.forward(x)): columns [0, 63) = embedded points, [63, 90) =
+// embedded view directions, any row stride, 4-byte alignment.  Rounded to bf16 in registers exactly as snerf_cast_pad does.
+static int fmlp_x_args(FmlpArgs& a, const float* x, long ldx, const void* wstream, long n_frags, const float* bias, int n_blocks, float* raw, long M) {
+  if (x == nullptr || ldx < 90 || (((uintptr_t)x) & 3) || raw == nullptr || (((uintptr_t)raw) & 15) || M >= (1L << 31)) return SNERF_ERR_ARG;
+  a.X = x; a.ldX = ldx; a.S = 1; a.wstream = (const char*)wstream; a.bias = bias; a.out = raw;
+  a.M = M; a.tiles = (int)((M + FM_TILE_ROWS - 1) / FM_TILE_ROWS); a.n_chunks = (int)(n_frags / FM_CHUNK); a.n_blocks = n_blocks;
+  return SNERF_OK;
+}
+
+extern "C" int snerf_fmlp_classic_x_fwd(const float* x, long ldx, const void* wstream, long n_frags, const float* bias, int n_blocks, float* raw,
+                                        long M, void* stream) {
+  if (M <= 0) return SNERF_OK;
+  FmlpArgs a{};
+  const int rc = fmlp_x_args(a, x, ldx, wstream, n_frags, bias, n_blocks, raw, M);
+  if (rc != SNERF_OK) return rc;
+  return fmlp_launch<FMLP_CLASSIC, FM_IN_X>(a, FMLP_CLASSIC_FRAGS, FMLP_CLASSIC_BLOCKS, n_frags, stream);
+}
+
+// training forward on x: snerf_fmlp_classic_train_fwd's stores (acts / act_ld / bits) plus the rounded inputs -- xin[0] = E [M, >= 64]
+// (the operand of pts_linears.0), xin[1] = the head of the skip buffer (64 columns), xin[2] = the view tail of [feature | views] (32
+// columns); columns 63 / 27.. are written as zeros.  Every pointer 16-byte aligned, every stride a multiple of 8.
+extern "C" int snerf_fmlp_classic_x_train_fwd(const float* x, long ldx, const void* wstream, long n_frags, const float* bias, int n_blocks,
+                                              float* raw, void* const* xin, const long* xin_ld, void* const* acts, const long* act_ld,
+                                              void* const* bits, long M, void* stream) {
+  if (M <= 0) return SNERF_OK;
+  if (xin == nullptr || xin_ld == nullptr || acts == nullptr || act_ld == nullptr || bits == nullptr) return SNERF_ERR_ARG;
+  FmlpArgs a{};
+  const int rc = fmlp_x_args(a, x, ldx, wstream, n_frags, bias, n_blocks, raw, M);
+  if (rc != SNERF_OK) return rc;
+  for (int i = 0; i < 3; ++i) {
+    if (xin[i] == nullptr || (((uintptr_t)xin[i]) & 15) || (xin_ld[i] % 8) != 0 || xin_ld[i] < (i == 2 ? 32 : 64)) return SNERF_ERR_ARG;
+    a.xin[i] = (__bf16*)xin[i]; a.xin_ld[i] = xin_ld[i];
+  }
+  for (int i = 0; i < 10; ++i) {
+    if (acts[i] == nullptr || (((uintptr_t)acts[i]) & 15) || (act_ld[i] % 8) != 0) return SNERF_ERR_ARG;
+    a.act[i] = (__bf16*)acts[i]; a.act_ld[i] = act_ld[i];
+    if (i < 9) {
+      if (bits[i] == nullptr || (((uintptr_t)bits[i]) & 15)) return SNERF_ERR_ARG;
+      a.bits[i] = (unsigned*)bits[i];
+    }
+  }
+  return fmlp_launch<FMLP_CLASSIC, FM_IN_X, true>(a, FMLP_CLASSIC_FRAGS, FMLP_CLASSIC_BLOCKS, n_frags, stream);
 }
 
 extern "C" int snerf_fmlp_proposal_fwd(const void* E, long ldE, const void* wstream, long n_frags, const float* bias, int n_blocks,
@@ -1346,7 +1441,7 @@ extern "C" int snerf_fmlp_proposal_fwd(const void* E, long ldE, const void* wstr
   a.E = (const __bf16*)E; a.ldE = ldE; a.S = 1; a.wstream = (const char*)wstream; a.bias = bias; a.out = raw_density;
   a.M = M; a.tiles = (int)((M + FM_TILE_ROWS - 1) / FM_TILE_ROWS); a.n_chunks = (int)(n_frags / FM_CHUNK); a.n_blocks = n_blocks;
   // 8 x 6 + 3 x 128 + 16 fragments; 32 + 1 blocks
-  return fmlp_launch<FMLP_PROPOSAL, false>(a, 448, 33, n_frags, stream);
+  return fmlp_launch<FMLP_PROPOSAL, FM_IN_ROWS>(a, 448, 33, n_frags, stream);
 }
 
 // training forward of the proposal MLP: acts[0..3] = outputs of layers.0 .. .3 (256 wide)
@@ -1363,7 +1458,7 @@ extern "C" int snerf_fmlp_proposal_train_fwd(const void* E, long ldE, const void
     if (bits[i] == nullptr) return SNERF_ERR_ARG;
     a.act[i] = (__bf16*)acts[i]; a.act_ld[i] = act_ld[i]; a.bits[i] = (unsigned*)bits[i];
   }
-  return fmlp_launch<FMLP_PROPOSAL, false, true>(a, 448, 33, n_frags, stream);
+  return fmlp_launch<FMLP_PROPOSAL, FM_IN_ROWS, true>(a, 448, 33, n_frags, stream);
 }
 
 // ---- colour head (cond_layers.0..2 + rgb_layer of the mip path's NeRF MLP, hidden 1024) -------------------------------------------

@@ -525,6 +525,7 @@ class ClassicNeRFNet(_Net):
         self.alpha_head = bool(alpha_head)
         self.fused = True                 # inference through the fused register-resident kernel where it applies (fused_ok)
         self.fused_embed = True           # ... with the positional encodings computed inside it (False: separate embedding kernel)
+        self.fused_x = True               # forward_embedded: the kernel reads the caller's fp32 rows itself (False: snerf_cast_pad into operand buffers first)
 
     @staticmethod
     def param_shapes(D=8, W=256, input_ch=63, input_ch_views=27, skips=(4,), alpha_head=True, output_ch=0):
@@ -630,16 +631,24 @@ class ClassicNeRFNet(_Net):
     def forward_fused_train(self, pts, viewdirs, S):
         """Training forward: the exact embedding kernel + ONE fused kernel that also stores the hidden activations in the buffers the
         per-layer backward reads (same `saved` structure as the per-layer forward)."""
+        W, Pw = self.Wd, self.Pw
+
+        def run(E, SK, V, OUT, acts, words):
+            ops.classic_embed(pts, viewdirs, S, (self.ic - 3) // 6, (self.icv - 3) // 6, E, SK[:, :Pw], Pw, V[:, W:], self.Vw, self.dt)
+            ops.fmlp_classic_train_fwd(E, V[:, W:], self.fstream, self.fbias, OUT, acts, words)
+        return self._fused_train(pts.shape[0], run)
+
+    def _fused_train(self, M, run):
+        """buffers of the fused training forward; run(E, SK, V, OUT, acts, words) fills the inputs E / SK[:, :Pw] / V[:, W:] and launches"""
         self._fused_ready()
         self.ensure_packed(True)
-        M, W, Pw = pts.shape[0], self.Wd, self.Pw
+        W, Pw = self.Wd, self.Pw
         E, SK, V = self.buf(M, Pw), self.buf(M, Pw + W), self.buf(M, W + self.Vw)
-        ops.classic_embed(pts, viewdirs, S, (self.ic - 3) // 6, (self.icv - 3) // 6, E, SK[:, :Pw], Pw, V[:, W:], self.Vw, self.dt)
         ys = [SK[:, Pw:] if i == self.skip else self.buf(M, W) for i in range(self.D)]
         HV, OUT = self.buf(M, W // 2), self.buf(M, 4, f32=True)
         words = [torch.empty(ops.mask_bits_words(M, W), dtype=torch.int32, device=self.dev) for _ in range(self.D)]
         words.append(torch.empty(ops.mask_bits_words(M, W // 2), dtype=torch.int32, device=self.dev))     # views_linears.0
-        ops.fmlp_classic_train_fwd(E, V[:, W:], self.fstream, self.fbias, OUT, ys + [V[:, :W], HV], words)
+        run(E, SK, V, OUT, ys + [V[:, :W], HV], words)
         for y, w in zip(ys, words):                                   # the data-gradient GEMMs take their ReLU masks from the bits
             self._bits[(y.data_ptr(), M)] = (w, W)
         acts, x, k = [], E, Pw
@@ -667,17 +676,66 @@ class ClassicNeRFNet(_Net):
             if not keep:
                 return self.forward_fused(pts, viewdirs, S), None
             return self.forward_fused_train(pts, viewdirs, S)
+        Pw, L = self.Pw, (self.ic - 3) // 6
+
+        def ingest(E, SK0, V1):
+            if V1 is None:
+                ops.classic_embed(pts, None, S, L, 0, E, SK0, Pw, None, 0, self.dt)
+            else:
+                ops.classic_embed(pts, viewdirs, S, L, (self.icv - 3) // 6, E, SK0, Pw, V1, self.Vw, self.dt)
+        return self._forward_layers(pts.shape[0], keep, ingest)
+
+    def _ingest_x(self, x):
+        """the column blocks of pre-embedded rows x into the operand layouts (compute dtype, split forms included): E, the head of the
+        skip buffer and the view tail of [feature | views] (V1 None: no view branch)"""
+        ic, icv, dt = self.ic, self.icv, self.dt
+
+        def ingest(E, SK0, V1):
+            ops.cast_pad(x[:, :ic], ic, E, self.Pw, dt)
+            ops.cast_pad(x[:, :ic], ic, SK0, self.Pw, dt)
+            if V1 is not None:
+                ops.cast_pad(x[:, ic:ic + icv], icv, V1, self.Vw, dt)
+        return ingest
+
+    def forward_embedded(self, x, keep: bool):
+        """NeRF.forward on pre-embedded rows (run_nerf_helpers.py:103-126): x [M, >= ic + icv] fp32 = [embedded pts | embedded views], unit
+        column stride, any row stride -> raw [M,4] (or [M, output_ch]) fp32 (+ saved activations when keep; backward() takes them, with
+        `want_input_grad` for the gradient w.r.t. x).  The fused kernel reads x itself (fused_x) or behind snerf_cast_pad into its operand
+        buffers; elsewhere the per-layer launches on cast_pad'ed operands."""
+        M, W, Pw, ic, icv = x.shape[0], self.Wd, self.Pw, self.ic, self.icv
+        if not self.fused_ok():
+            return self._forward_layers(M, keep, self._ingest_x(x))
+        if self.fused_x and M < (1 << 31):
+            if not keep:
+                self._fused_ready()
+                OUT = self.buf(M, 4, f32=True)
+                ops.fmlp_classic_x_fwd(x, self.fstream, self.fbias, OUT)
+                return OUT, None
+            return self._fused_train(M, lambda E, SK, V, OUT, acts, words: ops.fmlp_classic_x_train_fwd(
+                x, self.fstream, self.fbias, OUT, [E, SK[:, :Pw], V[:, W:]], acts, words))
+        if not keep:                                          # (the two-launch route: the A/B partner of the fused-x launch)
+            self._fused_ready()
+            E, VE, OUT = self.buf(M, 64), self.buf(M, 32), self.buf(M, 4, f32=True)
+            ops.cast_pad(x[:, :ic], ic, E, 64, self.dt)
+            ops.cast_pad(x[:, ic:ic + icv], icv, VE, 32, self.dt)
+            ops.fmlp_classic_fwd(E, VE, self.fstream, self.fbias, OUT)
+            return OUT, None
+
+        def run(E, SK, V, OUT, acts, words):
+            self._ingest_x(x)(E, SK[:, :Pw], V[:, W:])
+            ops.fmlp_classic_train_fwd(E, V[:, W:], self.fstream, self.fbias, OUT, acts, words)
+        return self._fused_train(M, run)
+
+    def _forward_layers(self, M, keep, ingest):
+        """the per-layer launches; ingest(E, SK[:, :Pw], V[:, W:] or None) writes the network's inputs"""
         self.ensure_packed(keep)
-        M, W, Pw = pts.shape[0], self.Wd, self.Pw
+        W, Pw = self.Wd, self.Pw
         E = self.buf(M, Pw)
         SK = self.buf(M, Pw + W)
         noviews = self.output_ch > 0
         V = None if noviews else self.buf(M, W + self.Vw)
         cs = self.cs                                          # (logical column ranges: twice as wide physically in the split layouts)
-        if noviews:
-            ops.classic_embed(pts, None, S, (self.ic - 3) // 6, 0, E, cs(SK, 0, Pw), Pw, None, 0, self.dt)
-        else:
-            ops.classic_embed(pts, viewdirs, S, (self.ic - 3) // 6, (self.icv - 3) // 6, E, cs(SK, 0, Pw), Pw, cs(V, W), self.Vw, self.dt)
+        ingest(E, cs(SK, 0, Pw), None if noviews else cs(V, W))
         acts = []
         x, k = E, Pw
         pp = [self.buf(M, W), self.buf(M, W)] if not keep else None
@@ -717,17 +775,60 @@ class ClassicNeRFNet(_Net):
         gw[:, :self.ic] += tmp[:, :self.ic]
         gw[:, self.ic:] += tmp[:, Pw:]
 
-    def backward(self, d_raw, saved):
-        """d_raw [M,4] fp32 -> accumulates parameter gradients into the arena (compute="bf16x3_fwd" / "f16f8" / "fp16": _Net._bwd, _scaled_backward)."""
+    def backward(self, d_raw, saved, want_input_grad=False):
+        """d_raw [M,4] fp32 -> accumulates parameter gradients into the arena (compute="bf16x3_fwd" / "f16f8" / "fp16": _Net._bwd, _scaled_backward).
+        `want_input_grad` -> the fp32 gradient [M, ic + icv] w.r.t. the pre-embedded rows of forward_embedded (else None)."""
+        if want_input_grad:
+            self._xgrad_ready()                               # (outside _bwd: the plan is built in the network's own operand layouts)
         with self._bwd():
             if self._fp16_backward():
-                return self._scaled_backward([d_raw], lambda g: self._backward(g[0], saved))
-            return self._backward(d_raw, saved)
+                return self._scaled_backward([d_raw], lambda g: self._backward(g[0], saved, want_input_grad))
+            return self._backward(d_raw, saved, want_input_grad)
 
-    def _backward(self, d_raw, saved):
+    def _xgrad_ready(self):
+        """W^T of the three weight-column blocks that read the input rows -- pts_linears.0, the point columns of the skip layer, the view
+        columns of views_linears.0 -- in a gather plan of their own (refreshed only for callers that ask for the input gradient)"""
+        v = self.version_fn()
+        if getattr(self, "_xtw_version", None) == v:
+            return
+        with torch.no_grad():
+            if "xgrad" not in self._plans:
+                tw, self.tw = self.tw, {}
+                try:
+                    def fill():
+                        self._pack_dgrad_cols("x0", [("pts_linears.0", 0)], self.ic)
+                        self._pack_dgrad_cols("x5", [(f"pts_linears.{self.skip + 1}", 0)], self.ic)
+                        if self.output_ch == 0:
+                            self._pack_dgrad_cols("xv", [("views_linears.0", self.Wd)], self.icv)
+                    plan, swap = self._build_plan(fill)
+                    self._plans["xgrad"] = (plan, swap(self.tw))
+                finally:
+                    self.tw = tw
+            plan, self._xtw = self._plans["xgrad"]
+            plan.refresh()
+        self._xtw_version = v
+
+    def _input_grad_x(self, dz0, dz5, dhv):
+        """d loss / d x of forward_embedded from the data gradients of pts_linears.0, of the skip layer and of views_linears.0 (None: no
+        view branch, whose input columns then get zeros): three data-gradient GEMMs with fp32 outputs + one summing launch"""
+        M, W, ic, icv = dz0.shape[0], self.Wd, self.ic, self.icv
+
+        def grad(key, dZ, K, width):
+            out = self.buf(M, width, f32=True)
+            ops.linear_fwd(dZ, self._xtw[key], None, out, K, width, ACT_NONE, self.dt, out_f32=True, variant=self.variant)
+            return out
+        g0, g5 = grad("x0", dz0, W, ic), grad("x5", dz5, W, ic)
+        gv = None if dhv is None or icv == 0 else grad("xv", dhv, W // 2, icv)
+        dx = torch.empty(M, ic + icv, dtype=torch.float32, device=self.dev) if gv is not None or icv == 0 else \
+            torch.zeros(M, ic + icv, dtype=torch.float32, device=self.dev)
+        ops.classic_x_grad(g0, g5, gv, ic, 0 if gv is None else icv, dx)
+        return dx
+
+    def _backward(self, d_raw, saved, want_input_grad=False):
         acts, V, HV, SK, E = saved[:5]
         W, Pw, g, M = self.Wd, self.Pw, self.g, d_raw.shape[0]
         ah = self.alpha_head
+        dzs = {} if want_input_grad else None                 # layer -> d pre-activation, for the input gradient
         if self.output_ch > 0:
             oc, x7 = self.output_ch, acts[-1][2]
             self.colsum(d_raw, oc, self.gB("output_linear"))
@@ -735,8 +836,8 @@ class ClassicNeRFNet(_Net):
             self.wgrad("output_linear", dz, x7, oc, W)
             dZ = self.buf(M, W)
             self.dgrad("out", dz, roundup(oc, g), dZ, W, mask=x7, colsum=self.gB(f"pts_linears.{self.D - 1}"))
-            self._trunk_backward(dZ, acts, SK, E)
-            return
+            self._trunk_backward(dZ, acts, SK, E, dzs)
+            return self._input_grad_x(dzs[0], dzs[self.skip + 1], None) if want_input_grad else None
         self.colsum(d_raw, 3, self.gB("rgb_linear"))
         if ah:
             self.colsum(d_raw[:, 3:], 1, self.gB("alpha_linear"))
@@ -762,7 +863,7 @@ class ClassicNeRFNet(_Net):
                     self.wgrad(n, dZ, E, W, self.ic)
                 else:
                     self.wgrad(n, dZ, x, W, W)
-            return
+            return self._input_grad_x(dZs[-1], dZs[self.D - 2 - self.skip], dHV) if want_input_grad else None
         dHV = self.buf(M, W // 2)
         self.dgrad("rgb", dz, g, dHV, W // 2, mask=HV, colsum=self.gB("views_linears.0"))
         self.wgrad("views_linears.0", dHV, V, W // 2, W + self.icv)
@@ -775,15 +876,18 @@ class ClassicNeRFNet(_Net):
             self.wgrad("alpha_linear", self.cs(DB, W), x7, 1, W)
         dZ = self.buf(M, W)
         self.dgrad("fa", DB, W + (g if ah else 0), dZ, W, mask=x7, colsum=self.gB(f"pts_linears.{self.D - 1}"))
-        self._trunk_backward(dZ, acts, SK, E)
+        self._trunk_backward(dZ, acts, SK, E, dzs)
+        return self._input_grad_x(dzs[0], dzs[self.skip + 1], dHV) if want_input_grad else None
 
-    def _trunk_backward(self, dZ, acts, SK, E):
+    def _trunk_backward(self, dZ, acts, SK, E, dzs=None):
         """weight gradients of pts_linears.{D-1 .. 0} and the data gradients between them, from dZ = d loss / d (pre-activation of the
-        last trunk layer)"""
+        last trunk layer); `dzs` (a dict): receives the d pre-activation of every trunk layer"""
         W, M = self.Wd, dZ.shape[0]
         for i in range(self.D - 1, -1, -1):
             x, k, y = acts[i]
             n = f"pts_linears.{i}"
+            if dzs is not None:
+                dzs[i] = dZ
             if i == self.skip + 1:
                 self._wgrad_skip(n, dZ, SK)
             elif i == 0:

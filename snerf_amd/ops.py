@@ -203,6 +203,35 @@ def fmlp_classic_pts_fwd(pts, viewdirs, S, stream, bias, raw):
               bias.numel() // 32, _p(raw), pts.shape[0], _stream())
 
 
+def _x_rows(x):
+    """pre-embedded classic input rows: fp32 [M, >= 90] CUDA view with unit column stride (any row stride)"""
+    assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1 and x.shape[1] >= 90, "expected fp32 [M, >= 90] rows"
+    assert x.shape[0] < (1 << 31) and (x.shape[0] <= 1 or x.stride(0) >= 90)
+    return x
+
+
+def fmlp_classic_x_fwd(x, stream, bias, raw):
+    """fmlp_classic_fwd on the caller's pre-embedded fp32 rows x [M, >= 90] = [embedded pts (63) | embedded views (27)] (any row
+    stride; rounded to bf16 in the kernel as cast_pad rounds) -> raw [M,4] fp32."""
+    _x_rows(x); _chk2d(raw, torch.float32)
+    assert stream.dtype == torch.bfloat16 and stream.is_contiguous() and bias.dtype == torch.float32 and raw.is_contiguous() and raw.shape == (x.shape[0], 4)
+    _lib.call("snerf_fmlp_classic_x_fwd", _p(x), max(x.stride(0), 90), _p(stream), stream.shape[0], _p(bias), bias.numel() // 32, _p(raw),
+              x.shape[0], _stream())
+
+
+def fmlp_classic_x_train_fwd(x, stream, bias, raw, xin, acts, bits):
+    """fmlp_classic_train_fwd on pre-embedded fp32 rows x (as fmlp_classic_x_fwd); additionally writes the bf16-rounded inputs into
+    `xin` = [E [M, >= 64], skip-buffer head [M, >= 64], view tail [M, >= 32]] (bf16 row-major views, 16-byte aligned, row strides % 8 == 0)."""
+    import ctypes
+    _x_rows(x); _chk2d(raw, torch.float32)
+    assert stream.dtype == torch.bfloat16 and stream.is_contiguous() and bias.dtype == torch.float32 and raw.is_contiguous() and raw.shape == (x.shape[0], 4)
+    assert len(bits) == 9 and len(xin) == 3
+    M = x.shape[0]
+    ptrs, lds, bp = _act_arrays(acts, bits, M, [256] * 9 + [128])
+    xp, xl, _ = _act_arrays(xin, [], M, [64, 64, 32])
+    _lib.call("snerf_fmlp_classic_x_train_fwd", _p(x), max(x.stride(0), 90), _p(stream), stream.shape[0], _p(bias), bias.numel() // 32, _p(raw),
+              ctypes.addressof(xp), ctypes.addressof(xl), ctypes.addressof(ptrs), ctypes.addressof(lds), ctypes.addressof(bp), M, _stream())
+
 def fmlp_proposal_fwd(E, stream, bias, raw_density):
     """The proposal MLP 96 -> 4 x 256 -> 1 in one launch: E [M,>=96] bf16 IPE rows -> raw density [M,1] fp32."""
     _chk2d(E, torch.bfloat16)
@@ -804,6 +833,18 @@ def cast_pad(src, C, dst, Cpad, dt):
     _chk2d(src, torch.float32)
     _lib.call("snerf_cast_pad", _p(src), src.stride(0), src.shape[0], C, Cpad, _p(dst), dst.stride(0), dt, _stream())
 
+
+def classic_x_grad(g0, g5, gv, ic, icv, dx):
+    """gradient w.r.t. the classic network's pre-embedded input: dx[:, :ic] = g0 + g5 (the data gradients reaching the point block
+    through pts_linears.0 and the skip layer), dx[:, ic:ic + icv] = gv (through views_linears.0; None when icv == 0).  fp32 2-D views."""
+    _chk2d(g0, torch.float32); _chk2d(g5, torch.float32); _chk2d(dx, torch.float32)
+    M = dx.shape[0]
+    assert g0.shape[0] == g5.shape[0] == M and g0.shape[1] >= ic and g5.shape[1] >= ic and dx.shape[1] >= ic + icv
+    if icv > 0:
+        _chk2d(gv, torch.float32)
+        assert gv.shape[0] == M and gv.shape[1] >= icv
+    _lib.call("snerf_classic_x_grad", _p(g0), g0.stride(0), _p(g5), g5.stride(0), _p(gv), 0 if gv is None else gv.stride(0), M, int(ic),
+              int(icv), _p(dx), dx.stride(0), _stream())
 
 def gather_pack(flat, idx, dst, tiles=None):
     """dst[i] = flat[idx[i]] (idx -1 -> 0, -2 -> 1) rounded to dst's dtype: all packed operands of a network in one launch.  `tiles` (int32
