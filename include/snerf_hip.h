@@ -408,6 +408,39 @@ int snerf_mip_loss_tail(const float* rgb, const float* tgt, const float* dist1, 
 int snerf_zip_pixels_to_rays(const int* pix_x, const int* pix_y, const int* cam_idx, const float* pixtocams, const float* camtoworlds,
                              int ncam, long N, float* origins, float* directions, float* viewdirs, float* radii, float* imageplane,
                              float* base_x, float* base_y, void* stream);
+/* Device-resident training batchers: the training set stays in device memory and ONE launch draws, casts and gathers one batch
+ * (positions [i0, i1) of a global batch of n rays: a rank's slice), with no host work and no sync.  The draws come from a
+ * counter-based generator (Philox4x32-10 keyed by `seed`, counted by the step, the ray's position in the global batch and the draw
+ * number; algorithm in csrc/callers.hip) instead of numpy's; given the drawn pixels, everything else is what snerf_pinhole_rays
+ * (training = 1) / snerf_zip_pixels_to_rays compute, bit for bit.  `counter` = int64 [2] device words {step, 0}: the launch draws
+ * the batch of step counter[0] and advances it by one (graph-safe: a replayed launch draws the next batch).  uint8 images
+ * (images_u8 = 1) decode to float32(k / 255.0), computed in double.  n = 0 is a no-op; bad arguments return 1 before any launch.
+ *
+ * Path A (s-nerf/dataloader/rayset.py:124-151 SingleImage + sample_utils.py:92-211 sample_single_img, no_batching): the image of
+ * step s is i_train[perm_epoch(s mod n_train)] (a keyed permutation of the training images per epoch: each once per epoch), its n
+ * pixels are the first n outputs of a keyed permutation of [0, H W) (distinct, n <= H W).  images [N,H,W,3] fp32 or uint8,
+ * depths [N,H,W] fp32 (nullable with depth), poses [N,3,4], intrinsics [N,4] = (cx, cy, fx, fy), near / far / app [N] per image
+ * (the bounds sample_single_img passes on), extras [n_extra,N,H,W] fp32 per-pixel maps (confidence, sky mask), i_train int32
+ * [n_train].  Outputs (i1 - i0 rows): origins / directions / viewdirs [.,3], radii / lossmult (= 1) / near / far / app [.],
+ * rgb [.,3], depth [.] (nullable), extras_out [n_extra, i1 - i0], sel_coords int64 [.,2] = (row, col), img_out int64 [1]. */
+int snerf_mip_image_batch(const void* images, int images_u8, const float* depths, const float* poses, const float* intrinsics,
+                          const float* near, const float* far, const float* app, const float* extras, int n_extra, const int* i_train,
+                          int n_train, int N, int H, int W, long seed, long* counter, long n, long i0, long i1, float* origins,
+                          float* directions, float* viewdirs, float* radii, float* lossmult, float* near_out, float* far_out,
+                          float* app_out, float* rgb, float* depth, float* extras_out, long* sel_coords, long* img_out, void* stream);
+/* Path C (s-nerfpp/zipnerf/internal/datasets.py:442-566 Dataset._next_train + _make_ray_batch, patch_size 1; anything else is a
+ * bad argument): per ray a camera in [0, N) and x in [border, W - border), y in [border, H - border), uniform WITH replacement like
+ * np.random.randint (single_image = 1: one camera per step, batching 'single_image').  images [N,H,W,3] fp32 or uint8, depths
+ * [N,H,W] fp32, semantics int32 [N,H,W], masks fp32 [N,H,W] (each nullable with its output), pixtocams [N,3,3], camtoworlds
+ * [N,3,4], local2global int32 [N] (nullable with glo_idx).  Outputs (i1 - i0 rows): the rays of snerf_zip_pixels_to_rays
+ * (imageplane nullable), lossmult (= 1) / near / far / cam_idx / glo_idx fp32 [.] (as _make_ray_batch's float casts), rgb [.,3],
+ * depth [.], semantic int32 [.], mask [.], and the drawn pix_x / pix_y int32 [.]. */
+int snerf_zip_ray_batch(const void* images, int images_u8, const float* depths, const int* semantics, const float* masks,
+                        const float* pixtocams, const float* camtoworlds, const int* local2global, int N, int H, int W, float near,
+                        float far, int border, int patch_size, int single_image, long seed, long* counter, long n, long i0, long i1,
+                        float* origins, float* directions, float* viewdirs, float* radii, float* imageplane, float* base_x,
+                        float* base_y, float* lossmult, float* near_out, float* far_out, float* cam_idx, float* glo_idx, float* rgb,
+                        float* depth, int* semantic, float* mask, int* pix_x, int* pix_y, void* stream);
 /* Per-ray loss tail of s-nerfpp/zipnerf/train.py:250-311, value and gradients w.r.t. the renderer outputs in one pass:
  * data term (internal/train_utils.py:62-90; mse = 0: Charbonnier sqrt(resid^2 + pad^2), 1: resid^2) weighted by lossmult [R]
  * (nullable = 1) and normalised by its sum; disparity L1 |1/(depth+1e-5) - 1/(1e-5+tdepth)| as a masked mean under dmask [R]

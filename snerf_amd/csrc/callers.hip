@@ -17,10 +17,38 @@ struct RayGen {
   float *origins, *directions, *viewdirs, *radii, *near_out, *far_out;
 };
 
-__device__ __forceinline__ void cam_dir(const RayGen& a, float jj, float ii, float f, float off, float* d) {
-  const float c0 = (ii - a.cx + off) / f, c1 = -((jj - a.cy + off) / f), c2 = -1.f;
+__device__ __forceinline__ void cam_dir(const float* p, float cx, float cy, float jj, float ii, float f, float off, float* d) {
+  const float c0 = (ii - cx + off) / f, c1 = -((jj - cy + off) / f), c2 = -1.f;
 #pragma unroll
-  for (int c = 0; c < 3; ++c) d[c] = (c0 * a.p[4 * c + 0] + c1 * a.p[4 * c + 1]) + c2 * a.p[4 * c + 2];
+  for (int c = 0; c < 3; ++c) d[c] = (c0 * p[4 * c + 0] + c1 * p[4 * c + 1]) + c2 * p[4 * c + 2];
+}
+
+// the ray of pixel (row, col): direction d, unit view direction v, radius; the origin is p[3], p[7], p[11].  Shared by the pixel
+// list launch below and the training batcher (snerf_mip_image_batch), which must agree with it bit for bit.
+__device__ __forceinline__ void pinhole_ray(const float* p, float cx, float cy, float fx, float fy, int H, int row, int col, int training,
+                                            float* d, float* v, float* radius) {
+  const float f = (fx + fy) / 2.f;
+  const float jj = (float)row, ii = (float)col;
+  if (training) {
+    // get_rays_by_coord: i = (col - cx) / focal, j = -(row - cy) / focal
+    const float c0 = (ii - cx) / f, c1 = -((jj - cy) / f);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) d[c] = (c0 * p[4 * c + 0] + c1 * p[4 * c + 1]) + (-1.f) * p[4 * c + 2];
+  } else {
+    cam_dir(p, cx, cy, jj, ii, f, 0.5f, d);
+  }
+  // radius: distance to the neighbour one row down on the half-pixel grid; the reference appends dx[-2:-1] for the last image
+  // row, i.e. the value of row H-3 (sample_utils.py:309-310), not that of row H-2
+  const float ja = row >= H - 1 ? (float)(H - 3) : jj;
+  float d0[3], d1[3];
+  cam_dir(p, cx, cy, ja, ii, f, 0.5f, d0);
+  cam_dir(p, cx, cy, ja + 1.f, ii, f, 0.5f, d1);
+  const float e0 = d0[0] - d1[0], e1 = d0[1] - d1[1], e2 = d0[2] - d1[2];
+  const float dx = sqrtf((e0 * e0 + e1 * e1) + e2 * e2);
+  const float nrm = sqrtf((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
+#pragma unroll
+  for (int c = 0; c < 3; ++c) v[c] = d[c] / nrm;
+  *radius = dx * 2.f / 3.4641016151377544f;            // dx[..., None] * 2 / np.sqrt(12)
 }
 
 __global__ __launch_bounds__(256) void pinhole_rays_kernel(RayGen a) {
@@ -29,33 +57,15 @@ __global__ __launch_bounds__(256) void pinhole_rays_kernel(RayGen a) {
   int row, col;
   if (a.coords != nullptr) { row = a.coords[2 * r]; col = a.coords[2 * r + 1]; }
   else { const long pix = a.first + r; row = (int)(pix / a.W); col = (int)(pix - (long)row * a.W); }
-  const float f = (a.fx + a.fy) / 2.f;
-  const float jj = (float)row, ii = (float)col;
-  float d[3];
-  if (a.training) {
-    // get_rays_by_coord: i = (col - cx) / focal, j = -(row - cy) / focal
-    const float c0 = (ii - a.cx) / f, c1 = -((jj - a.cy) / f);
-#pragma unroll
-    for (int c = 0; c < 3; ++c) d[c] = (c0 * a.p[4 * c + 0] + c1 * a.p[4 * c + 1]) + (-1.f) * a.p[4 * c + 2];
-  } else {
-    cam_dir(a, jj, ii, f, 0.5f, d);
-  }
-  // radius: distance to the neighbour one row down on the half-pixel grid; the reference appends dx[-2:-1] for the last image
-  // row, i.e. the value of row H-3 (sample_utils.py:309-310), not that of row H-2
-  const float ja = row >= a.H - 1 ? (float)(a.H - 3) : jj;
-  float d0[3], d1[3];
-  cam_dir(a, ja, ii, f, 0.5f, d0);
-  cam_dir(a, ja + 1.f, ii, f, 0.5f, d1);
-  const float e0 = d0[0] - d1[0], e1 = d0[1] - d1[1], e2 = d0[2] - d1[2];
-  const float dx = sqrtf((e0 * e0 + e1 * e1) + e2 * e2);
-  const float nrm = sqrtf((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
+  float d[3], v[3], rad;
+  pinhole_ray(a.p, a.cx, a.cy, a.fx, a.fy, a.H, row, col, a.training, d, v, &rad);
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
     a.origins[3 * r + c] = a.p[4 * c + 3];
     a.directions[3 * r + c] = d[c];
-    a.viewdirs[3 * r + c] = d[c] / nrm;
+    a.viewdirs[3 * r + c] = v[c];
   }
-  a.radii[r] = dx * 2.f / 3.4641016151377544f;          // dx[..., None] * 2 / np.sqrt(12)
+  a.radii[r] = rad;
   a.near_out[r] = a.near;
   a.far_out[r] = a.far;
 }
@@ -347,17 +357,16 @@ __device__ __forceinline__ void zip_cast(const double* k, const double* p, doubl
   for (int c = 0; c < 3; ++c) d[c] = (p[4 * c] * cam[0] + p[4 * c + 1] * cam[1]) + p[4 * c + 2] * cam[2];
 }
 
-__global__ __launch_bounds__(256) void zip_rays_kernel(ZipRayGen a) {
-  const long r = (long)blockIdx.x * 256 + threadIdx.x;
-  if (r >= a.N) return;
-  int cam = a.cam_idx != nullptr ? a.cam_idx[r] : 0;
-  cam = min(max(cam, 0), a.ncam - 1);
+// the ray of pixel (x, y) of camera (K = pixtocam [3,3], P = camtoworld [3,4]), stored at row r of the outputs (imageplane nullable).
+// Shared by the pixel list launch below and the training batcher (snerf_zip_ray_batch), which must agree with it bit for bit.
+__device__ __forceinline__ void zip_ray(const float* K, const float* P, int xi, int yi, long r, float* origins, float* directions, float* viewdirs,
+                                        float* radii, float* imageplane, float* base_x, float* base_y) {
   double k[9], p[12];
 #pragma unroll
-  for (int i = 0; i < 9; ++i) k[i] = (double)a.pixtocams[9 * cam + i];
+  for (int i = 0; i < 9; ++i) k[i] = (double)K[i];
 #pragma unroll
-  for (int i = 0; i < 12; ++i) p[i] = (double)a.camtoworlds[12 * cam + i];
-  const double x = (double)a.pix_x[r], y = (double)a.pix_y[r];
+  for (int i = 0; i < 12; ++i) p[i] = (double)P[i];
+  const double x = (double)xi, y = (double)yi;
   double c0[3], cx[3], cy[3], d[3], dx[3], dy[3];
   zip_cast(k, p, x, y, c0, d);
   zip_cast(k, p, x + 1.0, y, cx, dx);
@@ -368,14 +377,23 @@ __global__ __launch_bounds__(256) void zip_rays_kernel(ZipRayGen a) {
   nd = sqrt(nd); nx = sqrt(nx); ny = sqrt(ny);
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
-    a.origins[3 * r + c] = (float)p[4 * c + 3];
-    a.directions[3 * r + c] = (float)d[c];
-    a.viewdirs[3 * r + c] = (float)(d[c] / nd);
-    a.base_x[3 * r + c] = (float)(dx[c] / nx);
-    a.base_y[3 * r + c] = (float)(dy[c] / ny);
+    origins[3 * r + c] = (float)p[4 * c + 3];
+    directions[3 * r + c] = (float)d[c];
+    viewdirs[3 * r + c] = (float)(d[c] / nd);
+    base_x[3 * r + c] = (float)(dx[c] / nx);
+    base_y[3 * r + c] = (float)(dy[c] / ny);
   }
-  a.radii[r] = (float)((0.5 * (nx + ny)) * 2.0 / 3.4641016151377544);
-  if (a.imageplane != nullptr) { a.imageplane[2 * r] = (float)c0[0]; a.imageplane[2 * r + 1] = (float)c0[1]; }
+  radii[r] = (float)((0.5 * (nx + ny)) * 2.0 / 3.4641016151377544);
+  if (imageplane != nullptr) { imageplane[2 * r] = (float)c0[0]; imageplane[2 * r + 1] = (float)c0[1]; }
+}
+
+__global__ __launch_bounds__(256) void zip_rays_kernel(ZipRayGen a) {
+  const long r = (long)blockIdx.x * 256 + threadIdx.x;
+  if (r >= a.N) return;
+  int cam = a.cam_idx != nullptr ? a.cam_idx[r] : 0;
+  cam = min(max(cam, 0), a.ncam - 1);
+  zip_ray(a.pixtocams + 9 * cam, a.camtoworlds + 12 * cam, a.pix_x[r], a.pix_y[r], r, a.origins, a.directions, a.viewdirs, a.radii, a.imageplane,
+          a.base_x, a.base_y);
 }
 
 extern "C" int snerf_zip_pixels_to_rays(const int* pix_x, const int* pix_y, const int* cam_idx, const float* pixtocams, const float* camtoworlds,
@@ -387,6 +405,224 @@ extern "C" int snerf_zip_pixels_to_rays(const int* pix_x, const int* pix_y, cons
     return SNERF_ERR_ARG;
   ZipRayGen a{pix_x, pix_y, cam_idx, pixtocams, camtoworlds, N, ncam, origins, directions, viewdirs, radii, imageplane, base_x, base_y};
   hipLaunchKernelGGL(zip_rays_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
+  return snerf_check_launch();
+}
+
+// ---------------------------------------------------------------------------
+// Device-resident training batchers (the step before the render paths): the training set stays in HBM and one launch draws, casts
+// and gathers a batch, with no host work and no sync.  Only the draw differs from the reference (numpy's RNG there); given the drawn
+// pixels, rays and targets are those of pinhole_ray / zip_ray above, bit for bit.
+//
+// Generator: Philox4x32-10 (Salmon et al., SC'11; the Random123 constants), key (k0, k1) = (low, high 32 bits of the seed):
+//   round: (c0, c1, c2, c3) <- (hi(M1 c2) ^ c1 ^ k0, lo(M1 c2), hi(M0 c0) ^ c3 ^ k1, lo(M0 c0)), M0 = 0xD2511F53, M1 = 0xCD9E8D57,
+//   then (k0, k1) += (0x9E3779B9, 0xBB67AE85); ten rounds.  philox(c0, c1, c2, c3) below is the first output word.
+// Keyed permutation perm(tag, t, M) of [0, M): a balanced Feistel network over b bits (b = the bit length of M - 1, rounded up to
+// an even number, at least 2; h = b / 2), four rounds j = 0..3 on v = (L << h) | R:
+//   F = philox(R, tag << 16 | j, lo32(t), hi32(t)) & (2^h - 1);  (L, R) <- (R, L ^ F)
+// applied again to its own output ("cycle walking") until the value is below M: a bijection of [0, M) with O(1) expected passes.
+//   snerf_mip_image_batch, step s over n_train training images:  image = i_train[perm(1, s / n_train, n_train)(s % n_train)] (each
+//   training image once per epoch); ray i (global batch position) -> pixel q = perm(2, s, H W)(i), row = q / W, col = q % W:
+//   n distinct pixels without a sort.
+//   snerf_zip_ray_batch, step s, ray i, value v (0 = camera, 1 = x, 2 = y) drawn uniformly from [lo, lo + range): attempts
+//   a = 0, 1, ...: u = philox(i, 3 << 16 | v << 8 | a, lo32(s), hi32(s)), m = u * range (64 bits); accepted when lo32(m) >=
+//   2^32 mod range (Lemire's unbiased bounded integers); value = lo + hi32(m).  Attempt 255 is accepted as it is (a rejection has
+//   probability range / 2^32).  batching 'single_image': every ray takes the camera of ray 0.
+// A ray's draws depend on (seed, step, i) only: not on the rank slice [i0, i1) a launch writes, nor on the launch geometry.
+// Step counter ctr[2] (int64, device): ctr[0] = step.  Every workgroup reads it and takes a ticket (ctr[1]); the last one stores
+// step + 1 and resets the ticket: a replayed graph launch draws a new batch every time.
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ unsigned philox(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1) {
+#pragma unroll
+  for (int i = 0; i < 10; ++i) {
+    const unsigned long long p0 = (unsigned long long)0xD2511F53u * c0, p1 = (unsigned long long)0xCD9E8D57u * c2;
+    const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1;
+    c1 = (unsigned)p1; c3 = (unsigned)p0; c0 = n0; c2 = n2;
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+  }
+  return c0;
+}
+
+__device__ __forceinline__ unsigned long long keyed_perm(unsigned long long v, unsigned long long M, unsigned tag, long t, unsigned k0, unsigned k1) {
+  int b = 64 - __clzll(M - 1);
+  b = b < 2 ? 2 : b + (b & 1);
+  const int h = b >> 1;
+  const unsigned long long mask = (1ull << h) - 1;
+  const unsigned t0 = (unsigned)(unsigned long long)t, t1 = (unsigned)((unsigned long long)t >> 32);
+  do {
+#pragma unroll
+    for (unsigned j = 0; j < 4; ++j) {
+      const unsigned long long L = v >> h, R = v & mask;
+      const unsigned long long F = philox((unsigned)R, tag << 16 | j, t0, t1, k0, k1) & mask;
+      v = (R << h) | (L ^ F);
+    }
+  } while (v >= M);
+  return v;
+}
+
+__device__ __forceinline__ int bounded_draw(unsigned i, unsigned v, long s, unsigned range, unsigned k0, unsigned k1) {
+  const unsigned thresh = (0u - range) % range;
+  const unsigned s0 = (unsigned)(unsigned long long)s, s1 = (unsigned)((unsigned long long)s >> 32);
+  unsigned long long m = 0;
+  for (unsigned a = 0; a < 256; ++a) {
+    m = (unsigned long long)philox(i, 3u << 16 | v << 8 | a, s0, s1, k0, k1) * range;
+    if ((unsigned)m >= thresh) break;
+  }
+  return (int)(m >> 32);
+}
+
+// workgroup start: the step of this launch (LDS broadcast); the last workgroup to take a ticket advances the counter
+__device__ __forceinline__ long batch_step(long* ctr) {
+  __shared__ long s_step;
+  if (threadIdx.x == 0) {
+    const long s = __hip_atomic_load(ctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    s_step = s;
+    __threadfence();
+    const unsigned long long ticket = atomicAdd((unsigned long long*)(ctr + 1), 1ull);
+    if (ticket == gridDim.x - 1) {
+      __hip_atomic_store(ctr + 1, 0L, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store(ctr, s + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  }
+  __syncthreads();
+  return s_step;
+}
+
+// uint8 storage decodes to float32(k / 255.0) computed in double (numpy's `image / 255.` before its cast to float32)
+__device__ __forceinline__ float texel(const void* img, int u8, long idx) {
+  return u8 ? (float)((double)((const unsigned char*)img)[idx] / 255.0) : ((const float*)img)[idx];
+}
+
+struct MipBatch {
+  const void* images; int u8;                     // [N,H,W,3]
+  const float *depths, *poses, *intr, *near, *far, *app, *extras;   // [N,H,W] / [N,3,4] / [N,4] = (cx, cy, fx, fy) / [N] x 3 / [k,N,H,W]
+  int n_extra;
+  const int* i_train; int n_train;
+  int N, H, W;
+  unsigned k0, k1;
+  long* ctr;
+  long n, i0, i1;
+  float *origins, *directions, *viewdirs, *radii, *lossmult, *near_out, *far_out, *app_out, *rgb, *depth, *extras_out;
+  long *sel_coords, *img_out;
+};
+
+__global__ __launch_bounds__(256) void mip_image_batch_kernel(MipBatch a) {
+  const long s = batch_step(a.ctr);
+  const long e = s / a.n_train, pos = s - e * a.n_train;
+  const int img = a.i_train[keyed_perm((unsigned long long)pos, (unsigned long long)a.n_train, 1u, e, a.k0, a.k1)];
+  if (blockIdx.x == 0 && threadIdx.x == 0) a.img_out[0] = img;
+  const long i = a.i0 + (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= a.i1) return;
+  const long r = i - a.i0, HW = (long)a.H * a.W;
+  const long q = (long)keyed_perm((unsigned long long)i, (unsigned long long)HW, 2u, s, a.k0, a.k1);
+  const int row = (int)(q / a.W), col = (int)(q - (long)row * a.W);
+  const float* p = a.poses + 12 * (long)img;
+  const float* k = a.intr + 4 * (long)img;
+  float d[3], v[3], rad;
+  pinhole_ray(p, k[0], k[1], k[2], k[3], a.H, row, col, 1, d, v, &rad);
+  const long pix = (long)img * HW + q;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    a.origins[3 * r + c] = p[4 * c + 3];
+    a.directions[3 * r + c] = d[c];
+    a.viewdirs[3 * r + c] = v[c];
+    a.rgb[3 * r + c] = texel(a.images, a.u8, 3 * pix + c);
+  }
+  a.radii[r] = rad;
+  a.lossmult[r] = 1.f;
+  a.near_out[r] = a.near[img];
+  a.far_out[r] = a.far[img];
+  a.app_out[r] = a.app[img];
+  if (a.depth != nullptr) a.depth[r] = a.depths[pix];
+  const long nl = a.i1 - a.i0;
+  for (int x = 0; x < a.n_extra; ++x) a.extras_out[x * nl + r] = a.extras[(long)x * a.N * HW + pix];
+  a.sel_coords[2 * r] = row;
+  a.sel_coords[2 * r + 1] = col;
+}
+
+extern "C" int snerf_mip_image_batch(const void* images, int images_u8, const float* depths, const float* poses, const float* intrinsics,
+                                     const float* near, const float* far, const float* app, const float* extras, int n_extra, const int* i_train,
+                                     int n_train, int N, int H, int W, long seed, long* counter, long n, long i0, long i1, float* origins,
+                                     float* directions, float* viewdirs, float* radii, float* lossmult, float* near_out, float* far_out,
+                                     float* app_out, float* rgb, float* depth, float* extras_out, long* sel_coords, long* img_out, void* stream) {
+  if (n == 0) return SNERF_OK;
+  if (n < 0 || N < 1 || n_train < 1 || H < 3 || W < 1 || n > (long)H * W || i0 < 0 || i1 < i0 || i1 > n || n_extra < 0) return SNERF_ERR_ARG;
+  if (images == nullptr || poses == nullptr || intrinsics == nullptr || near == nullptr || far == nullptr || app == nullptr ||
+      i_train == nullptr || counter == nullptr || img_out == nullptr || (images_u8 != 0 && images_u8 != 1))
+    return SNERF_ERR_ARG;
+  if (origins == nullptr || directions == nullptr || viewdirs == nullptr || radii == nullptr || lossmult == nullptr || near_out == nullptr ||
+      far_out == nullptr || app_out == nullptr || rgb == nullptr || sel_coords == nullptr)
+    return SNERF_ERR_ARG;
+  if ((depth != nullptr && depths == nullptr) || (n_extra > 0 && (extras == nullptr || extras_out == nullptr))) return SNERF_ERR_ARG;
+  MipBatch a{images, images_u8, depths, poses, intrinsics, near, far, app, extras, n_extra, i_train, n_train, N, H, W,
+             (unsigned)(unsigned long)seed, (unsigned)((unsigned long)seed >> 32), counter, n, i0, i1, origins, directions, viewdirs, radii,
+             lossmult, near_out, far_out, app_out, rgb, depth, extras_out, sel_coords, img_out};
+  const long nl = i1 - i0;
+  hipLaunchKernelGGL(mip_image_batch_kernel, dim3((unsigned)(nl > 0 ? (nl + 255) / 256 : 1)), dim3(256), 0, (hipStream_t)stream, a);
+  return snerf_check_launch();
+}
+
+struct ZipBatch {
+  const void* images; int u8;                     // [N,H,W,3]
+  const float* depths; const int* semantics; const float* masks;  // [N,H,W], nullable
+  const float *pixtocams, *camtoworlds;           // [N,3,3], [N,3,4]
+  const int* local2global;                        // [N], nullable
+  int N, H, W, border, single_image;
+  float near, far;
+  unsigned k0, k1;
+  long* ctr;
+  long n, i0, i1;
+  float *origins, *directions, *viewdirs, *radii, *imageplane, *base_x, *base_y, *lossmult, *near_out, *far_out, *cam_out, *glo_out;
+  float *rgb, *depth; int* semantic; float* mask;
+  int *pix_x, *pix_y;
+};
+
+__global__ __launch_bounds__(256) void zip_ray_batch_kernel(ZipBatch a) {
+  const long s = batch_step(a.ctr);
+  const long i = a.i0 + (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= a.i1) return;
+  const long r = i - a.i0;
+  const int cam = bounded_draw(a.single_image ? 0u : (unsigned)i, 0u, s, (unsigned)a.N, a.k0, a.k1);
+  const int x = a.border + bounded_draw((unsigned)i, 1u, s, (unsigned)(a.W - 2 * a.border), a.k0, a.k1);
+  const int y = a.border + bounded_draw((unsigned)i, 2u, s, (unsigned)(a.H - 2 * a.border), a.k0, a.k1);
+  zip_ray(a.pixtocams + 9 * (long)cam, a.camtoworlds + 12 * (long)cam, x, y, r, a.origins, a.directions, a.viewdirs, a.radii, a.imageplane,
+          a.base_x, a.base_y);
+  const long pix = ((long)cam * a.H + y) * a.W + x;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) a.rgb[3 * r + c] = texel(a.images, a.u8, 3 * pix + c);
+  a.lossmult[r] = 1.f;
+  a.near_out[r] = a.near;
+  a.far_out[r] = a.far;
+  a.cam_out[r] = (float)cam;
+  if (a.glo_out != nullptr) a.glo_out[r] = (float)a.local2global[cam];
+  if (a.depth != nullptr) a.depth[r] = a.depths[pix];
+  if (a.semantic != nullptr) a.semantic[r] = a.semantics[pix];
+  if (a.mask != nullptr) a.mask[r] = a.masks[pix];
+  a.pix_x[r] = x;
+  a.pix_y[r] = y;
+}
+
+extern "C" int snerf_zip_ray_batch(const void* images, int images_u8, const float* depths, const int* semantics, const float* masks,
+                                   const float* pixtocams, const float* camtoworlds, const int* local2global, int N, int H, int W, float near,
+                                   float far, int border, int patch_size, int single_image, long seed, long* counter, long n, long i0, long i1,
+                                   float* origins, float* directions, float* viewdirs, float* radii, float* imageplane, float* base_x,
+                                   float* base_y, float* lossmult, float* near_out, float* far_out, float* cam_idx, float* glo_idx, float* rgb,
+                                   float* depth, int* semantic, float* mask, int* pix_x, int* pix_y, void* stream) {
+  if (n == 0) return SNERF_OK;
+  if (n < 0 || N < 1 || H < 1 || W < 1 || border < 0 || 2L * border >= W || 2L * border >= H || patch_size != 1 || i0 < 0 || i1 < i0 ||
+      i1 > n || n > 0xFFFFFFFFL || (single_image != 0 && single_image != 1) || (images_u8 != 0 && images_u8 != 1))
+    return SNERF_ERR_ARG;
+  if (images == nullptr || pixtocams == nullptr || camtoworlds == nullptr || counter == nullptr || origins == nullptr || directions == nullptr ||
+      viewdirs == nullptr || radii == nullptr || base_x == nullptr || base_y == nullptr || lossmult == nullptr || near_out == nullptr ||
+      far_out == nullptr || cam_idx == nullptr || rgb == nullptr || pix_x == nullptr || pix_y == nullptr)
+    return SNERF_ERR_ARG;
+  if ((depth != nullptr && depths == nullptr) || (semantic != nullptr && semantics == nullptr) || (mask != nullptr && masks == nullptr) ||
+      (glo_idx != nullptr && local2global == nullptr))
+    return SNERF_ERR_ARG;
+  ZipBatch a{images, images_u8, depths, semantics, masks, pixtocams, camtoworlds, local2global, N, H, W, border, single_image, near, far,
+             (unsigned)(unsigned long)seed, (unsigned)((unsigned long)seed >> 32), counter, n, i0, i1, origins, directions, viewdirs, radii,
+             imageplane, base_x, base_y, lossmult, near_out, far_out, cam_idx, glo_idx, rgb, depth, semantic, mask, pix_x, pix_y};
+  const long nl = i1 - i0;
+  hipLaunchKernelGGL(zip_ray_batch_kernel, dim3((unsigned)(nl > 0 ? (nl + 255) / 256 : 1)), dim3(256), 0, (hipStream_t)stream, a);
   return snerf_check_launch();
 }
 

@@ -1432,6 +1432,50 @@ def zip_pixels_to_rays(pix_x, pix_y, cam_idx, pixtocams, camtoworlds, want_image
     return out
 
 
+def _u8_or_f32(images):
+    assert images.is_cuda and images.is_contiguous() and images.dtype in (torch.uint8, torch.float32), "images: contiguous uint8 / fp32 CUDA tensor"
+    return 1 if images.dtype == torch.uint8 else 0
+
+
+def mip_image_batch(images, depths, poses, intrinsics, near, far, app, extras, i_train, seed, counter, n, i0, i1, out):
+    """snerf_mip_image_batch: rows [i0, i1) of step counter[0]'s global batch of n pixels into the preallocated `out` (dict: origins,
+    directions, viewdirs [m,3], radii, lossmult, near, far, app [m,1], rgb [m,3], depth [m] or None, extras [k,m] or None,
+    sel_coords int64 [m,2], img int64 [1]; m = i1 - i0); advances counter[0].  images [N,H,W,3] uint8 / fp32, depths [N,H,W],
+    poses [N,3,4], intrinsics [N,4] = (cx, cy, fx, fy), near / far / app [N], extras [k,N,H,W] or None, i_train int32."""
+    u8 = _u8_or_f32(images)
+    N, H, W = images.shape[:3]
+    for t in (depths, poses, intrinsics, near, far, app, extras):
+        _f32c(t)
+    assert i_train.dtype == torch.int32 and i_train.is_contiguous() and counter.dtype == torch.int64 and counter.numel() == 2
+    k = 0 if extras is None else extras.shape[0]
+    _lib.call("snerf_mip_image_batch", _p(images), u8, _p(depths), _p(poses), _p(intrinsics), _p(near), _p(far), _p(app), _p(extras), k,
+              _p(i_train), i_train.numel(), N, H, W, int(seed), _p(counter), int(n), int(i0), int(i1), _p(out["origins"]),
+              _p(out["directions"]), _p(out["viewdirs"]), _p(out["radii"]), _p(out["lossmult"]), _p(out["near"]), _p(out["far"]),
+              _p(out["app"]), _p(out["rgb"]), _p(out.get("depth")), _p(out.get("extras")), _p(out["sel_coords"]), _p(out["img"]), _stream())
+    return out
+
+
+def zip_ray_batch(images, depths, semantics, masks, pixtocams, camtoworlds, local2global, near, far, border, patch_size, single_image, seed,
+                  counter, n, i0, i1, out):
+    """snerf_zip_ray_batch: rows [i0, i1) of step counter[0]'s global batch of n rays into the preallocated `out` (dict: origins,
+    directions, viewdirs, base_x, base_y [m,3], radii, lossmult, near, far, cam_idx [m,1], imageplane [m,2] / glo_idx [m,1] / depth [m] /
+    semantic int32 [m] / mask [m] or absent, rgb [m,3], pix_x_int / pix_y_int int32 [m]); advances counter[0]."""
+    u8 = _u8_or_f32(images)
+    N, H, W = images.shape[:3]
+    for t in (depths, masks, pixtocams, camtoworlds):
+        _f32c(t)
+    for t in (semantics, local2global):
+        assert t is None or (t.dtype == torch.int32 and t.is_contiguous())
+    assert counter.dtype == torch.int64 and counter.numel() == 2
+    _lib.call("snerf_zip_ray_batch", _p(images), u8, _p(depths), _p(semantics), _p(masks), _p(pixtocams), _p(camtoworlds), _p(local2global),
+              N, H, W, float(near), float(far), int(border), int(patch_size), int(bool(single_image)), int(seed), _p(counter), int(n), int(i0),
+              int(i1), _p(out["origins"]), _p(out["directions"]), _p(out["viewdirs"]), _p(out["radii"]), _p(out.get("imageplane")),
+              _p(out["base_x"]), _p(out["base_y"]), _p(out["lossmult"]), _p(out["near"]), _p(out["far"]), _p(out["cam_idx"]),
+              _p(out.get("glo_idx")), _p(out["rgb"]), _p(out.get("depth")), _p(out.get("semantic")), _p(out.get("mask")), _p(out["pix_x_int"]),
+              _p(out["pix_y_int"]), _stream())
+    return out
+
+
 ZIP_LOSS_NAMES = ("data", "mse", "depth", "d_complete", "sem", "interlevel", "distortion")
 
 

@@ -121,3 +121,172 @@ def apply_pose_transform(rays, pose):
     R, t = pose[:3, :3], pose[:3, 3]
     rot = lambda v: (v[..., None, :] * R).sum(-1)
     return rays._replace(origins=rays.origins + t, directions=rot(rays.directions), viewdirs=rot(rays.viewdirs))
+
+
+# ---- device-resident training batcher (snerf_mip_image_batch) ------------------------------------------------------------------------
+_M32 = 0xFFFFFFFF
+
+
+def philox(c, seed):
+    """Philox4x32-10 of the 4-word counter `c` under the 64-bit `seed` -> its first output word (host form of csrc/callers.hip's)."""
+    c0, c1, c2, c3 = (int(x) & _M32 for x in c)
+    k0, k1 = seed & _M32, (seed >> 32) & _M32
+    for _ in range(10):
+        p0, p1 = 0xD2511F53 * c0, 0xCD9E8D57 * c2
+        c0, c1, c2, c3 = ((p1 >> 32) ^ c1 ^ k0) & _M32, p1 & _M32, ((p0 >> 32) ^ c3 ^ k1) & _M32, p0 & _M32
+        k0, k1 = (k0 + 0x9E3779B9) & _M32, (k1 + 0xBB67AE85) & _M32
+    return c0
+
+
+def keyed_perm(v, M, tag, t, seed):
+    """The keyed permutation of [0, M) the batchers draw with (4-round Feistel network with cycle walking; csrc/callers.hip)."""
+    b = max(2, (M - 1).bit_length())
+    b += b & 1
+    h = b >> 1
+    mask = (1 << h) - 1
+    t &= (1 << 64) - 1
+    while True:
+        for j in range(4):
+            L, R = v >> h, v & mask
+            v = (R << h) | (L ^ (philox((R, tag << 16 | j, t & _M32, t >> 32), seed) & mask))
+        if v < M:
+            return v
+
+
+def image_of_step(i_train, seed, s):
+    """ImageRayBatcher's image schedule: step s of epoch e = s // len(i_train) trains on i_train[keyed_perm(s % len(i_train))] (each
+    training image once per epoch, a new order every epoch)."""
+    nt = len(i_train)
+    e, p = divmod(int(s), nt)
+    return int(i_train[keyed_perm(p, nt, 1, e, int(seed))])
+
+
+def _stack(x, dtype=None):
+    if torch.is_tensor(x):
+        return x.detach()
+    if isinstance(x, (list, tuple)):
+        return torch.stack([torch.as_tensor(np.asarray(v) if not torch.is_tensor(v) else v) for v in x])
+    return torch.as_tensor(np.asarray(x, dtype=dtype) if dtype is not None else np.asarray(x))
+
+
+class ImageRayBatcher:
+    """Device-resident form of SingleImage + sample_single_img (s-nerf/dataloader/rayset.py:124-151, the `no_batching` loader that
+    `pose_refine = True` selects): the training images, depth maps, poses and intrinsics live on the device and `next()` draws, casts and
+    gathers one batch in ONE launch (`snerf_mip_image_batch`), with no host work, no upload and no sync per step.
+
+    Step s trains on image `image_of_step(s)` (a keyed permutation of i_train per epoch: DataLoader(shuffle=True, batch_size=1)
+    semantics) and on batch_n distinct pixels of it (without replacement, like np.random.choice(H W, n, replace=False)).  Only that
+    draw differs from the reference (a counter-based generator keyed by `seed` instead of numpy's); given the pixels, rays, targets
+    and bounds are what sample_single_img returns, bit for bit: near / far are near * 0.9 / far * 1.1, or with args.near_far the
+    image's non-zero depth float(min) * 0.9 / float(max) * 1.1 (computed once here), app = camera_index[img].
+
+    Rank r of `world` computes rows shard_bounds(batch_n, r, world) of the one global batch: the ranks together see exactly the rays of
+    a single-GPU run.  images: [N,H,W,3] uint8 (decoded to float32(k / 255.0)) or float; extras: per-pixel fp32 maps [N,H,W]
+    (confidence maps, sky masks) gathered with the targets."""
+
+    def __init__(self, args, images, depth_gts, poses, intrinsics, i_train, near, far, camera_index=None, batch_n=None, extras=None, seed=0,
+                 rank=0, world=1, device=None):
+        _check(args)
+        if getattr(args, "smooth_loss", False):
+            raise NotImplementedError("smooth_loss: the patches of sample_patches are not drawn by the device batcher")
+        if not 0 <= int(seed) < (1 << 63):
+            raise ValueError("seed must be in [0, 2^63)")
+        device = torch.device(device if device is not None else "cuda")
+        img = _stack(images)
+        if img.dim() != 4 or img.shape[-1] != 3 or img.shape[0] == 0:
+            raise ValueError("images: [N, H, W, 3] with N >= 1")
+        N, H, W = (int(v) for v in img.shape[:3])
+        n = int(batch_n if batch_n is not None else args.N_rgb)
+        if not 0 < n <= H * W:
+            raise ValueError(f"batch_n = {n}: needs 0 < batch_n <= H W = {H * W} (pixels are drawn without replacement)")
+        if H < 3:
+            raise ValueError("images need at least 3 rows (the radius of the last row is that of row H - 3)")
+        it = np.asarray(i_train.cpu() if torch.is_tensor(i_train) else i_train, dtype=np.int64).reshape(-1)
+        if it.size == 0:
+            raise ValueError("i_train is empty")
+        if it.min() < 0 or it.max() >= N:
+            raise ValueError("i_train indexes past the images")
+        dep = _stack(depth_gts).to(torch.float32)
+        if tuple(dep.shape) != (N, H, W):
+            raise ValueError(f"depth_gts: [N, H, W] = {(N, H, W)}, got {tuple(dep.shape)}")
+        P = _stack(poses).to(torch.float32)[:, :3, :4]
+        K = [_intr(k) for k in (_stack(intrinsics))]
+        if P.shape[0] != N or len(K) != N:
+            raise ValueError("poses / intrinsics: one per image")
+        ex = None
+        if extras is not None and len(extras) > 0:
+            ex = torch.stack([_stack(e).to(torch.float32) for e in extras])
+            if tuple(ex.shape[1:]) != (N, H, W):
+                raise ValueError("extras: per-pixel maps [N, H, W]")
+        if getattr(args, "near_far", False):
+            # sample_single_img's near_far bounds, per training image (one device->host read here, none per step)
+            bounds = {}
+            for i in sorted(set(it.tolist())):
+                nz = dep[i][dep[i] != 0]
+                bounds[i] = (float(nz.min()) * 0.9, float(nz.max()) * 1.1)
+            nf = [bounds.get(i, (near * 0.9, far * 1.1)) for i in range(N)]
+        else:
+            nf = [(near * 0.9, far * 1.1)] * N
+        cam = np.zeros(N) if camera_index is None else np.asarray(camera_index.cpu() if torch.is_tensor(camera_index) else camera_index, dtype=np.float64).reshape(-1)
+        f32 = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float32)).to(device)
+        self.images = img.to(device, torch.uint8 if img.dtype == torch.uint8 else torch.float32).contiguous()
+        self.depths = dep.to(device).contiguous()
+        self.poses, self.intrinsics = P.to(device).contiguous(), f32(K)
+        self.near_img, self.far_img = [b[0] for b in nf], [b[1] for b in nf]   # the bounds sample_single_img passes on (python floats)
+        self.near, self.far, self.app = f32(self.near_img), f32(self.far_img), f32([float(cam[i]) for i in range(N)])
+        self.extras = None if ex is None else ex.to(device).contiguous()
+        self.i_train_host = it
+        self.i_train = torch.as_tensor(it, dtype=torch.int32).to(device)
+        self.N, self.H, self.W, self.batch_n = N, H, W, n
+        from .trainer import shard_bounds
+        self.rank, self.world = int(rank), int(world)
+        self.i0, self.i1 = shard_bounds(n, self.rank, self.world)
+        self.seed, self.device = int(seed), device
+        self.counter = torch.zeros(2, dtype=torch.int64, device=device)        # {step, workgroup ticket}: advanced by the launch
+        self._step = 0
+
+    @property
+    def step(self):
+        """the step of the next draw (host mirror of the device counter; `advance_host` after graph replays of `next_into`)"""
+        return self._step
+
+    def image_of_step(self, s):
+        """index (into the images) of the image step s trains on -- on the host, no sync (pose refinement: pose_param_net(img_i))"""
+        return image_of_step(self.i_train_host, self.seed, s)
+
+    def state_dict(self):
+        return {"seed": self.seed, "step": self._step}
+
+    def load_state_dict(self, sd):
+        self.seed, self._step = int(sd["seed"]), int(sd["step"])
+        self.counter.copy_(torch.tensor([self._step, 0], dtype=torch.int64))
+
+    def advance_host(self, k=1):
+        """tell the host mirror that k draws ran inside graph replays"""
+        self._step += int(k)
+
+    def buffers(self):
+        """fresh output tensors of one batch (this rank's rows)"""
+        m, dev = self.i1 - self.i0, self.device
+        e = lambda *s, dt=torch.float32: torch.empty(*s, dtype=dt, device=dev)
+        return dict(origins=e(m, 3), directions=e(m, 3), viewdirs=e(m, 3), radii=e(m, 1), lossmult=e(m, 1), near=e(m, 1), far=e(m, 1),
+                    app=e(m, 1), rgb=e(m, 3), depth=e(m), extras=None if self.extras is None else e(self.extras.shape[0], m),
+                    sel_coords=e(m, 2, dt=torch.int64), img=e(1, dt=torch.int64))
+
+    def next_into(self, buf):
+        """draw the next batch into `buf` (from `buffers()`) on the current stream; graph-capturable (every replay draws the next step)
+        -> (rays, target_rgb, target_depth, sel_coords, img_i, extras) as views of `buf`"""
+        ops.mip_image_batch(self.images, self.depths, self.poses, self.intrinsics, self.near, self.far, self.app, self.extras, self.i_train,
+                            self.seed, self.counter, self.batch_n, self.i0, self.i1, buf)
+        self._step += 1
+        return self.view(buf)
+
+    def next(self):
+        """-> (rays, target_rgb, target_depth, sel_coords, img_i, extras) of the next step in new tensors (they stay valid)"""
+        return self.next_into(self.buffers())
+
+    @staticmethod
+    def view(buf):
+        rays = Rays(buf["origins"], buf["directions"], buf["viewdirs"], buf["radii"], buf["lossmult"], buf["near"], buf["far"], buf["app"])
+        ex = [] if buf["extras"] is None else list(buf["extras"].unbind(0))
+        return rays, buf["rgb"], buf["depth"], buf["sel_coords"], buf["img"], ex

@@ -233,7 +233,7 @@ class MipTrainer(_AdamState):
         return loss, outs
 
     # ---- hipGraph capture of the whole step --------------------------------------------------------------------------------------
-    def capture(self, rays, target_rgb, target_depth=None, conf=None, randomized=True, warmup=3, viewc=None):
+    def capture(self, rays, target_rgb, target_depth=None, conf=None, randomized=True, warmup=3, viewc=None, batcher=None, conf_extra=None):
         """Capture one full training step (draws, forward, loss tail, backward, Adam: ~130 launches) in a hipGraph over the GIVEN tensors;
         afterwards `replay()` runs a step with one graph launch -- the caller refreshes the batch by copying into those tensors
         (`rays.origins.copy_(...)` etc.).  Worth it when the step is launch-bound: at 512 rays per GPU (the 8-GPU split of the
@@ -248,7 +248,13 @@ class MipTrainer(_AdamState):
         Data parallel (world > 1; every rank calls capture / replay together): the graph holds forward + loss tail + backward -- the
         launch-bound part -- and `replay()` follows it with the gradient all-reduce and the Adam launch OUTSIDE the graph (one
         collective over the whole arena: nothing is left to overlap it with once the backward is a single graph launch; the
-        collective stays out of the graph so that any backend works, gloo on the 1-GPU box included)."""
+        collective stays out of the graph so that any backend works, gloo on the 1-GPU box included).
+
+        `batcher` (sample_utils.ImageRayBatcher): its draw (`next_into`, one launch) becomes the first node of the captured step, whose
+        rays and targets are the batcher's buffers (`rays` / `target_rgb` / `target_depth` are ignored; `conf_extra` = index of the
+        batcher's extra map that serves as the per-ray confidence, or None): every `replay()` trains on a fresh batch, the k-th on the
+        batch an eager batcher draws at step s0 + k (s0 = the batcher's step at this call).  The warm-up restores the batcher's counter
+        like the parameters.  `self.batch` holds the captured batch tensors (rays, target_rgb, target_depth, sel_coords, img_i, extras)."""
         self._set_viewc(viewc)                           # (fn = 0: the centre is a kernel argument, i.e. a constant of the captured graph)
         a = self.model.arena
         dev = a.flat.device
@@ -256,11 +262,23 @@ class MipTrainer(_AdamState):
         if self.world == 1:
             self._step_dev = torch.tensor([self.t], dtype=torch.int32, device=dev)
             self._lr_dev = torch.tensor([self.lr], dtype=torch.float32, device=dev)
+        self._batcher = batcher
+        if batcher is not None:
+            buf = batcher.buffers()
+            self.batch = batcher.view(buf)
+            rays, target_rgb, target_depth, _, _, extras = self.batch
+            conf = None if conf_extra is None else extras[conf_extra]
+            b_snap = (batcher.counter.clone(), batcher.step)
         args = (rays, target_rgb, target_depth, conf)
+
+        def draw():
+            if batcher is not None:
+                batcher.next_into(buf)
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side):                    # warm-up on a side stream
             for _ in range(warmup):
+                draw()
                 self.step(*args, randomized=randomized)
         torch.cuda.current_stream(dev).wait_stream(side)
         with torch.no_grad():
@@ -269,19 +287,26 @@ class MipTrainer(_AdamState):
             if self._step_dev is not None:
                 self._step_dev.fill_(self.t)
             a.grad.zero_()
+            if batcher is not None:                      # capturing uses up no draws
+                batcher.counter.copy_(b_snap[0])
         a.bump()
         self._graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self._graph):
+            draw()
             if self.world == 1:
                 self._graph_loss, self._graph_outs = self.step(*args, randomized=randomized)
             else:
                 self._graph_loss, self._graph_outs = self._forward_backward(*args, randomized, None, None, False, None)
+        if batcher is not None:
+            batcher._step = b_snap[1]
         if self.world == 1:
             self.t -= 1                                  # capturing records the step, it does not run it
         return self._graph_loss
 
     def replay(self):
         """One captured step.  -> (loss, outs): the same device tensors every time, overwritten by each replay."""
+        if getattr(self, "_batcher", None) is not None:
+            self._batcher.advance_host(1)                # the graph's first node drew the batch and advanced the device counter
         if self.world == 1:
             self._lr_dev.fill_(self.lr)                  # the graph reads the learning rate from the device
             self._graph.replay()

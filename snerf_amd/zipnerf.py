@@ -577,3 +577,102 @@ class _ZipFn(torch.autograd.Function):
             return (None,) * 12 + grads
         rays_g = tuple(g.reshape(sh).to(device=dev, dtype=dt) for g, (sh, dt, dev) in zip(rg, ctx.ray_meta))
         return (None,) * 7 + rays_g + grads
+
+
+class RayBatcher:
+    """Device-resident form of Dataset._next_train + _make_ray_batch (s-nerfpp/zipnerf/internal/datasets.py:442-566, patch_size 1): the
+    training images (and optional depth, semantic labels, masks) live on the device and `next()` draws, casts and gathers one batch in
+    ONE launch (`snerf_zip_ray_batch`): no numpy ray computation on the host, no upload, no sync.
+
+    Per ray a camera, x in [border, W - border) and y in [border, H - border) are drawn uniformly with replacement, like the
+    reference's np.random.randint (`batching='single_image'`: one camera per step).  Only that draw differs from the reference (a
+    counter-based generator keyed by `seed`, not numpy's); given (x, y, cam), the rays are those of ops.zip_pixels_to_rays bit for bit
+    and the targets are plain gathers.  `next()` -> the batch dict with the reference's keys: origins, directions, viewdirs, radii,
+    imageplane, base_x, base_y, lossmult, near, far, cam_idx (float, [R,1], as _make_ray_batch's casts), glo_idx (with local2global),
+    rgb [R,3], depth [R], semantic int32 [R], mask [R] (with their inputs), and the drawn pix_x_int / pix_y_int (int32 [R]).
+
+    Rank r of `world` computes rows trainer.shard_bounds(batch_size, r, world) of the one global batch: together the ranks see exactly
+    the rays of a single-GPU run (the reference's loader samples each rank's own share of the images instead; here every rank holds the
+    whole training set)."""
+
+    def __init__(self, images, pixtocams, camtoworlds, near, far, depths=None, semantics=None, masks=None, local2global=None, batch_size=65536,
+                 border=0, batching='all_images', patch_size=1, seed=0, rank=0, world=1, device="cuda"):
+        if int(patch_size) != 1:
+            raise NotImplementedError("patch_size > 1: the batcher draws single pixels (the reference's default patch_size = 1)")
+        if batching not in ('all_images', 'single_image'):
+            raise ValueError(f"batching: 'all_images' or 'single_image', not {batching!r}")
+        if not 0 <= int(seed) < (1 << 63):
+            raise ValueError("seed must be in [0, 2^63)")
+        dev = torch.device(device)
+        img = torch.as_tensor(images) if not torch.is_tensor(images) else images.detach()
+        if img.dim() != 4 or img.shape[-1] != 3 or img.shape[0] == 0:
+            raise ValueError("images: [N, H, W, 3] with N >= 1")
+        N, H, W = (int(v) for v in img.shape[:3])
+        border = int(border)
+        if border < 0 or 2 * border >= min(H, W):
+            raise ValueError(f"border {border} leaves no pixel of a {H} x {W} image")
+        if not 0 < int(batch_size) < (1 << 32):
+            raise ValueError("batch_size must be in [1, 2^32)")
+        t = lambda a, dt: None if a is None else (torch.as_tensor(a) if not torch.is_tensor(a) else a.detach()).to(dev, dt).contiguous()
+        self.images = img.to(dev, torch.uint8 if img.dtype == torch.uint8 else torch.float32).contiguous()
+        self.pixtocams, self.camtoworlds = t(pixtocams, torch.float32).reshape(N, 3, 3), t(camtoworlds, torch.float32)[:, :3, :4].contiguous()
+        self.depths, self.masks = t(depths, torch.float32), t(masks, torch.float32)
+        self.semantics = t(semantics, torch.int32)
+        self.local2global = t(local2global, torch.int32)
+        for name, a in (("depths", self.depths), ("semantics", self.semantics), ("masks", self.masks)):
+            if a is not None and tuple(a.shape) != (N, H, W):
+                raise ValueError(f"{name}: [N, H, W] = {(N, H, W)}, got {tuple(a.shape)}")
+        if self.camtoworlds.shape[0] != N or (self.local2global is not None and self.local2global.numel() != N):
+            raise ValueError("camtoworlds / local2global: one per image")
+        from .trainer import shard_bounds
+        self.N, self.H, self.W, self.batch_size, self.border = N, H, W, int(batch_size), border
+        self.near, self.far, self.single_image = float(near), float(far), batching == 'single_image'
+        self.rank, self.world = int(rank), int(world)
+        self.i0, self.i1 = shard_bounds(self.batch_size, self.rank, self.world)
+        self.seed, self.device = int(seed), dev
+        self.counter = torch.zeros(2, dtype=torch.int64, device=dev)           # {step, workgroup ticket}: advanced by the launch
+        self._step = 0
+
+    @property
+    def step(self):
+        """the step of the next draw (host mirror of the device counter; `advance_host` after graph replays of `next_into`)"""
+        return self._step
+
+    def state_dict(self):
+        return {"seed": self.seed, "step": self._step}
+
+    def load_state_dict(self, sd):
+        self.seed, self._step = int(sd["seed"]), int(sd["step"])
+        self.counter.copy_(torch.tensor([self._step, 0], dtype=torch.int64))
+
+    def advance_host(self, k=1):
+        """tell the host mirror that k draws ran inside graph replays"""
+        self._step += int(k)
+
+    def buffers(self):
+        """fresh output tensors of one batch (this rank's rows)"""
+        m, dev = self.i1 - self.i0, self.device
+        e = lambda *s, dt=torch.float32: torch.empty(*s, dtype=dt, device=dev)
+        b = dict(origins=e(m, 3), directions=e(m, 3), viewdirs=e(m, 3), radii=e(m, 1), imageplane=e(m, 2), lossmult=e(m, 1), near=e(m, 1),
+                 far=e(m, 1), cam_idx=e(m, 1), base_x=e(m, 3), base_y=e(m, 3), rgb=e(m, 3))
+        if self.local2global is not None:
+            b["glo_idx"] = e(m, 1)
+        if self.depths is not None:
+            b["depth"] = e(m)
+        if self.semantics is not None:
+            b["semantic"] = e(m, dt=torch.int32)
+        if self.masks is not None:
+            b["mask"] = e(m)
+        b["pix_x_int"], b["pix_y_int"] = e(m, dt=torch.int32), e(m, dt=torch.int32)
+        return b
+
+    def next_into(self, buf):
+        """draw the next batch into `buf` (from `buffers()`) on the current stream; graph-capturable -> buf"""
+        ops.zip_ray_batch(self.images, self.depths, self.semantics, self.masks, self.pixtocams, self.camtoworlds, self.local2global, self.near,
+                          self.far, self.border, 1, self.single_image, self.seed, self.counter, self.batch_size, self.i0, self.i1, buf)
+        self._step += 1
+        return buf
+
+    def next(self):
+        """-> the batch dict of the next step in new tensors (they stay valid)"""
+        return self.next_into(self.buffers())
