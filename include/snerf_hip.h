@@ -571,6 +571,30 @@ int snerf_fmlp_classic_train_fwd(const void* E, long ldE, const void* VE, long l
 int snerf_fmlp_proposal_train_fwd(const void* E, long ldE, const void* wstream, long n_frags, const float* bias, int n_blocks,
                                   float* raw_density, void* const* acts, const long* act_ld, void* const* bits, long M,
                                   void* stream);
+/* The seven entries above in either 16-bit flavour (library version >= 2): the same arguments with `int dtype` in front of `stream`.
+ * dtype = SNERF_DT_BF16 (what the entries without the suffix run; they forward here) or SNERF_DT_F16: E / VE, the weight stream (packed
+ * from fp16 weights), the stored activations and the xin copies are fp16, the products run on the f16 MFMA with fp32 accumulation, the
+ * heads leave from the unrounded fp32 accumulator.  pts / x inputs are rounded to fp16 to nearest even, as snerf_classic_embed /
+ * snerf_cast_pad round for SNERF_DT_F16, so "x flavour == snerf_cast_pad + rows flavour, bit for bit" holds in fp16 too.  The ReLU bit
+ * masks have the same layout and meaning (a 16-bit ReLU output is > 0 iff its bits are not 0).  Any other dtype: SNERF_ERR_ARG, before
+ * anything touches a device. */
+int snerf_fmlp_classic_fwd_dt(const void* E, long ldE, const void* VE, long ldVE, const void* wstream, long n_frags, const float* bias,
+                              int n_blocks, float* raw, long M, int dtype, void* stream);
+int snerf_fmlp_proposal_fwd_dt(const void* E, long ldE, const void* wstream, long n_frags, const float* bias, int n_blocks,
+                               float* raw_density, long M, int dtype, void* stream);
+int snerf_fmlp_classic_pts_fwd_dt(const float* pts, const float* viewdirs, long ldvd, int S, const void* wstream, long n_frags,
+                                  const float* bias, int n_blocks, float* raw, long M, int dtype, void* stream);
+int snerf_fmlp_classic_x_fwd_dt(const float* x, long ldx, const void* wstream, long n_frags, const float* bias, int n_blocks, float* raw,
+                                long M, int dtype, void* stream);
+int snerf_fmlp_classic_x_train_fwd_dt(const float* x, long ldx, const void* wstream, long n_frags, const float* bias, int n_blocks,
+                                      float* raw, void* const* xin, const long* xin_ld, void* const* acts, const long* act_ld,
+                                      void* const* bits, long M, int dtype, void* stream);
+int snerf_fmlp_classic_train_fwd_dt(const void* E, long ldE, const void* VE, long ldVE, const void* wstream, long n_frags,
+                                    const float* bias, int n_blocks, float* raw, void* const* acts, const long* act_ld,
+                                    void* const* bits, long M, int dtype, void* stream);
+int snerf_fmlp_proposal_train_fwd_dt(const void* E, long ldE, const void* wstream, long n_frags, const float* bias, int n_blocks,
+                                     float* raw_density, void* const* acts, const long* act_ld, void* const* bits, long M,
+                                     int dtype, void* stream);
 
 /* NeRF MLP of the zipnerf path at INFERENCE as one launch (s-nerfpp/zipnerf/internal/models.py:462-479, 586-703; waymo.gin branch, no GLO
  * vectors): F [M, ldF >= 64] grid features (columns 40.. zero) and D [M, ldD >= 16] direction encoding (columns 9.. zero) in `dtype`
@@ -628,6 +652,12 @@ int snerf_fcolour_bwd(const float* d_raw_rgb, const void* wstream, long n_frags,
 long snerf_fchain_bwd_ws_floats(int net, long M);
 int snerf_fchain_bwd(int net, const float* d_raw, const void* wstream, long n_frags, void* const* bits, void* const* dz, const long* dz_ld,
                      float* const* g_bias, float* ws, long ws_floats, long M, void* stream);
+/* ... in either 16-bit flavour (library version >= 2; snerf_fchain_bwd forwards here with SNERF_DT_BF16): dtype = SNERF_DT_BF16 or
+ * SNERF_DT_F16 = the type of the weight stream and of every dz; d_raw is rounded to it (nearest even).  Nothing is scaled: under an fp16
+ * loss scale d_raw arrives multiplied by it and the caller unscales what it reads.  The bias gradients are fp32 sums of the unrounded
+ * accumulators either way.  Any other dtype: SNERF_ERR_ARG before anything touches a device. */
+int snerf_fchain_bwd_dt(int net, const float* d_raw, const void* wstream, long n_frags, void* const* bits, void* const* dz, const long* dz_ld,
+                        float* const* g_bias, float* ws, long ws_floats, long M, int dtype, void* stream);
 
 /* ---- deterministic mode ("deterministic mode for parity tests") ------------------------------------------
  * The weight gradient normally lands in dW by fp32 atomics from the M slices (order varies run to run).  snerf_linear_wgrad_det makes

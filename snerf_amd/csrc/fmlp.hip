@@ -5,6 +5,8 @@
 //                             pts embedding (63) -> 8 x [Linear 256 + ReLU], cat([pts, h]) after layer 4 -> alpha, feature,
 //                             [feature | view embedding (27)] -> 128 ReLU -> rgb.  593 408 MAC per sample, 12 values out.
 //   snerf_fmlp_proposal_fwd : proposal MLP of the live mip path (s-nerf/model/models.py:299-325): IPE (96) -> 4 x [256 + ReLU] -> 1.
+//   Both, their training forwards and their data-gradient chains (fchain_bwd_kernel) exist in two 16-bit flavours, bf16 and fp16
+//   (template parameter F16; the `_dt` entries): the text below says "bf16" for the operand type of either.
 //
 // Why: as separate GEMM launches these layers are HBM-bound (K = N = 256: 128 FLOP per byte of activation traffic; measured
 // 0.16 of the MFMA peak).  Here nothing but the encoded input (128 - 192 B) and the raw outputs (4 - 16 B) of a
@@ -163,6 +165,18 @@ __device__ __forceinline__ void mac_seq(C& c, f32x16& acc, const bf16x8 (&in)[NK
 template <int F, int NK, typename C>
 __device__ __forceinline__ void mac(C& c, f32x16& acc, const bf16x8 (&in)[NK]) {
   mac_seq<F, NK>(c, acc, in, std::make_integer_sequence<int, NK>{});
+}
+
+// eight fp32 values -> eight 16-bit operands of the flavour, round to nearest even either way (v_cvt_pk_bf16_f32 / v_cvt_f16_f32: the
+// conversions snerf_cast_pad applies), never the round-toward-zero pack conversion
+template <bool F16>
+__device__ __forceinline__ bf16x8 cvt_operand(const __attribute__((ext_vector_type(8))) float& v) {
+  if constexpr (F16) {
+    typedef _Float16 fm_f16x8 __attribute__((ext_vector_type(8)));
+    return __builtin_bit_cast(bf16x8, __builtin_convertvector(v, fm_f16x8));
+  } else {
+    return __builtin_convertvector(v, bf16x8);
+  }
 }
 
 // accumulator -> the two B fragments (k-steps 2 j, 2 j + 1) of the next layer
@@ -354,22 +368,22 @@ __device__ __forceinline__ float embed_feature(const Vec3& x, bool hi_half) {
   return v;
 }
 
-template <int S, int WIDTH>
+template <int S, int WIDTH, bool F16 = false>
 __device__ __forceinline__ bf16x8 embed_frag(const Vec3& x, bool hi_half) {
   typedef __attribute__((ext_vector_type(8))) float f32x8;
   const f32x8 v = {embed_feature<16 * S + 0, WIDTH>(x, hi_half), embed_feature<16 * S + 1, WIDTH>(x, hi_half),
                    embed_feature<16 * S + 2, WIDTH>(x, hi_half), embed_feature<16 * S + 3, WIDTH>(x, hi_half),
                    embed_feature<16 * S + 4, WIDTH>(x, hi_half), embed_feature<16 * S + 5, WIDTH>(x, hi_half),
                    embed_feature<16 * S + 6, WIDTH>(x, hi_half), embed_feature<16 * S + 7, WIDTH>(x, hi_half)};
-  return __builtin_convertvector(v, bf16x8);
+  return cvt_operand<F16>(v);
 }
 
-template <int NK, int WIDTH>
+template <int NK, int WIDTH, bool F16 = false>
 __device__ __forceinline__ void embed_frags(const Vec3& x, bool hi_half, bf16x8 (&out)[NK]) {
-  out[0] = embed_frag<0, WIDTH>(x, hi_half);
-  if constexpr (NK > 1) out[1] = embed_frag<1, WIDTH>(x, hi_half);
-  if constexpr (NK > 2) out[2] = embed_frag<2, WIDTH>(x, hi_half);
-  if constexpr (NK > 3) out[3] = embed_frag<3, WIDTH>(x, hi_half);
+  out[0] = embed_frag<0, WIDTH, F16>(x, hi_half);
+  if constexpr (NK > 1) out[1] = embed_frag<1, WIDTH, F16>(x, hi_half);
+  if constexpr (NK > 2) out[2] = embed_frag<2, WIDTH, F16>(x, hi_half);
+  if constexpr (NK > 3) out[3] = embed_frag<3, WIDTH, F16>(x, hi_half);
   static_assert(NK <= 4, "embedding wider than 64 features");
 }
 
@@ -378,33 +392,35 @@ struct ClassicInputs { bf16x8 e[4], ve[2]; };
 // ---- pre-embedded fp32 inputs (NeRF.forward(x), run_nerf_helpers.py:103-104: torch.split(x, [63, 27], -1)) -----------------------
 // Lane (row, half) reads the features k = 16 s + 8 half + e of its row: x[k] for the embedding fragments e[s], x[63 + k] (k < 27) for
 // the view fragments ve[s]; the pad features are zero.  A row of 90 floats is only 8-byte aligned, the view block (offset 63) only
-// 4-byte aligned, and a column slice of a wider tensor (any ldX) not even that: dword loads, no 16-byte vectors.  The round to bf16 is
-// the conversion snerf_cast_pad applies (round to nearest even), so this input flavour is bit-identical to snerf_cast_pad into bf16
-// buffers followed by the buffer-reading flavour.
-template <int K0, int N>
+// 4-byte aligned, and a column slice of a wider tensor (any ldX) not even that: dword loads, no 16-byte vectors.  The round to bf16 /
+// fp16 is the conversion snerf_cast_pad applies (round to nearest even), so this input flavour is bit-identical to snerf_cast_pad into
+// buffers of the compute dtype followed by the buffer-reading flavour.
+template <int K0, int N, bool F16 = false>
 __device__ __forceinline__ bf16x8 x_frag(const float* r) {      // features K0 .. K0 + 7 of a block of N (r: the block's first column)
   typedef __attribute__((ext_vector_type(8))) float f32x8;
   f32x8 v;
 #pragma unroll
   for (int e = 0; e < 8; ++e) v[e] = K0 + e < N ? r[K0 + e] : 0.f;
-  return __builtin_convertvector(v, bf16x8);
+  return cvt_operand<F16>(v);
 }
+template <bool F16 = false>
 __device__ __forceinline__ ClassicInputs classic_x_inputs(const float* r, bool hi_half) {
   ClassicInputs in;
   if (hi_half) {
-    in.e[0] = x_frag<8, 63>(r); in.e[1] = x_frag<24, 63>(r); in.e[2] = x_frag<40, 63>(r); in.e[3] = x_frag<56, 63>(r);
-    in.ve[0] = x_frag<8, 27>(r + 63); in.ve[1] = x_frag<24, 27>(r + 63);
+    in.e[0] = x_frag<8, 63, F16>(r); in.e[1] = x_frag<24, 63, F16>(r); in.e[2] = x_frag<40, 63, F16>(r); in.e[3] = x_frag<56, 63, F16>(r);
+    in.ve[0] = x_frag<8, 27, F16>(r + 63); in.ve[1] = x_frag<24, 27, F16>(r + 63);
   } else {
-    in.e[0] = x_frag<0, 63>(r); in.e[1] = x_frag<16, 63>(r); in.e[2] = x_frag<32, 63>(r); in.e[3] = x_frag<48, 63>(r);
-    in.ve[0] = x_frag<0, 27>(r + 63); in.ve[1] = x_frag<16, 27>(r + 63);
+    in.e[0] = x_frag<0, 63, F16>(r); in.e[1] = x_frag<16, 63, F16>(r); in.e[2] = x_frag<32, 63, F16>(r); in.e[3] = x_frag<48, 63, F16>(r);
+    in.ve[0] = x_frag<0, 27, F16>(r + 63); in.ve[1] = x_frag<16, 27, F16>(r + 63);
   }
   return in;
 }
+template <bool F16 = false>
 __device__ __forceinline__ ClassicInputs classic_embed_inputs(const float* pp, const float* vp, bool hi_half) {
   const Vec3 x{pp[0], pp[1], pp[2]}, v{vp[0], vp[1], vp[2]};
   ClassicInputs r;
-  embed_frags<4, 63>(x, hi_half, r.e);                    // get_embedder(10): 63 features (+ 1 zero)
-  embed_frags<2, 27>(v, hi_half, r.ve);                   // get_embedder(4): 27 features (+ 5 zeros)
+  embed_frags<4, 63, F16>(x, hi_half, r.e);               // get_embedder(10): 63 features (+ 1 zero)
+  embed_frags<2, 27, F16>(v, hi_half, r.ve);              // get_embedder(4): 27 features (+ 5 zeros)
   return r;
 }
 
@@ -445,14 +461,16 @@ __device__ __forceinline__ void ctx_start(C& c, char* smem, const char* wstream,
 #define FM_IN_PTS 1
 #define FM_IN_X 2
 
-template <int NET, int IN, bool STORE>
+// the network pass in either 16-bit flavour: F16 = fp16 operand rows, weight stream, stored activations and xin copies (compute="fp16"),
+// the f16 MFMA and fp16 input conversions; the heads leave from the unrounded fp32 accumulator either way
+template <int NET, int IN, bool STORE, bool F16 = false>
 __global__ __launch_bounds__(64 * FM_WAVES, 2) void fmlp_kernel(FmlpArgs a) {   // (second argument: waves per SIMD -> at most 256 VGPRs)
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int half = lane >> 5;
 
-  CtxT<FM_RING> c;
+  CtxT<FM_RING, F16> c;
   ctx_start(c, smem, a.wstream, a.n_chunks, a.bias, a.n_blocks, tid, wave, lane);
 
   for (int tile = blockIdx.x; tile < a.tiles; tile += gridDim.x) {
@@ -463,12 +481,12 @@ __global__ __launch_bounds__(64 * FM_WAVES, 2) void fmlp_kernel(FmlpArgs a) {   
     if constexpr (NET == FMLP_CLASSIC) {
       bf16x8 e[4], ve[2], p[16], q[16];
       if constexpr (IN == FM_IN_PTS) {
-        const ClassicInputs in = classic_embed_inputs(a.pts + row * 3, a.viewdirs + (long)((unsigned)row / (unsigned)a.S) * a.ldvd, half != 0);   // (M < 2^31 rows, checked by the launcher)
+        const ClassicInputs in = classic_embed_inputs<F16>(a.pts + row * 3, a.viewdirs + (long)((unsigned)row / (unsigned)a.S) * a.ldvd, half != 0);   // (M < 2^31 rows, checked by the launcher)
 #pragma unroll
         for (int i = 0; i < 4; ++i) e[i] = in.e[i];
         ve[0] = in.ve[0]; ve[1] = in.ve[1];
       } else if constexpr (IN == FM_IN_X) {
-        const ClassicInputs in = classic_x_inputs(a.X + row * a.ldX, half != 0);
+        const ClassicInputs in = classic_x_inputs<F16>(a.X + row * a.ldX, half != 0);
 #pragma unroll
         for (int i = 0; i < 4; ++i) e[i] = in.e[i];
         ve[0] = in.ve[0]; ve[1] = in.ve[1];
@@ -975,7 +993,13 @@ __device__ __forceinline__ void chain_block(C& c, const bf16x8 (&in)[NK], const 
 #pragma unroll
   for (int r = 0; r < 16; ++r) acc[r] = 0.f;
   mac<F, NK>(c, acc, in);
-  if constexpr (EXTRA) acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(next_frag<F + NK>(c), extra, acc, 0, 0, 0);
+  if constexpr (EXTRA) {
+    if constexpr (C::f16) {
+      typedef _Float16 fm_f16x8 __attribute__((ext_vector_type(8)));
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(fm_f16x8, next_frag<F + NK>(c)), __builtin_bit_cast(fm_f16x8, extra), acc, 0, 0, 0);
+    } else
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(next_frag<F + NK>(c), extra, acc, 0, 0, 0);
+  }
 #define FCH_MASK1(R, NQ, E) { const float v = acc[R]; acc[R] = __builtin_bit_cast(float, __builtin_bit_cast(int, v) & __builtin_amdgcn_sbfe(NQ, E, 1)); }
 #define FCH_MASK4(Q) { const unsigned wq = w[Q]; const int nq = MASKED ? (row_ok ? (int)(wq >> sh) : 0) : (row_ok ? -1 : 0); \
                        FCH_MASK1(4 * Q + 0, nq, MASKED ? 0 : 0) FCH_MASK1(4 * Q + 1, nq, MASKED ? 1 : 0) FCH_MASK1(4 * Q + 2, nq, MASKED ? 2 : 0) FCH_MASK1(4 * Q + 3, nq, MASKED ? 3 : 0) }
@@ -989,7 +1013,7 @@ __device__ __forceinline__ void chain_block(C& c, const bf16x8 (&in)[NK], const 
       asm volatile("ds_add_f32 %0, %1 offset:%2" ::"v"(k.tab0), "v"(rs), "n"(32 * G * 4) : "memory");
     }
   }
-  to_frags<false>(acc, lo, hi);
+  to_frags<false, C::f16>(acc, lo, hi);
   store_block<false, J>(st, lo, hi);
 }
 template <int F, int NK, bool EXTRA, bool MASKED, int NB, int G0, bool LAST, typename C, int... J>
@@ -1010,7 +1034,8 @@ __device__ __forceinline__ void chain_step(C& c, const bf16x8 (&in)[NK], const b
 #define FCH_PROPOSAL_FRAGS 400                   // 8 + 3 x 128 = 392, padded
 #define FCH_PROPOSAL_COLS (4 * 256)              // layers.3 .. .0
 
-template <int NET>
+// (F16: d raw is rounded to fp16, the stream and the stored dz are fp16 -- the gradients arrive scaled by the caller, nothing is scaled here)
+template <int NET, bool F16 = false>
 __global__ __launch_bounds__(64 * FM_WAVES, 2) void fchain_bwd_kernel(ChainArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -1041,7 +1066,7 @@ __global__ __launch_bounds__(64 * FM_WAVES, 2) void fchain_bwd_kernel(ChainArgs 
   }
   ColsumCtx k;
   colsum_start(k, slab, cs, lane);
-  CtxT<FCH_RING> c;
+  CtxT<FCH_RING, F16> c;
   ctx_start(c, smem, a.wstream, a.n_chunks, nullptr, 0, tid, wave, lane);        // (ends with a barrier: the zeroed table is visible)
   const int sh = 8 * ((lane & 31) >> 3) + 4 * half;     // this lane's nibble inside a mask word
 
@@ -1065,8 +1090,8 @@ __global__ __launch_bounds__(64 * FM_WAVES, 2) void fchain_bwd_kernel(ChainArgs 
       const f32x4 dr = *(const f32x4*)(mk + 2560 + (ln & 31) * 16);
       const f32x8 v0 = {half == 0 ? dr[0] : 0.f, half == 0 ? dr[1] : 0.f, half == 0 ? dr[2] : 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
       const f32x8 v1 = {half == 0 ? dr[3] : 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-      bf16x8 g[1] = {__builtin_convertvector(v0, bf16x8)};
-      const bf16x8 ga = __builtin_convertvector(v1, bf16x8);
+      bf16x8 g[1] = {cvt_operand<F16>(v0)};
+      const bf16x8 ga = cvt_operand<F16>(v1);
       bf16x8 hv[8];
       chain_step<0, 1, false, true, 4, 0>(c, g, none, mk + 2048, ln, sh, row_ok, k, hv, to(0, 2));                       // d views_linears.0 (masked by its output)
       dma_mask(7, 0, row0, ln);                                                                                      // -> A: pts_linears.7's masks
@@ -1094,7 +1119,7 @@ __global__ __launch_bounds__(64 * FM_WAVES, 2) void fchain_bwd_kernel(ChainArgs 
     } else {
       const float dr = *(const float*)(mk + 2560 + (ln & 31) * 4);
       const f32x8 v0 = {half == 0 ? dr : 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-      bf16x8 g[1] = {__builtin_convertvector(v0, bf16x8)};
+      bf16x8 g[1] = {cvt_operand<F16>(v0)};
       dma_mask(2, 1, row0, ln);                          // -> B: layers.2's masks (A holds layers.3's, fetched during the previous tile)
       chain_step<0, 1, false, true, 8, 0>(c, g, none, mk, ln, sh, row_ok, k, p, to(0, 4));                              // d layers.3
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (the first step is 8 fragments long: too short for the counted wait)
@@ -1323,8 +1348,13 @@ __global__ __launch_bounds__(256) void fcolour_colsum_fold_kernel(const float* _
   }
 }
 
+// the `_dt` entries: dtype = SNERF_DT_BF16 or SNERF_DT_F16, the type of the operand rows, of the weight stream and of everything the
+// training forward stores; anything else is refused before a pointer is looked at
+static bool fmlp_dt_ok(int dtype) { return dtype == SNERF_DT_BF16 || dtype == SNERF_DT_F16; }
+
 template <int NET, int IN, bool STORE = false>
-static int fmlp_launch(const FmlpArgs& a, int expect_frags, int expect_blocks, long n_frags, void* stream) {
+static int fmlp_launch(const FmlpArgs& a, int expect_frags, int expect_blocks, long n_frags, int dtype, void* stream) {
+  if (!fmlp_dt_ok(dtype)) return SNERF_ERR_ARG;
   if (a.M <= 0) return SNERF_OK;
   if (n_frags != expect_frags || a.n_blocks != expect_blocks || a.n_blocks > FM_BIAS_MAX || (n_frags % FM_CHUNK) != 0) return SNERF_ERR_ARG;
   if (a.wstream == nullptr || a.bias == nullptr || a.out == nullptr || (((uintptr_t)a.wstream) & 15)) return SNERF_ERR_ARG;
@@ -1334,6 +1364,7 @@ static int fmlp_launch(const FmlpArgs& a, int expect_frags, int expect_blocks, l
   static int n_cu = 256;
   if (!attr_set) {
     (void)hipFuncSetAttribute((const void*)fmlp_kernel<NET, IN, STORE>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+    (void)hipFuncSetAttribute((const void*)fmlp_kernel<NET, IN, STORE, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
     int dev = 0;
     hipDeviceProp_t prop;
     if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
@@ -1341,18 +1372,24 @@ static int fmlp_launch(const FmlpArgs& a, int expect_frags, int expect_blocks, l
     attr_set = true;
   }
   const int grid = a.tiles < n_cu * FM_WG_PER_CU ? a.tiles : n_cu * FM_WG_PER_CU;
-  hipLaunchKernelGGL((fmlp_kernel<NET, IN, STORE>), dim3(grid), dim3(64 * FM_WAVES), LDS, (hipStream_t)stream, a);
+  if (dtype == SNERF_DT_F16) hipLaunchKernelGGL((fmlp_kernel<NET, IN, STORE, true>), dim3(grid), dim3(64 * FM_WAVES), LDS, (hipStream_t)stream, a);
+  else hipLaunchKernelGGL((fmlp_kernel<NET, IN, STORE>), dim3(grid), dim3(64 * FM_WAVES), LDS, (hipStream_t)stream, a);
   return snerf_check_launch();
 }
 
-extern "C" int snerf_fmlp_classic_fwd(const void* E, long ldE, const void* VE, long ldVE, const void* wstream, long n_frags, const float* bias,
-                                      int n_blocks, float* raw, long M, void* stream) {
+extern "C" int snerf_fmlp_classic_fwd_dt(const void* E, long ldE, const void* VE, long ldVE, const void* wstream, long n_frags, const float* bias,
+                                         int n_blocks, float* raw, long M, int dtype, void* stream) {
+  if (!fmlp_dt_ok(dtype)) return SNERF_ERR_ARG;
   if (M <= 0) return SNERF_OK;
   if (VE == nullptr || (ldVE % 8) != 0 || (((uintptr_t)VE) & 15) || (((uintptr_t)raw) & 15)) return SNERF_ERR_ARG;
   FmlpArgs a{};
   a.E = (const __bf16*)E; a.ldE = ldE; a.VE = (const __bf16*)VE; a.ldVE = ldVE; a.S = 1; a.wstream = (const char*)wstream; a.bias = bias; a.out = raw;
   a.M = M; a.tiles = (int)((M + FM_TILE_ROWS - 1) / FM_TILE_ROWS); a.n_chunks = (int)(n_frags / FM_CHUNK); a.n_blocks = n_blocks;
-  return fmlp_launch<FMLP_CLASSIC, FM_IN_ROWS>(a, FMLP_CLASSIC_FRAGS, FMLP_CLASSIC_BLOCKS, n_frags, stream);
+  return fmlp_launch<FMLP_CLASSIC, FM_IN_ROWS>(a, FMLP_CLASSIC_FRAGS, FMLP_CLASSIC_BLOCKS, n_frags, dtype, stream);
+}
+extern "C" int snerf_fmlp_classic_fwd(const void* E, long ldE, const void* VE, long ldVE, const void* wstream, long n_frags, const float* bias,
+                                      int n_blocks, float* raw, long M, void* stream) {
+  return snerf_fmlp_classic_fwd_dt(E, ldE, VE, ldVE, wstream, n_frags, bias, n_blocks, raw, M, SNERF_DT_BF16, stream);
 }
 
 // Training forward of the same network: additionally stores the outputs of the ten hidden layers for the backward pass --
@@ -1360,9 +1397,10 @@ extern "C" int snerf_fmlp_classic_fwd(const void* E, long ldE, const void* VE, l
 // (256), views_linears.0 (128); every pointer 16-byte aligned, every stride a multiple of 8 -- and bits[i] (HOST array of 9 device
 // pointers): the ReLU bit masks of pts_linears.i (i < 8: 4 * 8 * ceil(M / 256) * 4 * 64 bytes each) and of views_linears.0 (i = 8:
 // half that) in the layout snerf_linear_fwd's ACT_MASK_BITS reads.
-extern "C" int snerf_fmlp_classic_train_fwd(const void* E, long ldE, const void* VE, long ldVE, const void* wstream, long n_frags,
-                                            const float* bias, int n_blocks, float* raw, void* const* acts, const long* act_ld,
-                                            void* const* bits, long M, void* stream) {
+extern "C" int snerf_fmlp_classic_train_fwd_dt(const void* E, long ldE, const void* VE, long ldVE, const void* wstream, long n_frags,
+                                               const float* bias, int n_blocks, float* raw, void* const* acts, const long* act_ld,
+                                               void* const* bits, long M, int dtype, void* stream) {
+  if (!fmlp_dt_ok(dtype)) return SNERF_ERR_ARG;
   if (M <= 0) return SNERF_OK;
   if (VE == nullptr || (ldVE % 8) != 0 || (((uintptr_t)VE) & 15) || (((uintptr_t)raw) & 15) || acts == nullptr || act_ld == nullptr || bits == nullptr)
     return SNERF_ERR_ARG;
@@ -1377,22 +1415,32 @@ extern "C" int snerf_fmlp_classic_train_fwd(const void* E, long ldE, const void*
       a.bits[i] = (unsigned*)bits[i];
     }
   }
-  return fmlp_launch<FMLP_CLASSIC, FM_IN_ROWS, true>(a, FMLP_CLASSIC_FRAGS, FMLP_CLASSIC_BLOCKS, n_frags, stream);
+  return fmlp_launch<FMLP_CLASSIC, FM_IN_ROWS, true>(a, FMLP_CLASSIC_FRAGS, FMLP_CLASSIC_BLOCKS, n_frags, dtype, stream);
+}
+extern "C" int snerf_fmlp_classic_train_fwd(const void* E, long ldE, const void* VE, long ldVE, const void* wstream, long n_frags,
+                                            const float* bias, int n_blocks, float* raw, void* const* acts, const long* act_ld,
+                                            void* const* bits, long M, void* stream) {
+  return snerf_fmlp_classic_train_fwd_dt(E, ldE, VE, ldVE, wstream, n_frags, bias, n_blocks, raw, acts, act_ld, bits, M, SNERF_DT_BF16, stream);
 }
 
 // the same network with the positional encodings computed in the kernel: pts [M,3] fp32 sample positions, viewdirs [M / S, ldvd]
-extern "C" int snerf_fmlp_classic_pts_fwd(const float* pts, const float* viewdirs, long ldvd, int S, const void* wstream, long n_frags,
-                                          const float* bias, int n_blocks, float* raw, long M, void* stream) {
+extern "C" int snerf_fmlp_classic_pts_fwd_dt(const float* pts, const float* viewdirs, long ldvd, int S, const void* wstream, long n_frags,
+                                             const float* bias, int n_blocks, float* raw, long M, int dtype, void* stream) {
+  if (!fmlp_dt_ok(dtype)) return SNERF_ERR_ARG;
   if (M <= 0) return SNERF_OK;
   if (pts == nullptr || viewdirs == nullptr || S <= 0 || ldvd < 3 || (((uintptr_t)raw) & 15) || M >= (1L << 31)) return SNERF_ERR_ARG;
   FmlpArgs a{};
   a.pts = pts; a.viewdirs = viewdirs; a.ldvd = ldvd; a.S = S; a.wstream = (const char*)wstream; a.bias = bias; a.out = raw;
   a.M = M; a.tiles = (int)((M + FM_TILE_ROWS - 1) / FM_TILE_ROWS); a.n_chunks = (int)(n_frags / FM_CHUNK); a.n_blocks = n_blocks;
-  return fmlp_launch<FMLP_CLASSIC, FM_IN_PTS>(a, FMLP_CLASSIC_FRAGS, FMLP_CLASSIC_BLOCKS, n_frags, stream);
+  return fmlp_launch<FMLP_CLASSIC, FM_IN_PTS>(a, FMLP_CLASSIC_FRAGS, FMLP_CLASSIC_BLOCKS, n_frags, dtype, stream);
+}
+extern "C" int snerf_fmlp_classic_pts_fwd(const float* pts, const float* viewdirs, long ldvd, int S, const void* wstream, long n_frags,
+                                          const float* bias, int n_blocks, float* raw, long M, void* stream) {
+  return snerf_fmlp_classic_pts_fwd_dt(pts, viewdirs, ldvd, S, wstream, n_frags, bias, n_blocks, raw, M, SNERF_DT_BF16, stream);
 }
 
 // the same network on pre-embedded fp32 rows x [M, ldX >= 90] (NeRF.forward(x)): columns [0, 63) = embedded points, [63, 90) =
-// embedded view directions, any row stride, 4-byte alignment.  Rounded to bf16 in registers exactly as snerf_cast_pad does.
+// embedded view directions, any row stride, 4-byte alignment.  Rounded to bf16 / fp16 in registers exactly as snerf_cast_pad does.
 static int fmlp_x_args(FmlpArgs& a, const float* x, long ldx, const void* wstream, long n_frags, const float* bias, int n_blocks, float* raw, long M) {
   if (x == nullptr || ldx < 90 || (((uintptr_t)x) & 3) || raw == nullptr || (((uintptr_t)raw) & 15) || M >= (1L << 31)) return SNERF_ERR_ARG;
   a.X = x; a.ldX = ldx; a.S = 1; a.wstream = (const char*)wstream; a.bias = bias; a.out = raw;
@@ -1400,21 +1448,27 @@ static int fmlp_x_args(FmlpArgs& a, const float* x, long ldx, const void* wstrea
   return SNERF_OK;
 }
 
-extern "C" int snerf_fmlp_classic_x_fwd(const float* x, long ldx, const void* wstream, long n_frags, const float* bias, int n_blocks, float* raw,
-                                        long M, void* stream) {
+extern "C" int snerf_fmlp_classic_x_fwd_dt(const float* x, long ldx, const void* wstream, long n_frags, const float* bias, int n_blocks, float* raw,
+                                           long M, int dtype, void* stream) {
+  if (!fmlp_dt_ok(dtype)) return SNERF_ERR_ARG;
   if (M <= 0) return SNERF_OK;
   FmlpArgs a{};
   const int rc = fmlp_x_args(a, x, ldx, wstream, n_frags, bias, n_blocks, raw, M);
   if (rc != SNERF_OK) return rc;
-  return fmlp_launch<FMLP_CLASSIC, FM_IN_X>(a, FMLP_CLASSIC_FRAGS, FMLP_CLASSIC_BLOCKS, n_frags, stream);
+  return fmlp_launch<FMLP_CLASSIC, FM_IN_X>(a, FMLP_CLASSIC_FRAGS, FMLP_CLASSIC_BLOCKS, n_frags, dtype, stream);
+}
+extern "C" int snerf_fmlp_classic_x_fwd(const float* x, long ldx, const void* wstream, long n_frags, const float* bias, int n_blocks, float* raw,
+                                        long M, void* stream) {
+  return snerf_fmlp_classic_x_fwd_dt(x, ldx, wstream, n_frags, bias, n_blocks, raw, M, SNERF_DT_BF16, stream);
 }
 
 // training forward on x: snerf_fmlp_classic_train_fwd's stores (acts / act_ld / bits) plus the rounded inputs -- xin[0] = E [M, >= 64]
 // (the operand of pts_linears.0), xin[1] = the head of the skip buffer (64 columns), xin[2] = the view tail of [feature | views] (32
 // columns); columns 63 / 27.. are written as zeros.  Every pointer 16-byte aligned, every stride a multiple of 8.
-extern "C" int snerf_fmlp_classic_x_train_fwd(const float* x, long ldx, const void* wstream, long n_frags, const float* bias, int n_blocks,
-                                              float* raw, void* const* xin, const long* xin_ld, void* const* acts, const long* act_ld,
-                                              void* const* bits, long M, void* stream) {
+extern "C" int snerf_fmlp_classic_x_train_fwd_dt(const float* x, long ldx, const void* wstream, long n_frags, const float* bias, int n_blocks,
+                                                 float* raw, void* const* xin, const long* xin_ld, void* const* acts, const long* act_ld,
+                                                 void* const* bits, long M, int dtype, void* stream) {
+  if (!fmlp_dt_ok(dtype)) return SNERF_ERR_ARG;
   if (M <= 0) return SNERF_OK;
   if (xin == nullptr || xin_ld == nullptr || acts == nullptr || act_ld == nullptr || bits == nullptr) return SNERF_ERR_ARG;
   FmlpArgs a{};
@@ -1432,22 +1486,32 @@ extern "C" int snerf_fmlp_classic_x_train_fwd(const float* x, long ldx, const vo
       a.bits[i] = (unsigned*)bits[i];
     }
   }
-  return fmlp_launch<FMLP_CLASSIC, FM_IN_X, true>(a, FMLP_CLASSIC_FRAGS, FMLP_CLASSIC_BLOCKS, n_frags, stream);
+  return fmlp_launch<FMLP_CLASSIC, FM_IN_X, true>(a, FMLP_CLASSIC_FRAGS, FMLP_CLASSIC_BLOCKS, n_frags, dtype, stream);
+}
+extern "C" int snerf_fmlp_classic_x_train_fwd(const float* x, long ldx, const void* wstream, long n_frags, const float* bias, int n_blocks,
+                                              float* raw, void* const* xin, const long* xin_ld, void* const* acts, const long* act_ld,
+                                              void* const* bits, long M, void* stream) {
+  return snerf_fmlp_classic_x_train_fwd_dt(x, ldx, wstream, n_frags, bias, n_blocks, raw, xin, xin_ld, acts, act_ld, bits, M, SNERF_DT_BF16, stream);
 }
 
-extern "C" int snerf_fmlp_proposal_fwd(const void* E, long ldE, const void* wstream, long n_frags, const float* bias, int n_blocks,
-                                       float* raw_density, long M, void* stream) {
+extern "C" int snerf_fmlp_proposal_fwd_dt(const void* E, long ldE, const void* wstream, long n_frags, const float* bias, int n_blocks,
+                                          float* raw_density, long M, int dtype, void* stream) {
   FmlpArgs a{};
   a.E = (const __bf16*)E; a.ldE = ldE; a.S = 1; a.wstream = (const char*)wstream; a.bias = bias; a.out = raw_density;
   a.M = M; a.tiles = (int)((M + FM_TILE_ROWS - 1) / FM_TILE_ROWS); a.n_chunks = (int)(n_frags / FM_CHUNK); a.n_blocks = n_blocks;
   // 8 x 6 + 3 x 128 + 16 fragments; 32 + 1 blocks
-  return fmlp_launch<FMLP_PROPOSAL, FM_IN_ROWS>(a, 448, 33, n_frags, stream);
+  return fmlp_launch<FMLP_PROPOSAL, FM_IN_ROWS>(a, 448, 33, n_frags, dtype, stream);
+}
+extern "C" int snerf_fmlp_proposal_fwd(const void* E, long ldE, const void* wstream, long n_frags, const float* bias, int n_blocks,
+                                       float* raw_density, long M, void* stream) {
+  return snerf_fmlp_proposal_fwd_dt(E, ldE, wstream, n_frags, bias, n_blocks, raw_density, M, SNERF_DT_BF16, stream);
 }
 
 // training forward of the proposal MLP: acts[0..3] = outputs of layers.0 .. .3 (256 wide)
-extern "C" int snerf_fmlp_proposal_train_fwd(const void* E, long ldE, const void* wstream, long n_frags, const float* bias, int n_blocks,
-                                             float* raw_density, void* const* acts, const long* act_ld, void* const* bits, long M,
-                                             void* stream) {
+extern "C" int snerf_fmlp_proposal_train_fwd_dt(const void* E, long ldE, const void* wstream, long n_frags, const float* bias, int n_blocks,
+                                                float* raw_density, void* const* acts, const long* act_ld, void* const* bits, long M,
+                                                int dtype, void* stream) {
+  if (!fmlp_dt_ok(dtype)) return SNERF_ERR_ARG;
   if (M <= 0) return SNERF_OK;
   if (acts == nullptr || act_ld == nullptr || bits == nullptr) return SNERF_ERR_ARG;
   FmlpArgs a{};
@@ -1458,7 +1522,12 @@ extern "C" int snerf_fmlp_proposal_train_fwd(const void* E, long ldE, const void
     if (bits[i] == nullptr) return SNERF_ERR_ARG;
     a.act[i] = (__bf16*)acts[i]; a.act_ld[i] = act_ld[i]; a.bits[i] = (unsigned*)bits[i];
   }
-  return fmlp_launch<FMLP_PROPOSAL, FM_IN_ROWS, true>(a, 448, 33, n_frags, stream);
+  return fmlp_launch<FMLP_PROPOSAL, FM_IN_ROWS, true>(a, 448, 33, n_frags, dtype, stream);
+}
+extern "C" int snerf_fmlp_proposal_train_fwd(const void* E, long ldE, const void* wstream, long n_frags, const float* bias, int n_blocks,
+                                             float* raw_density, void* const* acts, const long* act_ld, void* const* bits, long M,
+                                             void* stream) {
+  return snerf_fmlp_proposal_train_fwd_dt(E, ldE, wstream, n_frags, bias, n_blocks, raw_density, acts, act_ld, bits, M, SNERF_DT_BF16, stream);
 }
 
 // ---- colour head (cond_layers.0..2 + rgb_layer of the mip path's NeRF MLP, hidden 1024) -------------------------------------------
@@ -1644,8 +1713,11 @@ extern "C" long snerf_fchain_bwd_ws_floats(int net, long M) {
 // = d pre-activation of layers.3 .. .0; bits[0..3] of layers.0 .. .3; n_steps = 4.
 // wstream: mlp.fmlp_pack of the transposed weights in chain order.  The bias gradient of step i is ADDED to g_bias[i] (the workgroups'
 // partial sums are reduced in LDS in arrival order: NOT bit-reproducible -- the deterministic mode uses the per-layer kernels).
-extern "C" int snerf_fchain_bwd(int net, const float* d_raw, const void* wstream, long n_frags, void* const* bits, void* const* dz, const long* dz_ld,
-                                float* const* g_bias, float* ws, long ws_floats, long M, void* stream) {
+// dtype (SNERF_DT_BF16 / SNERF_DT_F16): the type of the weight stream and of the stored dz.  d_raw arrives already scaled (the fp16 loss scale
+// is the caller's business); bias gradients are fp32 sums of the unrounded accumulators in either flavour.
+extern "C" int snerf_fchain_bwd_dt(int net, const float* d_raw, const void* wstream, long n_frags, void* const* bits, void* const* dz, const long* dz_ld,
+                                   float* const* g_bias, float* ws, long ws_floats, long M, int dtype, void* stream) {
+  if (!fmlp_dt_ok(dtype)) return SNERF_ERR_ARG;
   if (M <= 0) return SNERF_OK;
   if (net != FMLP_CLASSIC && net != FMLP_PROPOSAL) return SNERF_ERR_ARG;
   const bool classic = net == FMLP_CLASSIC;
@@ -1679,13 +1751,25 @@ extern "C" int snerf_fchain_bwd(int net, const float* d_raw, const void* wstream
   if (!attr_set) {
     (void)hipFuncSetAttribute((const void*)fchain_bwd_kernel<FMLP_CLASSIC>, hipFuncAttributeMaxDynamicSharedMemorySize, FCH_LDS(FCH_CLASSIC_COLS));
     (void)hipFuncSetAttribute((const void*)fchain_bwd_kernel<FMLP_PROPOSAL>, hipFuncAttributeMaxDynamicSharedMemorySize, FCH_LDS(FCH_PROPOSAL_COLS));
+    (void)hipFuncSetAttribute((const void*)(fchain_bwd_kernel<FMLP_CLASSIC, true>), hipFuncAttributeMaxDynamicSharedMemorySize, FCH_LDS(FCH_CLASSIC_COLS));
+    (void)hipFuncSetAttribute((const void*)(fchain_bwd_kernel<FMLP_PROPOSAL, true>), hipFuncAttributeMaxDynamicSharedMemorySize, FCH_LDS(FCH_PROPOSAL_COLS));
     attr_set = true;
   }
   hipStream_t st = (hipStream_t)stream;
-  if (classic) hipLaunchKernelGGL(fchain_bwd_kernel<FMLP_CLASSIC>, dim3(grid), dim3(64 * FM_WAVES), lds, st, a);
-  else hipLaunchKernelGGL(fchain_bwd_kernel<FMLP_PROPOSAL>, dim3(grid), dim3(64 * FM_WAVES), lds, st, a);
+  const dim3 g(grid), b(64 * FM_WAVES);
+  if (dtype == SNERF_DT_F16) {
+    if (classic) hipLaunchKernelGGL((fchain_bwd_kernel<FMLP_CLASSIC, true>), g, b, lds, st, a);
+    else hipLaunchKernelGGL((fchain_bwd_kernel<FMLP_PROPOSAL, true>), g, b, lds, st, a);
+  } else {
+    if (classic) hipLaunchKernelGGL(fchain_bwd_kernel<FMLP_CLASSIC>, g, b, lds, st, a);
+    else hipLaunchKernelGGL(fchain_bwd_kernel<FMLP_PROPOSAL>, g, b, lds, st, a);
+  }
   hipLaunchKernelGGL(fchain_colsum_fold_kernel, dim3((ncols + 63) / 64), dim3(256), 0, st, (const float*)ws, grid, ncols, tab);
   return snerf_check_launch();
+}
+extern "C" int snerf_fchain_bwd(int net, const float* d_raw, const void* wstream, long n_frags, void* const* bits, void* const* dz, const long* dz_ld,
+                                float* const* g_bias, float* ws, long ws_floats, long M, void* stream) {
+  return snerf_fchain_bwd_dt(net, d_raw, wstream, n_frags, bits, dz, dz_ld, g_bias, ws, ws_floats, M, SNERF_DT_BF16, stream);
 }
 
 // Data-gradient chain of the zipnerf NeRF MLP (fzip_chain_bwd_kernel; the backward of snerf_fmlp_zip_train_fwd).  d_rgb [M, ld_rgb >= 3], d_den

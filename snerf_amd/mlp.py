@@ -574,9 +574,9 @@ class ClassicNeRFNet(_Net):
                 self._pack_dgrad(n, [n], ic if i == self.skip + 1 else 0, W)
 
     def fused_ok(self):
-        """the register-resident fused kernel (csrc/fmlp.hip) covers the S-NeRF configuration: bf16, 8 x 256, skip after layer 4,
-        63 + 27 input channels, alpha head"""
-        return (self.fused and self.dt == ops.BF16 and self.D == 8 and self.Wd == 256 and self.skip == 4 and self.ic == 63 and self.icv == 27
+        """the register-resident fused kernel (csrc/fmlp.hip) covers the S-NeRF configuration: bf16 or fp16 (the one-pass modes; never the
+        plain backward behind a split forward), 8 x 256, skip after layer 4, 63 + 27 input channels, alpha head"""
+        return (self.fused and self.dt in (ops.BF16, ops.F16) and not self._in_plain_bwd and self.D == 8 and self.Wd == 256 and self.skip == 4 and self.ic == 63 and self.icv == 27
                 and self.alpha_head and self.output_ch == 0)
 
     def _pack_fused(self):
@@ -601,7 +601,7 @@ class ClassicNeRFNet(_Net):
         v = self.version_fn()
         if getattr(self, "_fused_version", None) != v:
             with torch.no_grad():
-                self._refresh_fused(self._pack_fused)
+                self._refresh_fused(self._pack_fused, dtype=self.tdt)
             self._fused_version = v
 
     def chain_ok(self):
@@ -624,7 +624,7 @@ class ClassicNeRFNet(_Net):
         v = self.version_fn()
         if getattr(self, "_chain_version", None) != v:
             with torch.no_grad():
-                self._chain = self._refresh_fused(self._pack_chain, "chain")
+                self._chain = self._refresh_fused(self._pack_chain, "chain", dtype=self.tdt)
             self._chain_version = v
         return self._chain[0]
 
@@ -932,7 +932,7 @@ class MipProposalNet(_Net):
             self._pack_dgrad_cols("enc", [("layers.0.layers.0", 0)], self.fd)
 
     def fused_ok(self):
-        return self.fused and self.dt == ops.BF16 and self.H == 256 and self.L == 4 and self.fd == 96
+        return self.fused and self.dt in (ops.BF16, ops.F16) and not self._in_plain_bwd and self.H == 256 and self.L == 4 and self.fd == 96
 
     def _pack_fused(self):
         L = [(self.W(f"layers.{i}.layers.0"), self.B(f"layers.{i}.layers.0"), [(0, self.fd if i == 0 else self.H, i > 0)])
@@ -944,7 +944,7 @@ class MipProposalNet(_Net):
         v = self.version_fn()
         if getattr(self, "_fused_version", None) != v:
             with torch.no_grad():
-                self._refresh_fused(self._pack_fused)
+                self._refresh_fused(self._pack_fused, dtype=self.tdt)
             self._fused_version = v
 
     def chain_ok(self):
@@ -959,7 +959,7 @@ class MipProposalNet(_Net):
         v = self.version_fn()
         if getattr(self, "_chain_version", None) != v:
             with torch.no_grad():
-                self._chain = self._refresh_fused(self._pack_chain, "chain")
+                self._chain = self._refresh_fused(self._pack_chain, "chain", dtype=self.tdt)
             self._chain_version = v
         return self._chain[0]
 

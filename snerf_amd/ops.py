@@ -184,23 +184,32 @@ def linear_wgrad(dZ, X, dW, n_valid, k_valid, dt, variant=0, deterministic=False
 
 
 # ------------------------------------------------------------ fused MLPs ----
+def _fmlp_dt(stream):
+    """the 16-bit flavour of a fused 256-wide launch = the dtype of its packed weight stream (bf16 or fp16); operand rows, stored activations,
+    xin copies and dz must carry the same one"""
+    assert stream.dtype in (torch.bfloat16, torch.float16) and stream.is_contiguous(), "the fused 256-wide networks run in bf16 or fp16"
+    return stream.dtype, _zip_dt(stream)
+
+
 def fmlp_classic_fwd(E, VE, stream, bias, raw):
-    """The whole classic NeRF 8 x 256 network in one launch (csrc/fmlp.hip): E [M,>=64] / VE [M,>=32] bf16 embeddings, `stream` /
-    `bias` from mlp.fmlp_pack -> raw [M,4] fp32."""
-    _chk2d(E, torch.bfloat16); _chk2d(VE, torch.bfloat16); _chk2d(raw, torch.float32)
-    assert stream.dtype == torch.bfloat16 and stream.is_contiguous() and bias.dtype == torch.float32 and raw.is_contiguous() and raw.shape[1] == 4
+    """The whole classic NeRF 8 x 256 network in one launch (csrc/fmlp.hip): E [M,>=64] / VE [M,>=32] embeddings in the stream's dtype
+    (bf16 or fp16), `stream` / `bias` from mlp.fmlp_pack -> raw [M,4] fp32."""
+    tdt, dt = _fmlp_dt(stream)
+    _chk2d(E, tdt); _chk2d(VE, tdt); _chk2d(raw, torch.float32)
+    assert bias.dtype == torch.float32 and raw.is_contiguous() and raw.shape[1] == 4
     assert E.shape[1] >= 64 and VE.shape[1] >= 32 and VE.shape[0] == E.shape[0] == raw.shape[0]
-    _lib.call("snerf_fmlp_classic_fwd", _p(E), E.stride(0), _p(VE), VE.stride(0), _p(stream), stream.shape[0], _p(bias), bias.numel() // 32,
-              _p(raw), E.shape[0], _stream())
+    _lib.call("snerf_fmlp_classic_fwd_dt", _p(E), E.stride(0), _p(VE), VE.stride(0), _p(stream), stream.shape[0], _p(bias), bias.numel() // 32,
+              _p(raw), E.shape[0], dt, _stream())
 
 
 def fmlp_classic_pts_fwd(pts, viewdirs, S, stream, bias, raw):
     """fmlp_classic_fwd with the embeddings computed in the kernel: pts [M,3] fp32, viewdirs [M/S,3] fp32 -> raw [M,4] fp32."""
     _f32c(pts); _chk2d(raw, torch.float32)
+    _, dt = _fmlp_dt(stream)
     assert viewdirs.dtype == torch.float32 and viewdirs.stride(1) == 1 and viewdirs.shape[1] == 3 and pts.shape[0] == viewdirs.shape[0] * S
-    assert stream.dtype == torch.bfloat16 and stream.is_contiguous() and bias.dtype == torch.float32 and raw.is_contiguous() and raw.shape == (pts.shape[0], 4)
-    _lib.call("snerf_fmlp_classic_pts_fwd", _p(pts), _p(viewdirs), viewdirs.stride(0), int(S), _p(stream), stream.shape[0], _p(bias),
-              bias.numel() // 32, _p(raw), pts.shape[0], _stream())
+    assert bias.dtype == torch.float32 and raw.is_contiguous() and raw.shape == (pts.shape[0], 4)
+    _lib.call("snerf_fmlp_classic_pts_fwd_dt", _p(pts), _p(viewdirs), viewdirs.stride(0), int(S), _p(stream), stream.shape[0], _p(bias),
+              bias.numel() // 32, _p(raw), pts.shape[0], dt, _stream())
 
 
 def _x_rows(x):
@@ -212,40 +221,45 @@ def _x_rows(x):
 
 def fmlp_classic_x_fwd(x, stream, bias, raw):
     """fmlp_classic_fwd on the caller's pre-embedded fp32 rows x [M, >= 90] = [embedded pts (63) | embedded views (27)] (any row
-    stride; rounded to bf16 in the kernel as cast_pad rounds) -> raw [M,4] fp32."""
+    stride; rounded to the stream's dtype in the kernel as cast_pad rounds) -> raw [M,4] fp32."""
     _x_rows(x); _chk2d(raw, torch.float32)
-    assert stream.dtype == torch.bfloat16 and stream.is_contiguous() and bias.dtype == torch.float32 and raw.is_contiguous() and raw.shape == (x.shape[0], 4)
-    _lib.call("snerf_fmlp_classic_x_fwd", _p(x), max(x.stride(0), 90), _p(stream), stream.shape[0], _p(bias), bias.numel() // 32, _p(raw),
-              x.shape[0], _stream())
+    _, dt = _fmlp_dt(stream)
+    assert bias.dtype == torch.float32 and raw.is_contiguous() and raw.shape == (x.shape[0], 4)
+    _lib.call("snerf_fmlp_classic_x_fwd_dt", _p(x), max(x.stride(0), 90), _p(stream), stream.shape[0], _p(bias), bias.numel() // 32, _p(raw),
+              x.shape[0], dt, _stream())
 
 
 def fmlp_classic_x_train_fwd(x, stream, bias, raw, xin, acts, bits):
-    """fmlp_classic_train_fwd on pre-embedded fp32 rows x (as fmlp_classic_x_fwd); additionally writes the bf16-rounded inputs into
-    `xin` = [E [M, >= 64], skip-buffer head [M, >= 64], view tail [M, >= 32]] (bf16 row-major views, 16-byte aligned, row strides % 8 == 0)."""
+    """fmlp_classic_train_fwd on pre-embedded fp32 rows x (as fmlp_classic_x_fwd); additionally writes the rounded inputs into
+    `xin` = [E [M, >= 64], skip-buffer head [M, >= 64], view tail [M, >= 32]] (row-major views in the stream's dtype, 16-byte aligned, row
+    strides % 8 == 0)."""
     import ctypes
     _x_rows(x); _chk2d(raw, torch.float32)
-    assert stream.dtype == torch.bfloat16 and stream.is_contiguous() and bias.dtype == torch.float32 and raw.is_contiguous() and raw.shape == (x.shape[0], 4)
+    tdt, dt = _fmlp_dt(stream)
+    assert bias.dtype == torch.float32 and raw.is_contiguous() and raw.shape == (x.shape[0], 4)
     assert len(bits) == 9 and len(xin) == 3
     M = x.shape[0]
-    ptrs, lds, bp = _act_arrays(acts, bits, M, [256] * 9 + [128])
-    xp, xl, _ = _act_arrays(xin, [], M, [64, 64, 32])
-    _lib.call("snerf_fmlp_classic_x_train_fwd", _p(x), max(x.stride(0), 90), _p(stream), stream.shape[0], _p(bias), bias.numel() // 32, _p(raw),
-              ctypes.addressof(xp), ctypes.addressof(xl), ctypes.addressof(ptrs), ctypes.addressof(lds), ctypes.addressof(bp), M, _stream())
+    ptrs, lds, bp = _act_arrays(acts, bits, M, [256] * 9 + [128], tdt)
+    xp, xl, _ = _act_arrays(xin, [], M, [64, 64, 32], tdt)
+    _lib.call("snerf_fmlp_classic_x_train_fwd_dt", _p(x), max(x.stride(0), 90), _p(stream), stream.shape[0], _p(bias), bias.numel() // 32, _p(raw),
+              ctypes.addressof(xp), ctypes.addressof(xl), ctypes.addressof(ptrs), ctypes.addressof(lds), ctypes.addressof(bp), M, dt, _stream())
+
 
 def fmlp_proposal_fwd(E, stream, bias, raw_density):
-    """The proposal MLP 96 -> 4 x 256 -> 1 in one launch: E [M,>=96] bf16 IPE rows -> raw density [M,1] fp32."""
-    _chk2d(E, torch.bfloat16)
-    assert stream.dtype == torch.bfloat16 and stream.is_contiguous() and bias.dtype == torch.float32 and E.shape[1] >= 96
+    """The proposal MLP 96 -> 4 x 256 -> 1 in one launch: E [M,>=96] IPE rows in the stream's dtype (bf16 or fp16) -> raw density [M,1] fp32."""
+    tdt, dt = _fmlp_dt(stream)
+    _chk2d(E, tdt)
+    assert bias.dtype == torch.float32 and E.shape[1] >= 96
     assert raw_density.dtype == torch.float32 and raw_density.is_contiguous() and raw_density.numel() == E.shape[0]
-    _lib.call("snerf_fmlp_proposal_fwd", _p(E), E.stride(0), _p(stream), stream.shape[0], _p(bias), bias.numel() // 32, _p(raw_density),
-              E.shape[0], _stream())
+    _lib.call("snerf_fmlp_proposal_fwd_dt", _p(E), E.stride(0), _p(stream), stream.shape[0], _p(bias), bias.numel() // 32, _p(raw_density),
+              E.shape[0], dt, _stream())
 
 
-def _act_arrays(acts, bits, M, widths):
+def _act_arrays(acts, bits, M, widths, tdt=torch.bfloat16):
     import ctypes
     assert len(acts) == len(widths)
     for y, w in zip(acts, widths):
-        assert y.dtype == torch.bfloat16 and y.dim() == 2 and y.stride(1) == 1 and y.shape[0] == M and y.shape[1] >= w
+        assert y.dtype == tdt and y.dim() == 2 and y.stride(1) == 1 and y.shape[0] == M and y.shape[1] >= w
         assert y.data_ptr() % 16 == 0 and y.stride(0) % 8 == 0
     for i, b in enumerate(bits):
         assert b.dtype == torch.int32 and b.is_contiguous() and b.numel() >= mask_bits_words(M, 128 if i == 8 else 256)
@@ -257,26 +271,28 @@ def _act_arrays(acts, bits, M, widths):
 
 def fmlp_classic_train_fwd(E, VE, stream, bias, raw, acts, bits):
     """fmlp_classic_fwd that also stores the ten hidden-layer outputs (`acts`: pts_linears.0..7 [M,256], feature [M,256], views
-    [M,128], bf16 row-major views) and the ReLU bit masks of the eight trunk layers (`bits[0..7]`: int32 [mask_bits_words(M, 256)]
+    [M,128], row-major views in the stream's dtype) and the ReLU bit masks of the eight trunk layers (`bits[0..7]`: int32 [mask_bits_words(M, 256)]
     each) and of views_linears.0 (`bits[8]`: [mask_bits_words(M, 128)]) for the backward pass."""
     import ctypes
-    _chk2d(E, torch.bfloat16); _chk2d(VE, torch.bfloat16); _chk2d(raw, torch.float32)
-    assert stream.dtype == torch.bfloat16 and stream.is_contiguous() and bias.dtype == torch.float32 and raw.is_contiguous() and raw.shape[1] == 4
+    tdt, dt = _fmlp_dt(stream)
+    _chk2d(E, tdt); _chk2d(VE, tdt); _chk2d(raw, torch.float32)
+    assert bias.dtype == torch.float32 and raw.is_contiguous() and raw.shape[1] == 4
     assert E.shape[1] >= 64 and VE.shape[1] >= 32 and VE.shape[0] == E.shape[0] == raw.shape[0] and len(bits) == 9
-    ptrs, lds, bp = _act_arrays(acts, bits, E.shape[0], [256] * 9 + [128])
-    _lib.call("snerf_fmlp_classic_train_fwd", _p(E), E.stride(0), _p(VE), VE.stride(0), _p(stream), stream.shape[0], _p(bias),
-              bias.numel() // 32, _p(raw), ctypes.addressof(ptrs), ctypes.addressof(lds), ctypes.addressof(bp), E.shape[0], _stream())
+    ptrs, lds, bp = _act_arrays(acts, bits, E.shape[0], [256] * 9 + [128], tdt)
+    _lib.call("snerf_fmlp_classic_train_fwd_dt", _p(E), E.stride(0), _p(VE), VE.stride(0), _p(stream), stream.shape[0], _p(bias),
+              bias.numel() // 32, _p(raw), ctypes.addressof(ptrs), ctypes.addressof(lds), ctypes.addressof(bp), E.shape[0], dt, _stream())
 
 
 def fmlp_proposal_train_fwd(E, stream, bias, raw_density, acts, bits):
-    """fmlp_proposal_fwd that also stores the four hidden-layer outputs (`acts`: [M,256] bf16 each) and their ReLU bit masks."""
+    """fmlp_proposal_fwd that also stores the four hidden-layer outputs (`acts`: [M,256] each, the stream's dtype) and their ReLU bit masks."""
     import ctypes
-    _chk2d(E, torch.bfloat16)
-    assert stream.dtype == torch.bfloat16 and stream.is_contiguous() and bias.dtype == torch.float32 and E.shape[1] >= 96
+    tdt, dt = _fmlp_dt(stream)
+    _chk2d(E, tdt)
+    assert bias.dtype == torch.float32 and E.shape[1] >= 96
     assert raw_density.dtype == torch.float32 and raw_density.is_contiguous() and raw_density.numel() == E.shape[0] and len(bits) == 4
-    ptrs, lds, bp = _act_arrays(acts, bits, E.shape[0], [256] * 4)
-    _lib.call("snerf_fmlp_proposal_train_fwd", _p(E), E.stride(0), _p(stream), stream.shape[0], _p(bias), bias.numel() // 32,
-              _p(raw_density), ctypes.addressof(ptrs), ctypes.addressof(lds), ctypes.addressof(bp), E.shape[0], _stream())
+    ptrs, lds, bp = _act_arrays(acts, bits, E.shape[0], [256] * 4, tdt)
+    _lib.call("snerf_fmlp_proposal_train_fwd_dt", _p(E), E.stride(0), _p(stream), stream.shape[0], _p(bias), bias.numel() // 32,
+              _p(raw_density), ctypes.addressof(ptrs), ctypes.addressof(lds), ctypes.addressof(bp), E.shape[0], dt, _stream())
 
 
 def fmlp_zip_fwd(Fb, D, stream, bias, raw_rgb, raw_d, x32=None):
@@ -397,18 +413,20 @@ def fchain_bwd(net, d_raw, stream, bits, dz, g_bias):
     """Fused data-gradient chain of a 256-wide network (csrc/fmlp.hip fchain_bwd_kernel), ONE launch instead of one GEMM per layer.
     CHAIN_CLASSIC: d_raw [M,4] fp32 -> dz = [d views_linears.0 (128), d feature_linear (256), d pts_linears.7 .. .0 (256)]; bits =
     masks of pts_linears.0..7 + views_linears.0.  CHAIN_PROPOSAL: d_raw [M] / [M,1] (d raw density) -> dz = [d layers.3 .. .0]; bits =
-    masks of layers.0..3.  The bias gradient of step i is added to g_bias[i] (not bit-reproducible: workgroup-level LDS atomics)."""
+    masks of layers.0..3.  The bias gradient of step i is added to g_bias[i] (not bit-reproducible: workgroup-level LDS atomics).
+    `stream` and every dz carry one 16-bit dtype, bf16 or fp16; in fp16 d_raw arrives already multiplied by the loss scale."""
     import ctypes
     classic = net == CHAIN_CLASSIC
     d_raw = _f32c(d_raw)
     M = d_raw.shape[0]
     widths = ([128] + [256] * 9) if classic else [256] * 4
-    assert d_raw.numel() == M * (4 if classic else 1) and stream.dtype == torch.bfloat16 and stream.is_contiguous()
+    tdt, dt = _fmlp_dt(stream)
+    assert d_raw.numel() == M * (4 if classic else 1)
     assert len(bits) == (9 if classic else 4) and len(dz) == len(widths) == len(g_bias)
     for i, b in enumerate(bits):
         assert b.dtype == torch.int32 and b.is_contiguous() and b.numel() >= mask_bits_words(M, 128 if i == 8 else 256)
     for y, w in zip(dz, widths):
-        assert y.dtype == torch.bfloat16 and y.dim() == 2 and y.stride(1) == 1 and y.shape[0] == M and y.shape[1] >= w
+        assert y.dtype == tdt and y.dim() == 2 and y.stride(1) == 1 and y.shape[0] == M and y.shape[1] >= w
     for gb, w in zip(g_bias, widths):
         assert gb.dtype == torch.float32 and gb.is_contiguous() and gb.numel() == w
     nws = _lib.query("snerf_fchain_bwd_ws_floats", net, M)
@@ -417,8 +435,8 @@ def fchain_bwd(net, d_raw, stream, bits, dz, g_bias):
     pz = (ctypes.c_void_p * len(dz))(*[y.data_ptr() for y in dz])
     pl = (ctypes.c_long * len(dz))(*[y.stride(0) for y in dz])
     pg = (ctypes.c_void_p * len(dz))(*[g.data_ptr() for g in g_bias])
-    _lib.call("snerf_fchain_bwd", net, _p(d_raw), _p(stream), stream.shape[0], ctypes.addressof(pb), ctypes.addressof(pz), ctypes.addressof(pl),
-              ctypes.addressof(pg), _p(ws), ws.numel(), M, _stream())
+    _lib.call("snerf_fchain_bwd_dt", net, _p(d_raw), _p(stream), stream.shape[0], ctypes.addressof(pb), ctypes.addressof(pz), ctypes.addressof(pl),
+              ctypes.addressof(pg), _p(ws), ws.numel(), M, dt, _stream())
 
 
 # --------------------------------------------------------------- encoders ----

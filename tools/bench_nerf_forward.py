@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """NeRF 8 x 256 inference on pre-embedded rows (NeRF.forward(x), as batchify(fn, netchunk) calls it) against run_network on the points,
-one MI355X, bf16: 65 536 rays x 192 samples.  Three routes, device events, a warm-up:
+one MI355X, bf16 (or --compute fp16): 65 536 rays x 192 samples.  Three routes, device events, a warm-up:
   run_network   the pts launch (positional encodings computed in the kernel, snerf_fmlp_classic_pts_fwd)
   fused_x       batchify(model, 65536)(x) through snerf_fmlp_classic_x_fwd (x = [Embedder(pts) | Embedder(viewdirs)], fp32)
   per_layer     the same calls with the fused kernel off (fused=False): cast_pad into operand buffers + the per-layer GEMMs
@@ -18,10 +18,11 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--route", default="all", choices=["all", "run_network", "fused_x", "per_layer"])
+    ap.add_argument("--compute", default="bf16", choices=["bf16", "fp16"])
     args = ap.parse_args()
     from snerf_amd import classic
     torch.manual_seed(0)
-    m = classic.NeRF(D=8, W=256, input_ch=63, input_ch_views=27, output_ch=4, skips=[4], use_viewdirs=True, compute="bf16", device="cuda")
+    m = classic.NeRF(D=8, W=256, input_ch=63, input_ch_views=27, output_ch=4, skips=[4], use_viewdirs=True, compute=args.compute, device="cuda")
     e, _ = classic.get_embedder(10, 0)
     ev, _ = classic.get_embedder(4, 0)
     N, S = args.rays, args.samples
@@ -41,7 +42,7 @@ def main():
             m.net.fused = True
     routes = {"run_network": lambda: classic.run_network(pts, vd, m, e, ev), "fused_x": lambda: batchify(m, args.netchunk)(x),
               "per_layer": per_layer}
-    res = {"rays": N, "samples": S, "rows": N * S, "netchunk": args.netchunk, "x_bytes": x.numel() * 4}
+    res = {"compute": args.compute, "rays": N, "samples": S, "rows": N * S, "netchunk": args.netchunk, "x_bytes": x.numel() * 4}
     with torch.no_grad():
         for name, fn in routes.items():
             if args.route not in ("all", name):

@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Race screen for the classic-network paths at a few-tile size (M = 768): the fused kernel (in-kernel embedding), the fused kernel
 behind the embedding kernel, and the per-layer GEMM chain must each give bit-identical outputs on repeated evaluation, with vendor
-kernels interleaved (different LDS / register garbage)."""
-import os, sys
+kernels interleaved (different LDS / register garbage).  --compute {bf16,fp16}: the network's compute mode (default bf16)."""
+import argparse, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from snerf_amd import classic
@@ -13,8 +13,11 @@ poison = ctypes.CDLL(_pz).lds_poison if os.path.exists(_pz) else None     # opti
 if poison is not None:
     poison.argtypes = [ctypes.c_uint, ctypes.c_void_p]
 
+ap = argparse.ArgumentParser()
+ap.add_argument("--compute", default="bf16", choices=["bf16", "fp16"])
+args = ap.parse_args()
 torch.manual_seed(0)
-net = classic.NeRF(D=8, W=256, input_ch=63, input_ch_views=27, output_ch=4, skips=[4], use_viewdirs=True, compute="bf16", device="cuda")
+net = classic.NeRF(D=8, W=256, input_ch=63, input_ch_views=27, output_ch=4, skips=[4], use_viewdirs=True, compute=args.compute, device="cuda")
 e, ev = classic.get_embedder(10, 0)[0], classic.get_embedder(4, 0)[0]
 big = torch.randn(4096, 4096, device="cuda").bfloat16()
 bad = 0
