@@ -639,6 +639,15 @@ int snerf_fcolour_fwd(const void* CB, long ldCB, const void* wstream, long n_fra
 long snerf_fcolour_bwd_ws_floats(long M);
 int snerf_fcolour_bwd(const float* d_raw_rgb, const void* wstream, long n_frags, void* const* bits, void* const* dC, const long* dC_ld,
                       void* dB, long dB_ld, float* const* g_bias, float* ws, long ws_floats, long M, void* stream);
+/* ... in either 16-bit flavour (library version >= 3; snerf_fcolour_fwd / snerf_fcolour_bwd forward here with SNERF_DT_BF16): dtype =
+ * SNERF_DT_BF16 or SNERF_DT_F16 = the type of CB, of the weight stream, of the stored activations and of dC / dB; d_raw_rgb is rounded
+ * to it (nearest even).  Nothing is scaled: under an fp16 loss scale d_raw_rgb arrives multiplied by it and the caller unscales what it
+ * reads.  raw_rgb, biases and the bias gradients (fixed-order fp32 sums of the unrounded accumulators, bit-reproducible) are fp32 either
+ * way.  Any other dtype: SNERF_ERR_ARG before anything touches a device, also for M = 0. */
+int snerf_fcolour_fwd_dt(const void* CB, long ldCB, const void* wstream, long n_frags, const float* bias, int n_blocks, float* raw_rgb,
+                         void* const* acts, const long* act_ld, void* const* bits, long M, int variant, int dtype, void* stream);
+int snerf_fcolour_bwd_dt(const float* d_raw_rgb, const void* wstream, long n_frags, void* const* bits, void* const* dC, const long* dC_ld,
+                         void* dB, long dB_ld, float* const* g_bias, float* ws, long ws_floats, long M, int dtype, void* stream);
 
 /* Data-gradient chains of the two 256-wide networks, fused (autograd of NeRF.forward, run_nerf_helpers.py:83-139, and of the mip
  * path's proposal MLP, s-nerf/model/models.py:237-262): d raw -> d pre-activation of every layer in ONE launch; replaces ten

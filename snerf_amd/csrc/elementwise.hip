@@ -589,7 +589,7 @@ extern "C" int snerf_gather_pack_pair(const float* flat, const int* idx, long n,
   return gather_pack_launch(flat, idx, n, dst, dtype, tiles, n_tiles, idx32, n32, dst32, stream);
 }
 
-extern "C" int snerf_version() { return 2; }   // 2: the `_dt` entries of the fused 256-wide networks (fmlp.hip)
+extern "C" int snerf_version() { return 3; }   // 2: the `_dt` entries of the fused 256-wide networks; 3: snerf_fcolour_fwd_dt / _bwd_dt (fmlp.hip)
 int g_snerf_last_hip_error = 0;
 extern "C" int snerf_last_hip_error() { return g_snerf_last_hip_error; }
 

@@ -670,7 +670,7 @@ __global__ __launch_bounds__(64 * FM_WAVES, 2) void fzip_fwd_kernel(FzipArgs a) 
 #define FC_BWD_FRAGS 336                            // 4 (rgb^T) + 32 + 32 + 256 (cond_layers.0^T, bottleneck columns) + 12 padding
 #define FC_BWD_COLS 1408                            // 3 x 128 + 1024 bias-gradient columns
 
-struct ColourFwdArgs {
+struct ColourFwdArgs {                // (the __bf16 pointers of both argument structs carry 16-bit patterns: fp16 ones in the F16 flavour)
   const __bf16* CB; long ldCB;        // [M, >= 1056] = [bottleneck 1024 | view encoding 27 | zeros]
   const char* wstream; const float* bias;
   float* raw_rgb;                     // [M, 3]
@@ -682,6 +682,10 @@ struct ColourFwdArgs {
 
 template <int F, int NB, int S, int... J, typename C>
 __device__ __forceinline__ void kmajor_mfma(C& c, f32x16 (&acc)[NB], const bf16x8& in, std::integer_sequence<int, J...>) {
+  if constexpr (C::f16) {
+    typedef _Float16 fm_f16x8 __attribute__((ext_vector_type(8)));
+    ((acc[J] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(fm_f16x8, next_frag<F + S * NB + J>(c)), __builtin_bit_cast(fm_f16x8, in), acc[J], 0, 0, 0)), ...);
+  } else
   ((acc[J] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(next_frag<F + S * NB + J>(c), in, acc[J], 0, 0, 0)), ...);
 }
 // The input fragments are fetched by inline-asm loads the compiler does not track, and waited for with counted s_waitcnt: with the
@@ -726,13 +730,15 @@ __device__ __forceinline__ void kmajor_prefetch(bf16x8 (&q)[QD], const __bf16* s
   (kmajor_fetch<NK, QD, K>(q, src), ...);
 }
 
-template <bool STORE, int QD>
+// F16: the fp16 flavour (compute="fp16") -- CB, the weight stream and the stored activations hold fp16 bit patterns, f16 MFMA, round-to-
+// nearest-even conversions; the input fetches, their wait counts and every LDS-DMA are the bf16 kernel's (16-bit operands either way)
+template <bool STORE, int QD, bool F16 = false>
 __global__ __launch_bounds__(64 * FM_WAVES, 2) void fcolour_fwd_kernel(ColourFwdArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int half = lane >> 5;
-  Ctx c;
+  CtxT<FM_RING, F16> c;
   ctx_start(c, smem, a.wstream, a.n_chunks, a.bias, a.n_blocks, tid, wave, lane);
   char* const slab = smem + FM_RING * FM_SLOT + FM_BIAS_MAX * 128 + wave * 4096;
 
@@ -747,13 +753,13 @@ __global__ __launch_bounds__(64 * FM_WAVES, 2) void fcolour_fwd_kernel(ColourFwd
     kmajor_seq<0, 4, FC_NK0, QD>(c, acc, qin, src, std::make_integer_sequence<int, FC_NK0>{});
     auto to = [&](int i) { return StoreTo{a.act[i], a.act_ld[i], a.bits[i], (long)tile * FM_TILE_ROWS + wave * 32, a.M, slab, lane, 2}; };
     bf16x8 p[8], q[8];
-    to_frags<true>(acc[0], p[0], p[1]);
+    to_frags<true, F16>(acc[0], p[0], p[1]);
     if constexpr (STORE) store_block<true, 0>(to(0), p[0], p[1]);
-    to_frags<true>(acc[1], p[2], p[3]);
+    to_frags<true, F16>(acc[1], p[2], p[3]);
     if constexpr (STORE) store_block<true, 1>(to(0), p[2], p[3]);
-    to_frags<true>(acc[2], p[4], p[5]);
+    to_frags<true, F16>(acc[2], p[4], p[5]);
     if constexpr (STORE) store_block<true, 2>(to(0), p[4], p[5]);
-    to_frags<true>(acc[3], p[6], p[7]);
+    to_frags<true, F16>(acc[3], p[6], p[7]);
     if constexpr (STORE) store_block<true, 3>(to(0), p[6], p[7]);
     constexpr int F1 = 4 * FC_NK0, F2 = F1 + 32, FR = F2 + 32;
     static_assert(FR + 8 == FC_FWD_FRAGS, "colour head: fragment count");
@@ -821,7 +827,7 @@ __device__ __forceinline__ void bwd_block(C& c, const bf16x8 (&in)[NK], const ch
   // register carries TWO blocks' partials across the tiles (44 registers would not fit beside the fragments)
   const float rs = rows_sum(acc, lane);
   cs[CS >> 1] += (((lane >> 4) & 1) == (CS & 1)) ? rs : 0.f;
-  to_frags<false>(acc, lo, hi);
+  to_frags<false, C::f16>(acc, lo, hi);
   store_block<false, J>(st, lo, hi);
 }
 template <int F, int NK, int CS0, int NB, typename C, int... J>
@@ -856,6 +862,9 @@ __device__ __forceinline__ void skip_frags(C& c, std::integer_sequence<int, I...
 #define FC_MASK_BYTES 6144
 #define FC_BWD_LDS (FC_BWD_RING * FM_SLOT + FM_WAVES * 4096 + FM_WAVES * FC_MASK_BYTES)
 
+// F16: the fp16 flavour -- transposed weight stream, d raw_rgb fragment and the stored dC / dB in fp16 (round to nearest even), f16 MFMA;
+// masks, bias-gradient partials and every DMA / wait count as in bf16.  d raw_rgb arrives already scaled (the loss scale is the caller's).
+template <bool F16 = false>
 __global__ __launch_bounds__(64 * FM_WAVES, 2) void fcolour_bwd_kernel(ColourBwdArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -885,7 +894,7 @@ __global__ __launch_bounds__(64 * FM_WAVES, 2) void fcolour_bwd_kernel(ColourBwd
     dma_narrow(row0, lane);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   }
-  CtxT<FC_BWD_RING> c;
+  CtxT<FC_BWD_RING, F16> c;
   ctx_start(c, smem, a.wstream, a.n_chunks, nullptr, 0, tid, wave, lane);
   const int sh = 8 * ((lane & 31) >> 3) + 4 * half;     // this lane's nibble inside a mask word
   float cs[FC_BWD_COLS / 64];                            // bias-gradient partials: register i = blocks 2 i (lanes with bit 4 clear) / 2 i + 1
@@ -910,7 +919,7 @@ __global__ __launch_bounds__(64 * FM_WAVES, 2) void fcolour_bwd_kernel(ColourBwd
       const float x0 = dp[0], x1 = dp[1], x2 = dp[2];
       typedef __attribute__((ext_vector_type(8))) float f32x8;
       const f32x8 v = {half == 0 ? x0 : 0.f, half == 0 ? x1 : 0.f, half == 0 ? x2 : 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-      g[0] = __builtin_convertvector(v, bf16x8);
+      g[0] = cvt_operand<F16>(v);
     }
     auto to = [&](int i) { return StoreTo{a.dC[i], a.dC_ld[i], nullptr, row0, a.M, slab, ln, 2}; };
     bf16x8 p[8], q[8];
@@ -1617,8 +1626,10 @@ static int fcolour_grid(int tiles) {
 // [bottleneck 1024 | view encoding 27 | zeros up to column 1056]; wstream / bias from mlp.fmlp_pack (cond_layers.0 k-major).
 // acts / act_ld / bits (HOST arrays of 3; all nullptr for inference): where the three hidden activations ([M, >= 128] bf16) and their
 // ReLU bit masks (snerf_linear_fwd's ACT_RELU_BITS layout for N = 128) are stored for the backward pass.
-extern "C" int snerf_fcolour_fwd(const void* CB, long ldCB, const void* wstream, long n_frags, const float* bias, int n_blocks, float* raw_rgb,
-                                 void* const* acts, const long* act_ld, void* const* bits, long M, int variant, void* stream) {
+// dtype (SNERF_DT_BF16 / SNERF_DT_F16): the type of CB, of the weight stream and of the stored activations.
+extern "C" int snerf_fcolour_fwd_dt(const void* CB, long ldCB, const void* wstream, long n_frags, const float* bias, int n_blocks, float* raw_rgb,
+                                    void* const* acts, const long* act_ld, void* const* bits, long M, int variant, int dtype, void* stream) {
+  if (!fmlp_dt_ok(dtype)) return SNERF_ERR_ARG;
   if (M <= 0) return SNERF_OK;
   if (CB == nullptr || wstream == nullptr || bias == nullptr || raw_rgb == nullptr || (((uintptr_t)CB) & 15) || (((uintptr_t)wstream) & 15) ||
       (ldCB % 8) != 0 || ldCB < 16 * FC_NK0 || n_frags != FC_FWD_FRAGS || n_blocks != FC_FWD_BLOCKS)
@@ -1641,19 +1652,36 @@ extern "C" int snerf_fcolour_fwd(const void* CB, long ldCB, const void* wstream,
     (void)hipFuncSetAttribute((const void*)fcolour_fwd_kernel<true, FC_QD>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     (void)hipFuncSetAttribute((const void*)fcolour_fwd_kernel<false, FC_QD_ALT>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     (void)hipFuncSetAttribute((const void*)fcolour_fwd_kernel<true, FC_QD_ALT>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    (void)hipFuncSetAttribute((const void*)(fcolour_fwd_kernel<false, FC_QD, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    (void)hipFuncSetAttribute((const void*)(fcolour_fwd_kernel<true, FC_QD, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    (void)hipFuncSetAttribute((const void*)(fcolour_fwd_kernel<false, FC_QD_ALT, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    (void)hipFuncSetAttribute((const void*)(fcolour_fwd_kernel<true, FC_QD_ALT, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     attr_set = true;
   }
   const int grid = fcolour_grid(a.tiles);
   const dim3 g(grid), b(64 * FM_WAVES);
   hipStream_t st = (hipStream_t)stream;
+  const bool f16 = dtype == SNERF_DT_F16;
   if (variant & 1) {                                    // tools/fcolour_probe.py: the alternative read-ahead depth
-    if (store) hipLaunchKernelGGL((fcolour_fwd_kernel<true, FC_QD_ALT>), g, b, lds, st, a);
-    else hipLaunchKernelGGL((fcolour_fwd_kernel<false, FC_QD_ALT>), g, b, lds, st, a);
+    if (f16) {
+      if (store) hipLaunchKernelGGL((fcolour_fwd_kernel<true, FC_QD_ALT, true>), g, b, lds, st, a);
+      else hipLaunchKernelGGL((fcolour_fwd_kernel<false, FC_QD_ALT, true>), g, b, lds, st, a);
+    } else {
+      if (store) hipLaunchKernelGGL((fcolour_fwd_kernel<true, FC_QD_ALT>), g, b, lds, st, a);
+      else hipLaunchKernelGGL((fcolour_fwd_kernel<false, FC_QD_ALT>), g, b, lds, st, a);
+    }
+  } else if (f16) {
+    if (store) hipLaunchKernelGGL((fcolour_fwd_kernel<true, FC_QD, true>), g, b, lds, st, a);
+    else hipLaunchKernelGGL((fcolour_fwd_kernel<false, FC_QD, true>), g, b, lds, st, a);
   } else {
     if (store) hipLaunchKernelGGL((fcolour_fwd_kernel<true, FC_QD>), g, b, lds, st, a);
     else hipLaunchKernelGGL((fcolour_fwd_kernel<false, FC_QD>), g, b, lds, st, a);
   }
   return snerf_check_launch();
+}
+extern "C" int snerf_fcolour_fwd(const void* CB, long ldCB, const void* wstream, long n_frags, const float* bias, int n_blocks, float* raw_rgb,
+                                 void* const* acts, const long* act_ld, void* const* bits, long M, int variant, void* stream) {
+  return snerf_fcolour_fwd_dt(CB, ldCB, wstream, n_frags, bias, n_blocks, raw_rgb, acts, act_ld, bits, M, variant, SNERF_DT_BF16, stream);
 }
 
 // workspace floats snerf_fcolour_bwd needs for M rows
@@ -1666,8 +1694,11 @@ extern "C" long snerf_fcolour_bwd_ws_floats(long M) {
 // bf16 each) and dB = d pre-activation of the bottleneck layer ([M, >= 1024] bf16); bits[0..3] = ReLU bit masks of cond_layers.2, .1,
 // .0 (N = 128) and of the bottleneck (N = 1024); wstream from mlp.fmlp_pack of the transposed weights; the bias gradients of the four
 // layers are ADDED to g_bias[0..3] (cond_layers.2, .1, .0: 128 floats, bottleneck: 1024) in a fixed order.  ws: snerf_fcolour_bwd_ws_floats(M).
-extern "C" int snerf_fcolour_bwd(const float* d_raw_rgb, const void* wstream, long n_frags, void* const* bits, void* const* dC, const long* dC_ld,
-                                 void* dB, long dB_ld, float* const* g_bias, float* ws, long ws_floats, long M, void* stream) {
+// dtype (SNERF_DT_BF16 / SNERF_DT_F16): the type of the weight stream and of the stored dC / dB.  d_raw_rgb arrives already scaled (the fp16
+// loss scale is the caller's business); the bias gradients are fp32 sums of the unrounded accumulators in either flavour.
+extern "C" int snerf_fcolour_bwd_dt(const float* d_raw_rgb, const void* wstream, long n_frags, void* const* bits, void* const* dC, const long* dC_ld,
+                                    void* dB, long dB_ld, float* const* g_bias, float* ws, long ws_floats, long M, int dtype, void* stream) {
+  if (!fmlp_dt_ok(dtype)) return SNERF_ERR_ARG;
   if (M <= 0) return SNERF_OK;
   if (d_raw_rgb == nullptr || wstream == nullptr || bits == nullptr || dC == nullptr || dC_ld == nullptr || dB == nullptr || g_bias == nullptr ||
       ws == nullptr || n_frags != FC_BWD_FRAGS || (((uintptr_t)wstream) & 15) || (((uintptr_t)dB) & 15) || (dB_ld % 8) != 0 || dB_ld < 1024 ||
@@ -1688,14 +1719,20 @@ extern "C" int snerf_fcolour_bwd(const float* d_raw_rgb, const void* wstream, lo
   const int lds = FC_BWD_LDS;
   static bool attr_set = false;
   if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)fcolour_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    (void)hipFuncSetAttribute((const void*)fcolour_bwd_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    (void)hipFuncSetAttribute((const void*)fcolour_bwd_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     attr_set = true;
   }
   const int grid = fcolour_grid(a.tiles);
-  hipLaunchKernelGGL(fcolour_bwd_kernel, dim3(grid), dim3(64 * FM_WAVES), lds, (hipStream_t)stream, a);
+  if (dtype == SNERF_DT_F16) hipLaunchKernelGGL(fcolour_bwd_kernel<true>, dim3(grid), dim3(64 * FM_WAVES), lds, (hipStream_t)stream, a);
+  else hipLaunchKernelGGL(fcolour_bwd_kernel<false>, dim3(grid), dim3(64 * FM_WAVES), lds, (hipStream_t)stream, a);
   hipLaunchKernelGGL(fcolour_colsum_fold_kernel, dim3(FC_BWD_COLS / 64), dim3(256), 0, (hipStream_t)stream, ws, grid, g_bias[0], g_bias[1],
                      g_bias[2], g_bias[3]);
   return snerf_check_launch();
+}
+extern "C" int snerf_fcolour_bwd(const float* d_raw_rgb, const void* wstream, long n_frags, void* const* bits, void* const* dC, const long* dC_ld,
+                                 void* dB, long dB_ld, float* const* g_bias, float* ws, long ws_floats, long M, void* stream) {
+  return snerf_fcolour_bwd_dt(d_raw_rgb, wstream, n_frags, bits, dC, dC_ld, dB, dB_ld, g_bias, ws, ws_floats, M, SNERF_DT_BF16, stream);
 }
 
 // ---- fused data-gradient chains of the 256-wide networks --------------------------------------------------------------------------

@@ -1114,8 +1114,8 @@ class MipNerfNet(_Net):
     # ---- fused colour head (csrc/fmlp.hip: fcolour_fwd_kernel / fcolour_bwd_kernel) ------------------------------------------------
     def colour_fused_ok(self):
         """cat([bottleneck, view encoding]) -> 3 x 128 -> rgb in ONE launch each way: the shipped configuration (hidden 1024, 27
-        view-encoding columns, rgb_layer 3 x 128, bf16)"""
-        return (getattr(self, "fused_colour", True) and self.dt == ops.BF16 and self.H == 1024 and self.cd == 27 and self.nc == 3 and self.cu == 128
+        view-encoding columns, rgb_layer 3 x 128) in bf16 or fp16; not inside the plain backward pass of the split modes"""
+        return (getattr(self, "fused_colour", True) and self.dt in (ops.BF16, ops.F16) and not self._in_plain_bwd and self.H == 1024 and self.cd == 27 and self.nc == 3 and self.cu == 128
                 and self.Cw >= 32)
 
     def _pack_colour_fwd(self):
@@ -1139,9 +1139,9 @@ class MipNerfNet(_Net):
         v = self.version_fn()
         if getattr(self, "_colour_version", None) != (v, train) and not (not train and getattr(self, "_colour_version", None) == (v, True)):
             with torch.no_grad():
-                self._cfwd = self._refresh_fused(self._pack_colour_fwd, "colour_fwd")
+                self._cfwd = self._refresh_fused(self._pack_colour_fwd, "colour_fwd", dtype=self.tdt)
                 if train:
-                    self._cbwd = self._refresh_fused(self._pack_colour_bwd, "colour_bwd")
+                    self._cbwd = self._refresh_fused(self._pack_colour_bwd, "colour_bwd", dtype=self.tdt)
             self._colour_version = (v, train)
 
     def alloc_inputs(self, M):

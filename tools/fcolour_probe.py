@@ -1,12 +1,18 @@
 #!/usr/bin/env python3
 """Fused colour head (snerf_fcolour_fwd / _bwd) against the per-layer GEMM launches it replaces, same box, same operands:
-inference forward, training forward (stores + bit masks), the data-gradient chain; the forward at both input read-ahead depths."""
-import os, sys
+inference forward, training forward (stores + bit masks), the data-gradient chain; the forward at both input read-ahead depths.
+--compute {bf16,fp16}: the 16-bit flavour of both routes."""
+import argparse, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from snerf_amd import ops
 from snerf_amd.mlp import MipNerfNet, ParamArena
 
+ap = argparse.ArgumentParser()
+ap.add_argument("--compute", choices=["bf16", "fp16"], default="bf16")
+args = ap.parse_args()
+DT = ops.F16 if args.compute == "fp16" else ops.BF16
+TDT = ops.torch_dtype(DT)
 M, H = 524288, 1024
 dev = torch.device("cuda")
 torch.manual_seed(0)
@@ -15,10 +21,10 @@ arena = ParamArena(shapes, dev)
 for n in arena.names:
     p = arena.p[n]
     (torch.nn.init.xavier_uniform_(p if p.dim() == 2 else p.view(1, -1)) if n.endswith("weight") else p.uniform_(-0.05, 0.05))
-net = MipNerfNet(arena, "mlp.", ops.BF16, H)
-x = torch.relu(torch.randn(M, H, device=dev)).bfloat16()
+net = MipNerfNet(arena, "mlp.", DT, H)
+x = torch.relu(torch.randn(M, H, device=dev)).to(TDT)
 CB = net.buf(M, H + net.Cw); CB.zero_()
-CB[:, H:H + 27] = (torch.rand(M, 27, device=dev) * 2 - 1).bfloat16()
+CB[:, H:H + 27] = (torch.rand(M, 27, device=dev) * 2 - 1).to(TDT)
 d_rgb = torch.randn(M, 3, device=dev) * 1e-3
 
 
@@ -59,7 +65,7 @@ for fused in (True, False):
         return ys, None
     t_inf = timeit(lambda: fwd(False))
     t_trn = timeit(lambda: fwd(True))
-    line = f"{'fused' if fused else 'per-layer'}: forward inference {t_inf:7.1f} us, training {t_trn:7.1f} us"
+    line = f"{args.compute} {'fused' if fused else 'per-layer'}: forward inference {t_inf:7.1f} us, training {t_trn:7.1f} us"
     if fused:
         line += f"; read-ahead 5 lines: inference {timeit(lambda: fwd(False, 1)):7.1f} us, training {timeit(lambda: fwd(True, 1)):7.1f} us"
     net._bits = {(CB.data_ptr(), M): bb}
