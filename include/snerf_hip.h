@@ -767,7 +767,9 @@ int snerf_adam_step_cnt(float* p, float* g, float* m, float* v, long n, float lr
                         int* step_dev, const float* lr_dev, float grad_scale, int zero_grad, int nonfinite, float grad_max_val,
                         const float* clip_coef, void* dropped, void* stream);
 /* torch.nn.utils.clip_grad_norm_ coefficient over a flat gradient arena: out[0] = min(1, max_norm / (|grad_scale| * ||g||_2 + 1e-6)),
- * out[1] = the norm.  ws: >= 1024 doubles of device scratch.  Fixed reduction order (deterministic). */
+ * out[1] = the norm.  ws: >= 1024 doubles of device scratch.  Fixed reduction order (deterministic).  A NaN in g gives out[0] = out[1]
+ * = NaN (torch's clamp(max=1) keeps the NaN too): snerf_adam_step_ex then sees NaN gradients everywhere and its `nonfinite` policy decides
+ * (1 / 2: the step applies an all-zero gradient; 0: parameters poisoned, as torch's are).  +-Inf in g gives out[0] = 0. */
 int snerf_grad_clip_coef(const float* g, long n, float grad_scale, float max_norm, void* ws, float* out, void* stream);
 /* The found-inf check of a dynamic loss scaler (torch.cuda.amp.GradScaler, which accelerate wraps around the reference's fp16 training:
  * s-nerfpp/zipnerf/train.py:44,215,331): *flag |= 1 when any of the n fp32 gradients is NaN or +-Inf.  The caller zeroes *flag

@@ -80,9 +80,13 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, float*
   }
 }
 
-static int adam_launch(float* p, float* g, float* m, float* v, long n, const AdamArgs& a, void* stream) {
+__global__ void adam_tick_kernel(int* step) { *step += 1; }
+
+// `tick`: *a.step_dev += 1 first (after the argument checks: a refused call leaves the counter alone)
+static int adam_launch(float* p, float* g, float* m, float* v, long n, const AdamArgs& a, void* stream, bool tick = false) {
   if (n <= 0) return SNERF_OK;
   if ((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 3) || a.nonfinite < 0 || a.nonfinite > 2) return SNERF_ERR_ARG;
+  if (tick) hipLaunchKernelGGL(adam_tick_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, (int*)a.step_dev);
   const bool vec = ((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0);
   const long units = vec ? (n >> 2) : n;
   int blocks = (int)((units + 255) / 256);
@@ -100,14 +104,11 @@ extern "C" int snerf_adam_step(float* p, float* g, float* m, float* v, long n, f
 
 // The same update with the step count in device memory (incremented here): nothing in the launch depends on host state, so a whole
 // training step can be captured in a hipGraph and replayed (trainer.MipTrainer.capture).
-__global__ void adam_tick_kernel(int* step) { *step += 1; }
-
 extern "C" int snerf_adam_step_dev(float* p, float* g, float* m, float* v, long n, float lr, float b1, float b2, float eps, int* step_dev,
                                    float grad_scale, int zero_grad, void* stream) {
   if (n <= 0) return SNERF_OK;
   if (step_dev == nullptr) return SNERF_ERR_ARG;
-  hipLaunchKernelGGL(adam_tick_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, step_dev);
-  return adam_launch(p, g, m, v, n, AdamArgs{lr, b1, b2, eps, grad_scale, 0.f, zero_grad, 0, step_dev, nullptr, nullptr, 0, nullptr}, stream);
+  return adam_launch(p, g, m, v, n, AdamArgs{lr, b1, b2, eps, grad_scale, 0.f, zero_grad, 0, step_dev, nullptr, nullptr, 0, nullptr}, stream, true);
 }
 
 extern "C" int snerf_adam_step_ex(float* p, float* g, float* m, float* v, long n, float lr, float b1, float b2, float eps, int step,
@@ -115,8 +116,8 @@ extern "C" int snerf_adam_step_ex(float* p, float* g, float* m, float* v, long n
                                   float grad_max_val, const float* clip_coef, void* stream) {
   if (n <= 0) return SNERF_OK;
   if (step_dev == nullptr && step < 1) return SNERF_ERR_ARG;
-  if (step_dev != nullptr) hipLaunchKernelGGL(adam_tick_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, step_dev);
-  return adam_launch(p, g, m, v, n, AdamArgs{lr, b1, b2, eps, grad_scale, grad_max_val, zero_grad, nonfinite, step_dev, lr_dev, clip_coef, step, nullptr}, stream);
+  return adam_launch(p, g, m, v, n, AdamArgs{lr, b1, b2, eps, grad_scale, grad_max_val, zero_grad, nonfinite, step_dev, lr_dev, clip_coef, step, nullptr}, stream,
+                     step_dev != nullptr);
 }
 
 // snerf_adam_step_ex + `dropped` (device uint64, never reset here): += the number of NaN / +-Inf gradient elements of this launch.  An
@@ -127,14 +128,14 @@ extern "C" int snerf_adam_step_cnt(float* p, float* g, float* m, float* v, long 
   if (n <= 0) return SNERF_OK;
   if (step_dev == nullptr && step < 1) return SNERF_ERR_ARG;
   if (dropped != nullptr && ((uintptr_t)dropped & 7)) return SNERF_ERR_ARG;
-  if (step_dev != nullptr) hipLaunchKernelGGL(adam_tick_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, step_dev);
   return adam_launch(p, g, m, v, n, AdamArgs{lr, b1, b2, eps, grad_scale, grad_max_val, zero_grad, nonfinite, step_dev, lr_dev, clip_coef, step,
-                                             (unsigned long long*)dropped}, stream);
+                                             (unsigned long long*)dropped}, stream, step_dev != nullptr);
 }
 
 // Global-norm clip coefficient of torch.nn.utils.clip_grad_norm_ (accelerator.clip_grad_norm_, train_utils.py:236-237):
-// coef = min(1, max_norm / (||grad_scale * g||_2 + 1e-6)) over the flat gradient arena, NaN-poisoned like torch's.  Two launches:
-// per-block partial sums of squares in a fixed order (deterministic), then one block folds them.
+// coef = min(1, max_norm / (||grad_scale * g||_2 + 1e-6)) over the flat gradient arena.  A NaN gradient makes the norm and the
+// coefficient NaN, as torch.clamp(max=1) keeps it (fminf would return 1, i.e. switch the clip off exactly then); an Inf gives 0.
+// Two launches: per-block partial sums of squares in a fixed order (deterministic), then one block folds them.
 __global__ __launch_bounds__(256) void sumsq_partial_kernel(const float* __restrict__ g, long n, double* __restrict__ part) {
   __shared__ double red[4];
   double acc = 0.0;
@@ -149,7 +150,8 @@ __global__ void clip_coef_kernel(const double* __restrict__ part, int nb, float 
   double s = 0.0;
   for (int i = 0; i < nb; ++i) s += part[i];
   const float norm = fabsf(grad_scale) * (float)sqrt(s);
-  out[0] = fminf(max_norm / (norm + 1e-6f), 1.f);
+  const float c = max_norm / (norm + 1e-6f);
+  out[0] = c > 1.f ? 1.f : c;                              // NaN stays NaN
   out[1] = norm;
 }
 

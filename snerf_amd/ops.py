@@ -808,7 +808,8 @@ def adam_step_dev(p, g, m, v, lr, b1, b2, eps, step_dev, grad_scale=1.0, zero_gr
 
 
 def grad_clip_coef(g, grad_scale, max_norm):
-    """-> fp32 [2] on the device = (min(1, max_norm / (|grad_scale| ||g|| + 1e-6)), the norm): clip_grad_norm_'s coefficient for adam_step."""
+    """-> fp32 [2] on the device = (min(1, max_norm / (|grad_scale| ||g|| + 1e-6)), the norm): clip_grad_norm_'s coefficient for adam_step.
+    A NaN in g gives (NaN, NaN) as in torch -- adam_step's `nonfinite` policy then decides about the whole step; +-Inf gives (0, Inf)."""
     _f32c(g)
     ws = torch.empty(1024, dtype=torch.float64, device=g.device)
     out = torch.empty(2, dtype=torch.float32, device=g.device)

@@ -323,7 +323,9 @@ def adam_step(p, g, m, v, lr, b1, b2, eps, step, grad_scale=1.0, zero_grad=True,
         step = int(step_dev)
     if lr_dev is not None:
         lr = float(lr_dev)
-    gg = g * grad_scale * (1.0 if clip_coef is None else float(clip_coef[0]))
+    # the kernel's order: ONE fp32 factor grad_scale * coef, then the product (a NaN coefficient poisons every element, as torch's does)
+    f32 = lambda x: torch.tensor(float(x), dtype=torch.float32)
+    gg = g * (f32(grad_scale) * (f32(1.0) if clip_coef is None else clip_coef[0].float().cpu())).to(g.device)
     if grad_max_val > 0:
         gg = torch.clamp(gg, -grad_max_val, grad_max_val)
     if nonfinite == "zero":
@@ -339,7 +341,8 @@ def adam_step(p, g, m, v, lr, b1, b2, eps, step, grad_scale=1.0, zero_grad=True,
 
 def grad_clip_coef(g, grad_scale, max_norm):
     norm = abs(grad_scale) * float(g.double().pow(2).sum().sqrt())
-    return torch.tensor([min(max_norm / (norm + 1e-6), 1.0), norm], dtype=torch.float32)
+    c = max_norm / (norm + 1e-6)
+    return torch.tensor([1.0 if c > 1.0 else c, norm], dtype=torch.float32)       # NaN in g: (NaN, NaN), torch's clamp(max=1) keeps it; Inf: (0, Inf)
 
 
 def nonfinite_flag(g, flag):
