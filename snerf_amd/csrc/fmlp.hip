@@ -1361,6 +1361,75 @@ __global__ __launch_bounds__(256) void fcolour_colsum_fold_kernel(const float* _
 // training forward stores; anything else is refused before a pointer is looked at
 static bool fmlp_dt_ok(int dtype) { return dtype == SNERF_DT_BF16 || dtype == SNERF_DT_F16; }
 
+// ---- what the entries below share -------------------------------------------------------------------------------------------------
+static int fmlp_tiles(long M) { return (int)((M + FM_TILE_ROWS - 1) / FM_TILE_ROWS); }
+
+// one persistent workgroup per tile, at most wg_per_cu per CU of the current device (asked once; 256 CUs when the query fails)
+static int fmlp_grid(int tiles, int wg_per_cu = 1) {
+  static int n_cu = 0;
+  if (n_cu == 0) {
+    int dev = 0;
+    hipDeviceProp_t prop;
+    n_cu = 256;
+    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
+      n_cu = prop.multiProcessorCount;
+  }
+  return tiles < n_cu * wg_per_cu ? tiles : n_cu * wg_per_cu;
+}
+
+// launches the bf16 (KB) or the fp16 (KH) instantiation of a kernel, whichever dtype names; the first launch of a pair raises the
+// dynamic-LDS limit of both (the static below exists once per pair)
+template <typename Args, void (*KB)(Args), void (*KH)(Args)>
+static void fmlp_launch_pair(int dtype, int grid, int lds, void* stream, const Args& a) {
+  static bool attr_set = false;
+  if (!attr_set) {
+    for (auto k : {KB, KH}) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    attr_set = true;
+  }
+  hipLaunchKernelGGL(dtype == SNERF_DT_F16 ? KH : KB, dim3(grid), dim3(64 * FM_WAVES), lds, (hipStream_t)stream, a);
+}
+
+// HOST arrays of n device pointers / row strides (elements) of stored 16-bit matrices: every pointer non-null and 16-byte aligned, every
+// stride a multiple of 8 and at least min_width[i] (nullptr: the entry asks for no minimum).  Copies them into the argument struct.
+static bool fmlp_mats_ok(void* const* p, const long* ld, int n, const int* min_width, __bf16** dst, long* dst_ld) {
+  if (p == nullptr || ld == nullptr) return false;
+  for (int i = 0; i < n; ++i) {
+    if (p[i] == nullptr || (((uintptr_t)p[i]) & 15) || (ld[i] % 8) != 0 || (min_width != nullptr && ld[i] < min_width[i])) return false;
+    dst[i] = (__bf16*)p[i]; dst_ld[i] = ld[i];
+  }
+  return true;
+}
+
+// HOST array of n ReLU bit-mask pointers: non-null and, where the entry asks for it, 16-byte aligned
+template <typename T>
+static bool fmlp_bits_ok(void* const* bits, int n, bool aligned, T** dst) {
+  if (bits == nullptr) return false;
+  for (int i = 0; i < n; ++i) {
+    if (bits[i] == nullptr || (aligned && (((uintptr_t)bits[i]) & 15))) return false;
+    dst[i] = (T*)bits[i];
+  }
+  return true;
+}
+
+// what the entries of the 256-wide networks fill alike
+static FmlpArgs fmlp_args(const void* wstream, long n_frags, const float* bias, int n_blocks, float* out, long M) {
+  FmlpArgs a{};
+  a.S = 1; a.wstream = (const char*)wstream; a.bias = bias; a.out = out;
+  a.M = M; a.tiles = fmlp_tiles(M); a.n_chunks = (int)(n_frags / FM_CHUNK); a.n_blocks = n_blocks;
+  return a;
+}
+
+// the columns of the chains' bias-gradient workspace: step i < n owns widths[i] of them and is folded into dst[i]
+static ChainFoldTab fchain_fold_tab(const int* widths, int n, float* const* dst) {
+  ChainFoldTab tab{};
+  int col = 0;
+  for (int i = 0; i < 10; ++i) {
+    tab.dst[i] = i < n ? dst[i] : nullptr; tab.first[i] = i < n ? col : 1 << 30;
+    if (i < n) col += widths[i];
+  }
+  return tab;
+}
+
 template <int NET, int IN, bool STORE = false>
 static int fmlp_launch(const FmlpArgs& a, int expect_frags, int expect_blocks, long n_frags, int dtype, void* stream) {
   if (!fmlp_dt_ok(dtype)) return SNERF_ERR_ARG;
@@ -1369,20 +1438,7 @@ static int fmlp_launch(const FmlpArgs& a, int expect_frags, int expect_blocks, l
   if (a.wstream == nullptr || a.bias == nullptr || a.out == nullptr || (((uintptr_t)a.wstream) & 15)) return SNERF_ERR_ARG;
   if (IN == FM_IN_ROWS && (a.E == nullptr || (a.ldE % 8) != 0 || (((uintptr_t)a.E) & 15))) return SNERF_ERR_ARG;
   constexpr int LDS = FM_RING * FM_SLOT + FM_BIAS_MAX * 128 + (STORE ? FM_WAVES * 4096 : 0);   // + the transposition slabs of the training stores
-  static bool attr_set = false;
-  static int n_cu = 256;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)fmlp_kernel<NET, IN, STORE>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    (void)hipFuncSetAttribute((const void*)fmlp_kernel<NET, IN, STORE, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
-      n_cu = prop.multiProcessorCount;
-    attr_set = true;
-  }
-  const int grid = a.tiles < n_cu * FM_WG_PER_CU ? a.tiles : n_cu * FM_WG_PER_CU;
-  if (dtype == SNERF_DT_F16) hipLaunchKernelGGL((fmlp_kernel<NET, IN, STORE, true>), dim3(grid), dim3(64 * FM_WAVES), LDS, (hipStream_t)stream, a);
-  else hipLaunchKernelGGL((fmlp_kernel<NET, IN, STORE>), dim3(grid), dim3(64 * FM_WAVES), LDS, (hipStream_t)stream, a);
+  fmlp_launch_pair<FmlpArgs, fmlp_kernel<NET, IN, STORE>, fmlp_kernel<NET, IN, STORE, true>>(dtype, fmlp_grid(a.tiles, FM_WG_PER_CU), LDS, stream, a);
   return snerf_check_launch();
 }
 
@@ -1391,9 +1447,8 @@ extern "C" int snerf_fmlp_classic_fwd_dt(const void* E, long ldE, const void* VE
   if (!fmlp_dt_ok(dtype)) return SNERF_ERR_ARG;
   if (M <= 0) return SNERF_OK;
   if (VE == nullptr || (ldVE % 8) != 0 || (((uintptr_t)VE) & 15) || (((uintptr_t)raw) & 15)) return SNERF_ERR_ARG;
-  FmlpArgs a{};
-  a.E = (const __bf16*)E; a.ldE = ldE; a.VE = (const __bf16*)VE; a.ldVE = ldVE; a.S = 1; a.wstream = (const char*)wstream; a.bias = bias; a.out = raw;
-  a.M = M; a.tiles = (int)((M + FM_TILE_ROWS - 1) / FM_TILE_ROWS); a.n_chunks = (int)(n_frags / FM_CHUNK); a.n_blocks = n_blocks;
+  FmlpArgs a = fmlp_args(wstream, n_frags, bias, n_blocks, raw, M);
+  a.E = (const __bf16*)E; a.ldE = ldE; a.VE = (const __bf16*)VE; a.ldVE = ldVE;
   return fmlp_launch<FMLP_CLASSIC, FM_IN_ROWS>(a, FMLP_CLASSIC_FRAGS, FMLP_CLASSIC_BLOCKS, n_frags, dtype, stream);
 }
 extern "C" int snerf_fmlp_classic_fwd(const void* E, long ldE, const void* VE, long ldVE, const void* wstream, long n_frags, const float* bias,
@@ -1411,19 +1466,10 @@ extern "C" int snerf_fmlp_classic_train_fwd_dt(const void* E, long ldE, const vo
                                                void* const* bits, long M, int dtype, void* stream) {
   if (!fmlp_dt_ok(dtype)) return SNERF_ERR_ARG;
   if (M <= 0) return SNERF_OK;
-  if (VE == nullptr || (ldVE % 8) != 0 || (((uintptr_t)VE) & 15) || (((uintptr_t)raw) & 15) || acts == nullptr || act_ld == nullptr || bits == nullptr)
-    return SNERF_ERR_ARG;
-  FmlpArgs a{};
-  a.E = (const __bf16*)E; a.ldE = ldE; a.VE = (const __bf16*)VE; a.ldVE = ldVE; a.S = 1; a.wstream = (const char*)wstream; a.bias = bias; a.out = raw;
-  a.M = M; a.tiles = (int)((M + FM_TILE_ROWS - 1) / FM_TILE_ROWS); a.n_chunks = (int)(n_frags / FM_CHUNK); a.n_blocks = n_blocks;
-  for (int i = 0; i < 10; ++i) {
-    if (acts[i] == nullptr || (((uintptr_t)acts[i]) & 15) || (act_ld[i] % 8) != 0) return SNERF_ERR_ARG;
-    a.act[i] = (__bf16*)acts[i]; a.act_ld[i] = act_ld[i];
-    if (i < 9) {
-      if (bits[i] == nullptr || (((uintptr_t)bits[i]) & 15)) return SNERF_ERR_ARG;
-      a.bits[i] = (unsigned*)bits[i];
-    }
-  }
+  if (VE == nullptr || (ldVE % 8) != 0 || (((uintptr_t)VE) & 15) || (((uintptr_t)raw) & 15)) return SNERF_ERR_ARG;
+  FmlpArgs a = fmlp_args(wstream, n_frags, bias, n_blocks, raw, M);
+  a.E = (const __bf16*)E; a.ldE = ldE; a.VE = (const __bf16*)VE; a.ldVE = ldVE;
+  if (!fmlp_mats_ok(acts, act_ld, 10, nullptr, a.act, a.act_ld) || !fmlp_bits_ok(bits, 9, true, a.bits)) return SNERF_ERR_ARG;
   return fmlp_launch<FMLP_CLASSIC, FM_IN_ROWS, true>(a, FMLP_CLASSIC_FRAGS, FMLP_CLASSIC_BLOCKS, n_frags, dtype, stream);
 }
 extern "C" int snerf_fmlp_classic_train_fwd(const void* E, long ldE, const void* VE, long ldVE, const void* wstream, long n_frags,
@@ -1438,9 +1484,8 @@ extern "C" int snerf_fmlp_classic_pts_fwd_dt(const float* pts, const float* view
   if (!fmlp_dt_ok(dtype)) return SNERF_ERR_ARG;
   if (M <= 0) return SNERF_OK;
   if (pts == nullptr || viewdirs == nullptr || S <= 0 || ldvd < 3 || (((uintptr_t)raw) & 15) || M >= (1L << 31)) return SNERF_ERR_ARG;
-  FmlpArgs a{};
-  a.pts = pts; a.viewdirs = viewdirs; a.ldvd = ldvd; a.S = S; a.wstream = (const char*)wstream; a.bias = bias; a.out = raw;
-  a.M = M; a.tiles = (int)((M + FM_TILE_ROWS - 1) / FM_TILE_ROWS); a.n_chunks = (int)(n_frags / FM_CHUNK); a.n_blocks = n_blocks;
+  FmlpArgs a = fmlp_args(wstream, n_frags, bias, n_blocks, raw, M);
+  a.pts = pts; a.viewdirs = viewdirs; a.ldvd = ldvd; a.S = S;
   return fmlp_launch<FMLP_CLASSIC, FM_IN_PTS>(a, FMLP_CLASSIC_FRAGS, FMLP_CLASSIC_BLOCKS, n_frags, dtype, stream);
 }
 extern "C" int snerf_fmlp_classic_pts_fwd(const float* pts, const float* viewdirs, long ldvd, int S, const void* wstream, long n_frags,
@@ -1450,20 +1495,17 @@ extern "C" int snerf_fmlp_classic_pts_fwd(const float* pts, const float* viewdir
 
 // the same network on pre-embedded fp32 rows x [M, ldX >= 90] (NeRF.forward(x)): columns [0, 63) = embedded points, [63, 90) =
 // embedded view directions, any row stride, 4-byte alignment.  Rounded to bf16 / fp16 in registers exactly as snerf_cast_pad does.
-static int fmlp_x_args(FmlpArgs& a, const float* x, long ldx, const void* wstream, long n_frags, const float* bias, int n_blocks, float* raw, long M) {
-  if (x == nullptr || ldx < 90 || (((uintptr_t)x) & 3) || raw == nullptr || (((uintptr_t)raw) & 15) || M >= (1L << 31)) return SNERF_ERR_ARG;
-  a.X = x; a.ldX = ldx; a.S = 1; a.wstream = (const char*)wstream; a.bias = bias; a.out = raw;
-  a.M = M; a.tiles = (int)((M + FM_TILE_ROWS - 1) / FM_TILE_ROWS); a.n_chunks = (int)(n_frags / FM_CHUNK); a.n_blocks = n_blocks;
-  return SNERF_OK;
+static bool fmlp_x_ok(const float* x, long ldx, const float* raw, long M) {
+  return x != nullptr && ldx >= 90 && !(((uintptr_t)x) & 3) && raw != nullptr && !(((uintptr_t)raw) & 15) && M < (1L << 31);
 }
 
 extern "C" int snerf_fmlp_classic_x_fwd_dt(const float* x, long ldx, const void* wstream, long n_frags, const float* bias, int n_blocks, float* raw,
                                            long M, int dtype, void* stream) {
   if (!fmlp_dt_ok(dtype)) return SNERF_ERR_ARG;
   if (M <= 0) return SNERF_OK;
-  FmlpArgs a{};
-  const int rc = fmlp_x_args(a, x, ldx, wstream, n_frags, bias, n_blocks, raw, M);
-  if (rc != SNERF_OK) return rc;
+  if (!fmlp_x_ok(x, ldx, raw, M)) return SNERF_ERR_ARG;
+  FmlpArgs a = fmlp_args(wstream, n_frags, bias, n_blocks, raw, M);
+  a.X = x; a.ldX = ldx;
   return fmlp_launch<FMLP_CLASSIC, FM_IN_X>(a, FMLP_CLASSIC_FRAGS, FMLP_CLASSIC_BLOCKS, n_frags, dtype, stream);
 }
 extern "C" int snerf_fmlp_classic_x_fwd(const float* x, long ldx, const void* wstream, long n_frags, const float* bias, int n_blocks, float* raw,
@@ -1479,22 +1521,13 @@ extern "C" int snerf_fmlp_classic_x_train_fwd_dt(const float* x, long ldx, const
                                                  void* const* bits, long M, int dtype, void* stream) {
   if (!fmlp_dt_ok(dtype)) return SNERF_ERR_ARG;
   if (M <= 0) return SNERF_OK;
-  if (xin == nullptr || xin_ld == nullptr || acts == nullptr || act_ld == nullptr || bits == nullptr) return SNERF_ERR_ARG;
-  FmlpArgs a{};
-  const int rc = fmlp_x_args(a, x, ldx, wstream, n_frags, bias, n_blocks, raw, M);
-  if (rc != SNERF_OK) return rc;
-  for (int i = 0; i < 3; ++i) {
-    if (xin[i] == nullptr || (((uintptr_t)xin[i]) & 15) || (xin_ld[i] % 8) != 0 || xin_ld[i] < (i == 2 ? 32 : 64)) return SNERF_ERR_ARG;
-    a.xin[i] = (__bf16*)xin[i]; a.xin_ld[i] = xin_ld[i];
-  }
-  for (int i = 0; i < 10; ++i) {
-    if (acts[i] == nullptr || (((uintptr_t)acts[i]) & 15) || (act_ld[i] % 8) != 0) return SNERF_ERR_ARG;
-    a.act[i] = (__bf16*)acts[i]; a.act_ld[i] = act_ld[i];
-    if (i < 9) {
-      if (bits[i] == nullptr || (((uintptr_t)bits[i]) & 15)) return SNERF_ERR_ARG;
-      a.bits[i] = (unsigned*)bits[i];
-    }
-  }
+  if (!fmlp_x_ok(x, ldx, raw, M)) return SNERF_ERR_ARG;
+  FmlpArgs a = fmlp_args(wstream, n_frags, bias, n_blocks, raw, M);
+  a.X = x; a.ldX = ldx;
+  const int xin_width[3] = {64, 64, 32};
+  if (!fmlp_mats_ok(xin, xin_ld, 3, xin_width, a.xin, a.xin_ld) || !fmlp_mats_ok(acts, act_ld, 10, nullptr, a.act, a.act_ld) ||
+      !fmlp_bits_ok(bits, 9, true, a.bits))
+    return SNERF_ERR_ARG;
   return fmlp_launch<FMLP_CLASSIC, FM_IN_X, true>(a, FMLP_CLASSIC_FRAGS, FMLP_CLASSIC_BLOCKS, n_frags, dtype, stream);
 }
 extern "C" int snerf_fmlp_classic_x_train_fwd(const float* x, long ldx, const void* wstream, long n_frags, const float* bias, int n_blocks,
@@ -1505,9 +1538,8 @@ extern "C" int snerf_fmlp_classic_x_train_fwd(const float* x, long ldx, const vo
 
 extern "C" int snerf_fmlp_proposal_fwd_dt(const void* E, long ldE, const void* wstream, long n_frags, const float* bias, int n_blocks,
                                           float* raw_density, long M, int dtype, void* stream) {
-  FmlpArgs a{};
-  a.E = (const __bf16*)E; a.ldE = ldE; a.S = 1; a.wstream = (const char*)wstream; a.bias = bias; a.out = raw_density;
-  a.M = M; a.tiles = (int)((M + FM_TILE_ROWS - 1) / FM_TILE_ROWS); a.n_chunks = (int)(n_frags / FM_CHUNK); a.n_blocks = n_blocks;
+  FmlpArgs a = fmlp_args(wstream, n_frags, bias, n_blocks, raw_density, M);
+  a.E = (const __bf16*)E; a.ldE = ldE;
   // 8 x 6 + 3 x 128 + 16 fragments; 32 + 1 blocks
   return fmlp_launch<FMLP_PROPOSAL, FM_IN_ROWS>(a, 448, 33, n_frags, dtype, stream);
 }
@@ -1522,15 +1554,9 @@ extern "C" int snerf_fmlp_proposal_train_fwd_dt(const void* E, long ldE, const v
                                                 int dtype, void* stream) {
   if (!fmlp_dt_ok(dtype)) return SNERF_ERR_ARG;
   if (M <= 0) return SNERF_OK;
-  if (acts == nullptr || act_ld == nullptr || bits == nullptr) return SNERF_ERR_ARG;
-  FmlpArgs a{};
-  a.E = (const __bf16*)E; a.ldE = ldE; a.S = 1; a.wstream = (const char*)wstream; a.bias = bias; a.out = raw_density;
-  a.M = M; a.tiles = (int)((M + FM_TILE_ROWS - 1) / FM_TILE_ROWS); a.n_chunks = (int)(n_frags / FM_CHUNK); a.n_blocks = n_blocks;
-  for (int i = 0; i < 4; ++i) {
-    if (acts[i] == nullptr || (((uintptr_t)acts[i]) & 15) || (act_ld[i] % 8) != 0) return SNERF_ERR_ARG;
-    if (bits[i] == nullptr) return SNERF_ERR_ARG;
-    a.act[i] = (__bf16*)acts[i]; a.act_ld[i] = act_ld[i]; a.bits[i] = (unsigned*)bits[i];
-  }
+  FmlpArgs a = fmlp_args(wstream, n_frags, bias, n_blocks, raw_density, M);
+  a.E = (const __bf16*)E; a.ldE = ldE;
+  if (!fmlp_mats_ok(acts, act_ld, 4, nullptr, a.act, a.act_ld) || !fmlp_bits_ok(bits, 4, false, a.bits)) return SNERF_ERR_ARG;
   return fmlp_launch<FMLP_PROPOSAL, FM_IN_ROWS, true>(a, 448, 33, n_frags, dtype, stream);
 }
 extern "C" int snerf_fmlp_proposal_train_fwd(const void* E, long ldE, const void* wstream, long n_frags, const float* bias, int n_blocks,
@@ -1548,24 +1574,11 @@ extern "C" int snerf_fmlp_zip_fwd(const void* F, long ldF, const void* D, long l
   if (x32 != nullptr && (ld_x < 32 || (ld_x % 4) || (((uintptr_t)x32) & 7))) return SNERF_ERR_ARG;
   if (F == nullptr || D == nullptr || wstream == nullptr || bias == nullptr || raw_rgb == nullptr || raw_d == nullptr || ldF < 64 || ldD < 16 || (ldF % 8) ||
       (ldD % 8) || (((uintptr_t)F) & 15) || (((uintptr_t)D) & 15) || ld_rgb < 3 || ld_d < 1 || M >= (1L << 31) || n_blocks != FZIP_BLOCKS ||
-      n_frags != ((FZIP_FRAGS + FM_CHUNK - 1) / FM_CHUNK) * FM_CHUNK || (dtype != SNERF_DT_BF16 && dtype != SNERF_DT_F16))
+      n_frags != ((FZIP_FRAGS + FM_CHUNK - 1) / FM_CHUNK) * FM_CHUNK || !fmlp_dt_ok(dtype))
     return SNERF_ERR_ARG;
-  FzipArgs a{(const __bf16*)F, ldF, (const __bf16*)D, ldD, (const char*)wstream, bias, raw_rgb, ld_rgb, raw_d, ld_d, (__bf16*)x32, ld_x, M, 0, (int)(n_frags / FM_CHUNK), n_blocks, {}, {}, {}};
-  a.tiles = (int)((M + FM_TILE_ROWS - 1) / FM_TILE_ROWS);
+  FzipArgs a{(const __bf16*)F, ldF, (const __bf16*)D, ldD, (const char*)wstream, bias, raw_rgb, ld_rgb, raw_d, ld_d, (__bf16*)x32, ld_x, M, fmlp_tiles(M), (int)(n_frags / FM_CHUNK), n_blocks, {}, {}, {}};
   const int lds = FM_RING * FM_SLOT + FM_BIAS_MAX * 128;
-  static bool attr = false;
-  static int n_cu = 256;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)fzip_fwd_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    (void)hipFuncSetAttribute((const void*)fzip_fwd_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) n_cu = prop.multiProcessorCount;
-    attr = true;
-  }
-  const int grid = a.tiles < n_cu * FM_WG_PER_CU ? a.tiles : n_cu * FM_WG_PER_CU;
-  if (dtype == SNERF_DT_F16) hipLaunchKernelGGL(fzip_fwd_kernel<true>, dim3(grid), dim3(64 * FM_WAVES), lds, (hipStream_t)stream, a);
-  else hipLaunchKernelGGL(fzip_fwd_kernel<false>, dim3(grid), dim3(64 * FM_WAVES), lds, (hipStream_t)stream, a);
+  fmlp_launch_pair<FzipArgs, fzip_fwd_kernel<false>, fzip_fwd_kernel<true>>(dtype, fmlp_grid(a.tiles, FM_WG_PER_CU), lds, stream, a);
   return snerf_check_launch();
 }
 
@@ -1578,49 +1591,23 @@ extern "C" int snerf_fmlp_zip_train_fwd(const void* F, long ldF, const void* D, 
                                         int n_blocks, float* raw_rgb, long ld_rgb, float* raw_d, long ld_d, void* const* acts, const long* act_ld,
                                         void* const* bits, long M, int dtype, void* stream) {
   if (M <= 0) return SNERF_OK;
-  if (F == nullptr || D == nullptr || wstream == nullptr || bias == nullptr || raw_rgb == nullptr || raw_d == nullptr || acts == nullptr || act_ld == nullptr ||
-      bits == nullptr || ldF < 64 || ldD < 16 || (ldF % 8) || (ldD % 8) || (((uintptr_t)F) & 15) || (((uintptr_t)D) & 15) || ld_rgb < 3 || ld_d < 1 ||
-      M >= (1L << 31) || n_blocks != FZIP_BLOCKS || n_frags != ((FZIP_FRAGS + FM_CHUNK - 1) / FM_CHUNK) * FM_CHUNK ||
-      (dtype != SNERF_DT_BF16 && dtype != SNERF_DT_F16))
+  if (F == nullptr || D == nullptr || wstream == nullptr || bias == nullptr || raw_rgb == nullptr || raw_d == nullptr || ldF < 64 || ldD < 16 ||
+      (ldF % 8) || (ldD % 8) || (((uintptr_t)F) & 15) || (((uintptr_t)D) & 15) || ld_rgb < 3 || ld_d < 1 || M >= (1L << 31) ||
+      n_blocks != FZIP_BLOCKS || n_frags != ((FZIP_FRAGS + FM_CHUNK - 1) / FM_CHUNK) * FM_CHUNK || !fmlp_dt_ok(dtype))
     return SNERF_ERR_ARG;
-  FzipArgs a{(const __bf16*)F, ldF, (const __bf16*)D, ldD, (const char*)wstream, bias, raw_rgb, ld_rgb, raw_d, ld_d, nullptr, 0, M, 0, (int)(n_frags / FM_CHUNK), n_blocks, {}, {}, {}};
-  for (int i = 0; i < 4; ++i) {
-    if (acts[i] == nullptr || (((uintptr_t)acts[i]) & 15) || (act_ld[i] % 8) != 0 || act_ld[i] < (i == 0 ? 64 : 256)) return SNERF_ERR_ARG;
-    a.act[i] = (__bf16*)acts[i]; a.act_ld[i] = act_ld[i];
-  }
-  for (int i = 0; i < 3; ++i) {
-    if (bits[i] == nullptr || (((uintptr_t)bits[i]) & 15)) return SNERF_ERR_ARG;
-    a.bits[i] = (unsigned*)bits[i];
-  }
-  a.tiles = (int)((M + FM_TILE_ROWS - 1) / FM_TILE_ROWS);
+  FzipArgs a{(const __bf16*)F, ldF, (const __bf16*)D, ldD, (const char*)wstream, bias, raw_rgb, ld_rgb, raw_d, ld_d, nullptr, 0, M, fmlp_tiles(M), (int)(n_frags / FM_CHUNK), n_blocks, {}, {}, {}};
+  const int act_width[4] = {64, 256, 256, 256};
+  if (!fmlp_mats_ok(acts, act_ld, 4, act_width, a.act, a.act_ld) || !fmlp_bits_ok(bits, 3, true, a.bits)) return SNERF_ERR_ARG;
   const int lds = FM_RING * FM_SLOT + FM_BIAS_MAX * 128 + FM_WAVES * 4096;
-  static bool attr = false;
-  static int n_cu = 256;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)fzip_fwd_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    (void)hipFuncSetAttribute((const void*)fzip_fwd_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) n_cu = prop.multiProcessorCount;
-    attr = true;
-  }
-  const int grid = a.tiles < n_cu * FM_WG_PER_CU ? a.tiles : n_cu * FM_WG_PER_CU;
-  if (dtype == SNERF_DT_F16) hipLaunchKernelGGL((fzip_fwd_kernel<true, true>), dim3(grid), dim3(64 * FM_WAVES), lds, (hipStream_t)stream, a);
-  else hipLaunchKernelGGL((fzip_fwd_kernel<false, true>), dim3(grid), dim3(64 * FM_WAVES), lds, (hipStream_t)stream, a);
+  fmlp_launch_pair<FzipArgs, fzip_fwd_kernel<false, true>, fzip_fwd_kernel<true, true>>(dtype, fmlp_grid(a.tiles, FM_WG_PER_CU), lds, stream, a);
   return snerf_check_launch();
 }
 
-static int fcolour_grid(int tiles) {
-  static int n_cu = 0;
-  if (n_cu == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    n_cu = 256;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
-      n_cu = prop.multiProcessorCount;
-  }
-  return tiles < n_cu ? tiles : n_cu;
-}
+// The code object lists kernels in the order the host code first names them.  Naming the bf16 flavours here keeps them in front of the
+// fp16 ones, where they were before the launches went through fmlp_launch_pair (whose pairs would interleave the two): the device code
+// stays byte for byte what it was.  fchain_kernel_order below does the same for the chains.
+static const void* const fcolour_kernel_order[] = {(const void*)fcolour_fwd_kernel<false, FC_QD>, (const void*)fcolour_fwd_kernel<true, FC_QD>,
+                                                   (const void*)fcolour_fwd_kernel<false, FC_QD_ALT>, (const void*)fcolour_fwd_kernel<true, FC_QD_ALT>};
 
 // raw_rgb [M,3] fp32 = rgb_layer(cond_layers.2(cond_layers.1(cond_layers.0(CB[:, :1051])))) (models.py:283-296).  CB [M, ldCB] bf16 =
 // [bottleneck 1024 | view encoding 27 | zeros up to column 1056]; wstream / bias from mlp.fmlp_pack (cond_layers.0 k-major).
@@ -1636,46 +1623,17 @@ extern "C" int snerf_fcolour_fwd_dt(const void* CB, long ldCB, const void* wstre
     return SNERF_ERR_ARG;
   ColourFwdArgs a{};
   a.CB = (const __bf16*)CB; a.ldCB = ldCB; a.wstream = (const char*)wstream; a.bias = bias; a.raw_rgb = raw_rgb; a.M = M;
-  a.tiles = (int)((M + FM_TILE_ROWS - 1) / FM_TILE_ROWS); a.n_chunks = (int)(n_frags / FM_CHUNK); a.n_blocks = n_blocks;
+  a.tiles = fmlp_tiles(M); a.n_chunks = (int)(n_frags / FM_CHUNK); a.n_blocks = n_blocks;
   const bool store = acts != nullptr;
-  if (store) {
-    if (act_ld == nullptr || bits == nullptr) return SNERF_ERR_ARG;
-    for (int i = 0; i < 3; ++i) {
-      if (acts[i] == nullptr || bits[i] == nullptr || (((uintptr_t)acts[i]) & 15) || (act_ld[i] % 8) != 0 || act_ld[i] < 128) return SNERF_ERR_ARG;
-      a.act[i] = (__bf16*)acts[i]; a.act_ld[i] = act_ld[i]; a.bits[i] = (unsigned*)bits[i];
-    }
-  }
-  const int lds = FM_RING * FM_SLOT + FM_BIAS_MAX * 128 + FM_WAVES * 4096;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)fcolour_fwd_kernel<false, FC_QD>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    (void)hipFuncSetAttribute((const void*)fcolour_fwd_kernel<true, FC_QD>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    (void)hipFuncSetAttribute((const void*)fcolour_fwd_kernel<false, FC_QD_ALT>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    (void)hipFuncSetAttribute((const void*)fcolour_fwd_kernel<true, FC_QD_ALT>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    (void)hipFuncSetAttribute((const void*)(fcolour_fwd_kernel<false, FC_QD, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    (void)hipFuncSetAttribute((const void*)(fcolour_fwd_kernel<true, FC_QD, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    (void)hipFuncSetAttribute((const void*)(fcolour_fwd_kernel<false, FC_QD_ALT, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    (void)hipFuncSetAttribute((const void*)(fcolour_fwd_kernel<true, FC_QD_ALT, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    attr_set = true;
-  }
-  const int grid = fcolour_grid(a.tiles);
-  const dim3 g(grid), b(64 * FM_WAVES);
-  hipStream_t st = (hipStream_t)stream;
-  const bool f16 = dtype == SNERF_DT_F16;
-  if (variant & 1) {                                    // tools/fcolour_probe.py: the alternative read-ahead depth
-    if (f16) {
-      if (store) hipLaunchKernelGGL((fcolour_fwd_kernel<true, FC_QD_ALT, true>), g, b, lds, st, a);
-      else hipLaunchKernelGGL((fcolour_fwd_kernel<false, FC_QD_ALT, true>), g, b, lds, st, a);
-    } else {
-      if (store) hipLaunchKernelGGL((fcolour_fwd_kernel<true, FC_QD_ALT>), g, b, lds, st, a);
-      else hipLaunchKernelGGL((fcolour_fwd_kernel<false, FC_QD_ALT>), g, b, lds, st, a);
-    }
-  } else if (f16) {
-    if (store) hipLaunchKernelGGL((fcolour_fwd_kernel<true, FC_QD, true>), g, b, lds, st, a);
-    else hipLaunchKernelGGL((fcolour_fwd_kernel<false, FC_QD, true>), g, b, lds, st, a);
-  } else {
-    if (store) hipLaunchKernelGGL((fcolour_fwd_kernel<true, FC_QD>), g, b, lds, st, a);
-    else hipLaunchKernelGGL((fcolour_fwd_kernel<false, FC_QD>), g, b, lds, st, a);
+  const int act_width[3] = {128, 128, 128};
+  if (store && (!fmlp_mats_ok(acts, act_ld, 3, act_width, a.act, a.act_ld) || !fmlp_bits_ok(bits, 3, false, a.bits))) return SNERF_ERR_ARG;
+  const int lds = FM_RING * FM_SLOT + FM_BIAS_MAX * 128 + FM_WAVES * 4096, grid = fmlp_grid(a.tiles);
+  if (!(variant & 1)) {
+    if (!store) fmlp_launch_pair<ColourFwdArgs, fcolour_fwd_kernel<false, FC_QD>, fcolour_fwd_kernel<false, FC_QD, true>>(dtype, grid, lds, stream, a);
+    else fmlp_launch_pair<ColourFwdArgs, fcolour_fwd_kernel<true, FC_QD>, fcolour_fwd_kernel<true, FC_QD, true>>(dtype, grid, lds, stream, a);
+  } else {                                              // tools/fcolour_probe.py: the alternative read-ahead depth
+    if (!store) fmlp_launch_pair<ColourFwdArgs, fcolour_fwd_kernel<false, FC_QD_ALT>, fcolour_fwd_kernel<false, FC_QD_ALT, true>>(dtype, grid, lds, stream, a);
+    else fmlp_launch_pair<ColourFwdArgs, fcolour_fwd_kernel<true, FC_QD_ALT>, fcolour_fwd_kernel<true, FC_QD_ALT, true>>(dtype, grid, lds, stream, a);
   }
   return snerf_check_launch();
 }
@@ -1687,7 +1645,7 @@ extern "C" int snerf_fcolour_fwd(const void* CB, long ldCB, const void* wstream,
 // workspace floats snerf_fcolour_bwd needs for M rows
 extern "C" long snerf_fcolour_bwd_ws_floats(long M) {
   if (M <= 0) return 0;
-  return (long)fcolour_grid((int)((M + FM_TILE_ROWS - 1) / FM_TILE_ROWS)) * FC_BWD_COLS;
+  return (long)fmlp_grid(fmlp_tiles(M)) * FC_BWD_COLS;
 }
 
 // Data-gradient chain of the colour head: d_raw_rgb [M,3] fp32 -> dC[0..2] = d pre-activation of cond_layers.2, .1, .0 ([M, >= 128]
@@ -1700,32 +1658,19 @@ extern "C" int snerf_fcolour_bwd_dt(const float* d_raw_rgb, const void* wstream,
                                     void* dB, long dB_ld, float* const* g_bias, float* ws, long ws_floats, long M, int dtype, void* stream) {
   if (!fmlp_dt_ok(dtype)) return SNERF_ERR_ARG;
   if (M <= 0) return SNERF_OK;
-  if (d_raw_rgb == nullptr || wstream == nullptr || bits == nullptr || dC == nullptr || dC_ld == nullptr || dB == nullptr || g_bias == nullptr ||
-      ws == nullptr || n_frags != FC_BWD_FRAGS || (((uintptr_t)wstream) & 15) || (((uintptr_t)dB) & 15) || (dB_ld % 8) != 0 || dB_ld < 1024 ||
-      ws_floats < snerf_fcolour_bwd_ws_floats(M))
+  if (d_raw_rgb == nullptr || wstream == nullptr || dB == nullptr || g_bias == nullptr || ws == nullptr || n_frags != FC_BWD_FRAGS ||
+      (((uintptr_t)wstream) & 15) || (((uintptr_t)dB) & 15) || (dB_ld % 8) != 0 || dB_ld < 1024 || ws_floats < snerf_fcolour_bwd_ws_floats(M))
     return SNERF_ERR_ARG;
   ColourBwdArgs a{};
   a.d_rgb = d_raw_rgb; a.wstream = (const char*)wstream; a.dB = (__bf16*)dB; a.dB_ld = dB_ld; a.colsum_ws = ws; a.M = M;
-  a.tiles = (int)((M + FM_TILE_ROWS - 1) / FM_TILE_ROWS); a.n_chunks = (int)(n_frags / FM_CHUNK);
-  for (int i = 0; i < 4; ++i) {
-    if (bits[i] == nullptr || (((uintptr_t)bits[i]) & 15) || g_bias[i] == nullptr) return SNERF_ERR_ARG;
-    a.bits[i] = (const unsigned*)bits[i];
-  }
-  for (int i = 0; i < 3; ++i) {
-    if (dC[i] == nullptr || (((uintptr_t)dC[i]) & 15) || (dC_ld[i] % 8) != 0 || dC_ld[i] < 128) return SNERF_ERR_ARG;
-    a.dC[i] = (__bf16*)dC[i]; a.dC_ld[i] = dC_ld[i];
-  }
+  a.tiles = fmlp_tiles(M); a.n_chunks = (int)(n_frags / FM_CHUNK);
+  const int dC_width[3] = {128, 128, 128};
+  if (!fmlp_bits_ok(bits, 4, true, a.bits) || !fmlp_mats_ok(dC, dC_ld, 3, dC_width, a.dC, a.dC_ld)) return SNERF_ERR_ARG;
+  for (int i = 0; i < 4; ++i)
+    if (g_bias[i] == nullptr) return SNERF_ERR_ARG;
   if (M * 12 >= (1L << 31) || (((uintptr_t)d_raw_rgb) & 15)) return SNERF_ERR_ARG;      // d raw_rgb goes through a 32-bit buffer descriptor
-  const int lds = FC_BWD_LDS;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)fcolour_bwd_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    (void)hipFuncSetAttribute((const void*)fcolour_bwd_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    attr_set = true;
-  }
-  const int grid = fcolour_grid(a.tiles);
-  if (dtype == SNERF_DT_F16) hipLaunchKernelGGL(fcolour_bwd_kernel<true>, dim3(grid), dim3(64 * FM_WAVES), lds, (hipStream_t)stream, a);
-  else hipLaunchKernelGGL(fcolour_bwd_kernel<false>, dim3(grid), dim3(64 * FM_WAVES), lds, (hipStream_t)stream, a);
+  const int grid = fmlp_grid(a.tiles);
+  fmlp_launch_pair<ColourBwdArgs, fcolour_bwd_kernel<false>, fcolour_bwd_kernel<true>>(dtype, grid, FC_BWD_LDS, stream, a);
   hipLaunchKernelGGL(fcolour_colsum_fold_kernel, dim3(FC_BWD_COLS / 64), dim3(256), 0, (hipStream_t)stream, ws, grid, g_bias[0], g_bias[1],
                      g_bias[2], g_bias[3]);
   return snerf_check_launch();
@@ -1740,8 +1685,10 @@ extern "C" int snerf_fcolour_bwd(const float* d_raw_rgb, const void* wstream, lo
 extern "C" long snerf_fchain_bwd_ws_floats(int net, long M) {
   if (M <= 0 || (net != FMLP_CLASSIC && net != FMLP_PROPOSAL)) return 0;
   const int ncols = net == FMLP_CLASSIC ? FCH_CLASSIC_COLS : FCH_PROPOSAL_COLS;
-  return (long)fcolour_grid((int)((M + FM_TILE_ROWS - 1) / FM_TILE_ROWS)) * ncols + 64;       // + the fold's two small tables
+  return (long)fmlp_grid(fmlp_tiles(M)) * ncols + 64;       // + the fold's two small tables
 }
+
+static const void* const fchain_kernel_order[] = {(const void*)fchain_bwd_kernel<FMLP_CLASSIC>, (const void*)fchain_bwd_kernel<FMLP_PROPOSAL>};
 
 // net 0 (classic NeRF, run_nerf_helpers.py:83-139): d_raw [M,4] fp32 (d rgb, d alpha) -> dz[0] = d pre-activation of views_linears.0
 // ([M, >= 128] bf16), dz[1] = d feature_linear output ([M, >= 256]), dz[2..9] = d pre-activation of pts_linears.7 .. .0; bits[0..7] =
@@ -1759,49 +1706,21 @@ extern "C" int snerf_fchain_bwd_dt(int net, const float* d_raw, const void* wstr
   if (net != FMLP_CLASSIC && net != FMLP_PROPOSAL) return SNERF_ERR_ARG;
   const bool classic = net == FMLP_CLASSIC;
   const int n_steps = classic ? 10 : 4, n_bits = classic ? 9 : 4, ncols = classic ? FCH_CLASSIC_COLS : FCH_PROPOSAL_COLS, dc = classic ? 4 : 1;
-  if (d_raw == nullptr || wstream == nullptr || bits == nullptr || dz == nullptr || dz_ld == nullptr || g_bias == nullptr || ws == nullptr ||
-      n_frags != (classic ? FCH_CLASSIC_FRAGS : FCH_PROPOSAL_FRAGS) || (((uintptr_t)wstream) & 15) || (((uintptr_t)d_raw) & 15) ||
-      ws_floats < snerf_fchain_bwd_ws_floats(net, M) || M * dc * 4 >= (1L << 31))
+  const int widths[10] = {classic ? 128 : 256, 256, 256, 256, 256, 256, 256, 256, 256, 256};
+  if (d_raw == nullptr || wstream == nullptr || g_bias == nullptr || ws == nullptr || n_frags != (classic ? FCH_CLASSIC_FRAGS : FCH_PROPOSAL_FRAGS) ||
+      (((uintptr_t)wstream) & 15) || (((uintptr_t)d_raw) & 15) || ws_floats < snerf_fchain_bwd_ws_floats(net, M) || M * dc * 4 >= (1L << 31))
     return SNERF_ERR_ARG;
   ChainArgs a{};
   a.d_raw = d_raw; a.d_cols = dc; a.wstream = (const char*)wstream; a.colsum_ws = ws; a.M = M; a.n_cols = ncols;
-  a.tiles = (int)((M + FM_TILE_ROWS - 1) / FM_TILE_ROWS); a.n_chunks = (int)(n_frags / FM_CHUNK);
-  for (int i = 0; i < n_bits; ++i) {
-    if (bits[i] == nullptr || (((uintptr_t)bits[i]) & 15)) return SNERF_ERR_ARG;
-    a.bits[i] = (const unsigned*)bits[i];
-  }
-  ChainFoldTab tab{};
-  int col = 0;
-  for (int i = 0; i < 10; ++i) {
-    if (i < n_steps) {
-      const int width = (classic && i == 0) ? 128 : 256;
-      if (dz[i] == nullptr || (((uintptr_t)dz[i]) & 15) || (dz_ld[i] % 8) != 0 || dz_ld[i] < width || g_bias[i] == nullptr) return SNERF_ERR_ARG;
-      a.dz[i] = (__bf16*)dz[i]; a.dz_ld[i] = dz_ld[i];
-      tab.dst[i] = g_bias[i]; tab.first[i] = col; col += width;
-    } else {
-      tab.dst[i] = nullptr; tab.first[i] = 1 << 30;
-    }
-  }
-  const int grid = fcolour_grid(a.tiles);
-  const int lds = FCH_LDS(ncols);
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)fchain_bwd_kernel<FMLP_CLASSIC>, hipFuncAttributeMaxDynamicSharedMemorySize, FCH_LDS(FCH_CLASSIC_COLS));
-    (void)hipFuncSetAttribute((const void*)fchain_bwd_kernel<FMLP_PROPOSAL>, hipFuncAttributeMaxDynamicSharedMemorySize, FCH_LDS(FCH_PROPOSAL_COLS));
-    (void)hipFuncSetAttribute((const void*)(fchain_bwd_kernel<FMLP_CLASSIC, true>), hipFuncAttributeMaxDynamicSharedMemorySize, FCH_LDS(FCH_CLASSIC_COLS));
-    (void)hipFuncSetAttribute((const void*)(fchain_bwd_kernel<FMLP_PROPOSAL, true>), hipFuncAttributeMaxDynamicSharedMemorySize, FCH_LDS(FCH_PROPOSAL_COLS));
-    attr_set = true;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  const dim3 g(grid), b(64 * FM_WAVES);
-  if (dtype == SNERF_DT_F16) {
-    if (classic) hipLaunchKernelGGL((fchain_bwd_kernel<FMLP_CLASSIC, true>), g, b, lds, st, a);
-    else hipLaunchKernelGGL((fchain_bwd_kernel<FMLP_PROPOSAL, true>), g, b, lds, st, a);
-  } else {
-    if (classic) hipLaunchKernelGGL(fchain_bwd_kernel<FMLP_CLASSIC>, g, b, lds, st, a);
-    else hipLaunchKernelGGL(fchain_bwd_kernel<FMLP_PROPOSAL>, g, b, lds, st, a);
-  }
-  hipLaunchKernelGGL(fchain_colsum_fold_kernel, dim3((ncols + 63) / 64), dim3(256), 0, st, (const float*)ws, grid, ncols, tab);
+  a.tiles = fmlp_tiles(M); a.n_chunks = (int)(n_frags / FM_CHUNK);
+  if (!fmlp_bits_ok(bits, n_bits, true, a.bits) || !fmlp_mats_ok(dz, dz_ld, n_steps, widths, a.dz, a.dz_ld)) return SNERF_ERR_ARG;
+  for (int i = 0; i < n_steps; ++i)
+    if (g_bias[i] == nullptr) return SNERF_ERR_ARG;
+  const ChainFoldTab tab = fchain_fold_tab(widths, n_steps, g_bias);
+  const int grid = fmlp_grid(a.tiles), lds = FCH_LDS(ncols);
+  if (classic) fmlp_launch_pair<ChainArgs, fchain_bwd_kernel<FMLP_CLASSIC>, fchain_bwd_kernel<FMLP_CLASSIC, true>>(dtype, grid, lds, stream, a);
+  else fmlp_launch_pair<ChainArgs, fchain_bwd_kernel<FMLP_PROPOSAL>, fchain_bwd_kernel<FMLP_PROPOSAL, true>>(dtype, grid, lds, stream, a);
+  hipLaunchKernelGGL(fchain_colsum_fold_kernel, dim3((ncols + 63) / 64), dim3(256), 0, (hipStream_t)stream, (const float*)ws, grid, ncols, tab);
   return snerf_check_launch();
 }
 extern "C" int snerf_fchain_bwd(int net, const float* d_raw, const void* wstream, long n_frags, void* const* bits, void* const* dz, const long* dz_ld,
@@ -1816,47 +1735,29 @@ extern "C" int snerf_fchain_bwd(int net, const float* d_raw, const void* wstream
 // not bit-reproducible; the deterministic mode keeps the per-layer kernels).  wstream: ZipNerfNet._pack_fused_chain (448 fragments).
 extern "C" long snerf_fmlp_zip_chain_ws_floats(long M) {
   if (M <= 0) return 0;
-  return (long)fcolour_grid((int)((M + FM_TILE_ROWS - 1) / FM_TILE_ROWS)) * FZCH_COLS + 64;
+  return (long)fmlp_grid(fmlp_tiles(M)) * FZCH_COLS + 64;
 }
 extern "C" int snerf_fmlp_zip_chain_bwd(const float* d_rgb, long ld_rgb, const float* d_den, long ld_den, int den_cols, const void* wstream, long n_frags,
                                         void* const* bits, void* const* dz, const long* dz_ld, float* const* g_bias, float* ws, long ws_floats, long M,
                                         int dtype, void* stream) {
   if (M <= 0) return SNERF_OK;
-  if (d_rgb == nullptr || d_den == nullptr || wstream == nullptr || bits == nullptr || dz == nullptr || dz_ld == nullptr || g_bias == nullptr || ws == nullptr ||
-      ld_rgb < 3 || den_cols < 1 || den_cols > 32 || ld_den < den_cols || n_frags != FZCH_FRAGS || (((uintptr_t)wstream) & 15) ||
-      ws_floats < snerf_fmlp_zip_chain_ws_floats(M) || M >= (1L << 31) || (dtype != SNERF_DT_BF16 && dtype != SNERF_DT_F16))
+  if (d_rgb == nullptr || d_den == nullptr || wstream == nullptr || g_bias == nullptr || ws == nullptr || ld_rgb < 3 || den_cols < 1 || den_cols > 32 ||
+      ld_den < den_cols || n_frags != FZCH_FRAGS || (((uintptr_t)wstream) & 15) || ws_floats < snerf_fmlp_zip_chain_ws_floats(M) || M >= (1L << 31) ||
+      !fmlp_dt_ok(dtype))
     return SNERF_ERR_ARG;
   ZipChainArgs a{};
   a.d_rgb = d_rgb; a.ld_rgb = ld_rgb; a.d_den = d_den; a.ld_den = ld_den; a.den_cols = den_cols; a.wstream = (const char*)wstream; a.colsum_ws = ws; a.M = M;
-  a.tiles = (int)((M + FM_TILE_ROWS - 1) / FM_TILE_ROWS); a.n_chunks = (int)(n_frags / FM_CHUNK);
-  for (int i = 0; i < 3; ++i) {
-    if (bits[i] == nullptr || (((uintptr_t)bits[i]) & 15)) return SNERF_ERR_ARG;
-    a.bits[i] = (const unsigned*)bits[i];
-  }
-  const int grid = fcolour_grid(a.tiles);
-  ChainFoldTab tab{};
+  a.tiles = fmlp_tiles(M); a.n_chunks = (int)(n_frags / FM_CHUNK);
   const int widths[5] = {256, 256, 256, 64, 64};
-  int col = 0;
-  for (int i = 0; i < 10; ++i) {
-    if (i < 5) {
-      if (dz[i] == nullptr || (((uintptr_t)dz[i]) & 15) || (dz_ld[i] % 8) != 0 || dz_ld[i] < widths[i] || (i < 4 && g_bias[i] == nullptr)) return SNERF_ERR_ARG;
-      a.dz[i] = (__bf16*)dz[i]; a.dz_ld[i] = dz_ld[i];
-      tab.dst[i] = i < 4 ? g_bias[i] : ws + (long)grid * FZCH_COLS;      // (the last step's column sums are not a bias gradient: into the workspace's tail)
-      tab.first[i] = col; col += widths[i];
-    } else {
-      tab.dst[i] = nullptr; tab.first[i] = 1 << 30;
-    }
-  }
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)fzip_chain_bwd_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, FZCH_LDS);
-    (void)hipFuncSetAttribute((const void*)fzip_chain_bwd_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, FZCH_LDS);
-    attr_set = true;
-  }
+  if (!fmlp_bits_ok(bits, 3, true, a.bits) || !fmlp_mats_ok(dz, dz_ld, 5, widths, a.dz, a.dz_ld)) return SNERF_ERR_ARG;
+  for (int i = 0; i < 4; ++i)
+    if (g_bias[i] == nullptr) return SNERF_ERR_ARG;
+  const int grid = fmlp_grid(a.tiles);
+  float* const dst[5] = {g_bias[0], g_bias[1], g_bias[2], g_bias[3], ws + (long)grid * FZCH_COLS};   // (the last step's column sums are not a bias gradient: into the workspace's tail)
+  const ChainFoldTab tab = fchain_fold_tab(widths, 5, dst);
   hipStream_t st = (hipStream_t)stream;
   (void)hipMemsetAsync(ws + (long)grid * FZCH_COLS, 0, 64 * sizeof(float), st);
-  if (dtype == SNERF_DT_F16) hipLaunchKernelGGL(fzip_chain_bwd_kernel<true>, dim3(grid), dim3(64 * FM_WAVES), FZCH_LDS, st, a);
-  else hipLaunchKernelGGL(fzip_chain_bwd_kernel<false>, dim3(grid), dim3(64 * FM_WAVES), FZCH_LDS, st, a);
+  fmlp_launch_pair<ZipChainArgs, fzip_chain_bwd_kernel<false>, fzip_chain_bwd_kernel<true>>(dtype, grid, FZCH_LDS, stream, a);
   hipLaunchKernelGGL(fchain_colsum_fold_kernel, dim3((FZCH_COLS + 63) / 64), dim3(256), 0, st, (const float*)ws, grid, FZCH_COLS, tab);
   return snerf_check_launch();
 }

@@ -255,6 +255,7 @@ class _Net:
         self.fw, self.fb, self.tw = {}, {}, {}
         self._rec = None                  # while a plan is being recorded: [(index image, dtype of the operand)]
         self._plans = {}                  # what was packed -> _PackPlan
+        self._fused = {}                  # fused kernel -> (parameter version, (weight stream, bias table)): _fused_stream
 
     # ---- packing -------------------------------------------------------------
     # The pack() methods below DESCRIBE the operand layouts with ordinary slicing code.  They run once per network (and per train
@@ -389,6 +390,22 @@ class _Net:
         if key == "fused":
             self.fstream, self.fbias = sb
         return sb
+
+    def _fused_stream(self, key, pack):
+        """(stream, bias) of the fused kernel `key` (`pack`: its fmlp_pack description), gathered again when the parameters have changed since"""
+        v = self.version_fn()
+        hit = self._fused.get(key)
+        if hit is None or hit[0] != v:
+            with torch.no_grad():
+                hit = self._fused[key] = (v, self._refresh_fused(pack, key, dtype=self.tdt))
+        return hit[1]
+
+    def _fused_ready(self):
+        """the 256-wide networks: self.fstream / self.fbias are current"""
+        self._fused_stream("fused", self._pack_fused)
+
+    def _chain_stream(self):
+        return self._fused_stream("chain", self._pack_chain)[0]
 
     def _pack_fwd(self, key, name, segs, kbuf):
         W = self.W(name)
@@ -597,13 +614,6 @@ class ClassicNeRFNet(_Net):
         L.append((self.W("rgb_linear"), self.B("rgb_linear"), [(0, W // 2, True)]))
         return fmlp_pack(L, self.dev)
 
-    def _fused_ready(self):
-        v = self.version_fn()
-        if getattr(self, "_fused_version", None) != v:
-            with torch.no_grad():
-                self._refresh_fused(self._pack_fused, dtype=self.tdt)
-            self._fused_version = v
-
     def chain_ok(self):
         """the data-gradient chain as ONE launch (csrc/fmlp.hip fchain_bwd_kernel); its bias gradients meet in LDS atomics, so the
         deterministic mode keeps the per-layer kernels"""
@@ -619,14 +629,6 @@ class ClassicNeRFNet(_Net):
             Wi = self.W(f"pts_linears.{i}")
             L.append(((Wi[:, ic:] if i == self.skip + 1 else Wi).t(), None, [(0, W, True)]))         # d pts_linears.i -> d pts_linears.(i-1)
         return fmlp_pack(L, self.dev)
-
-    def _chain_stream(self):
-        v = self.version_fn()
-        if getattr(self, "_chain_version", None) != v:
-            with torch.no_grad():
-                self._chain = self._refresh_fused(self._pack_chain, "chain", dtype=self.tdt)
-            self._chain_version = v
-        return self._chain[0]
 
     def forward_fused_train(self, pts, viewdirs, S):
         """Training forward: the exact embedding kernel + ONE fused kernel that also stores the hidden activations in the buffers the
@@ -940,13 +942,6 @@ class MipProposalNet(_Net):
         L.append((self.W("density_layer"), self.B("density_layer"), [(0, self.H, True)]))
         return fmlp_pack(L, self.dev)
 
-    def _fused_ready(self):
-        v = self.version_fn()
-        if getattr(self, "_fused_version", None) != v:
-            with torch.no_grad():
-                self._refresh_fused(self._pack_fused, dtype=self.tdt)
-            self._fused_version = v
-
     def chain_ok(self):
         return self.fused_ok() and getattr(self, "fused_chain", True) and not self.deterministic
 
@@ -954,14 +949,6 @@ class MipProposalNet(_Net):
         L = [(self.W("density_layer").t(), None, [(0, 1, False)])]
         L += [(self.W(f"layers.{i}.layers.0").t(), None, [(0, self.H, True)]) for i in range(self.L - 1, 0, -1)]
         return fmlp_pack(L, self.dev)
-
-    def _chain_stream(self):
-        v = self.version_fn()
-        if getattr(self, "_chain_version", None) != v:
-            with torch.no_grad():
-                self._chain = self._refresh_fused(self._pack_chain, "chain", dtype=self.tdt)
-            self._chain_version = v
-        return self._chain[0]
 
     def forward_fused(self, E):
         self._fused_ready()
@@ -1136,13 +1123,9 @@ class MipNerfNet(_Net):
         return fmlp_pack(L, self.dev)
 
     def _colour_streams(self, train):
-        v = self.version_fn()
-        if getattr(self, "_colour_version", None) != (v, train) and not (not train and getattr(self, "_colour_version", None) == (v, True)):
-            with torch.no_grad():
-                self._cfwd = self._refresh_fused(self._pack_colour_fwd, "colour_fwd", dtype=self.tdt)
-                if train:
-                    self._cbwd = self._refresh_fused(self._pack_colour_bwd, "colour_bwd", dtype=self.tdt)
-            self._colour_version = (v, train)
+        self._cfwd = self._fused_stream("colour_fwd", self._pack_colour_fwd)
+        if train:                                       # (the backward's stream: training only)
+            self._cbwd = self._fused_stream("colour_bwd", self._pack_colour_bwd)
 
     def alloc_inputs(self, M):
         """-> (SKIP, CB); the encoders write SKIP[:, H:] and CB[:, H:] in place."""
@@ -1462,18 +1445,10 @@ class ZipNerfNet(_Net):
             layers.append((Wr[:, 32 * j:32 * j + 32], br if j == 0 else None, [(0, 32, True)]))
         return fmlp_pack(layers, self.dev)
 
-    def _zip_streams(self):
-        v = self.version_fn()
-        if getattr(self, "_zinfer_version", None) != v:
-            with torch.no_grad():
-                self._zinfer = self._refresh_fused(self._pack_fused_infer, "zip_infer", dtype=self.tdt)
-            self._zinfer_version = v
-        return self._zinfer
-
     def forward_fused(self, Fb, D, want_x=False):
         """Fb [M, 64] grid features, D [M, 16] direction encoding (compute dtype, zero padded) -> raw_rgb [M,3], raw_density [M,1] fp32;
         `want_x`: self.last_x = the first 32 channels of x [M, 32] (the semantic head's logits are its columns 1 .. C)"""
-        st, bi = self._zip_streams()
+        st, bi = self._fused_stream("zip_infer", self._pack_fused_infer)
         M = Fb.shape[0]
         raw_rgb, raw_d = self.buf(M, 3, f32=True), self.buf(M, 1, f32=True)
         self.last_x = self.buf(M, 32) if want_x else None
@@ -1485,7 +1460,7 @@ class ZipNerfNet(_Net):
         know which of the two ran).  SB [M, Wd + B + Dw] arrives with the direction encoding in its last block; h and x are written into
         its first two."""
         self.ensure_packed(True)                                  # (the backward's operands + the bit-mask registry of this step)
-        st, bi = self._zip_streams()
+        st, bi = self._fused_stream("zip_infer", self._pack_fused_infer)
         M, B, Wd = Fb.shape[0], self.Bw, self.Wd
         H1, H3 = self.buf(M, self.H), self.buf(M, Wd)
         h2, X = SB[:, :Wd], SB[:, Wd:Wd + B]
@@ -1577,13 +1552,9 @@ class ZipNerfNet(_Net):
         if self.fused_chain_ok(saved, d_raw_density.shape[1]):
             # the five data gradients as ONE launch (csrc/fmlp.hip, fzip_chain_bwd_kernel) on the bit masks the fused forward wrote; the
             # weight gradients read its outputs exactly like the per-layer chain's
-            v = self.version_fn()
-            if getattr(self, "_zchain_version", None) != v:
-                with torch.no_grad():
-                    self._zchain = self._refresh_fused(self._pack_fused_chain, "zip_chain", dtype=self.tdt)
-                self._zchain_version = v
+            zchain = self._fused_stream("zip_chain", self._pack_fused_chain)[0]
             dx, dH1, dF = self.buf(M, B), self.buf(M, self.H), self.buf(M, self.Fw)
-            ops.fmlp_zip_chain_bwd(_f32(d_raw_rgb), _f32(d_raw_density), self._zchain[0], self._zip_bits[0], [DZ[:, Wd:2 * Wd], DZ[:, :Wd], dx, dH1, dF],
+            ops.fmlp_zip_chain_bwd(_f32(d_raw_rgb), _f32(d_raw_density), zchain, self._zip_bits[0], [DZ[:, Wd:2 * Wd], DZ[:, :Wd], dx, dH1, dF],
                                    [self.gB("lin_second_stage_1"), self.gB("lin_second_stage_0"), self.gB("density_layer.2"), self.gB("density_layer.0")])
             self.wgrad("lin_second_stage_1", DZ[:, Wd:2 * Wd], SB, Wd, Wd + B + self.dd)
             self.wgrad("lin_second_stage_0", DZ[:, :Wd], SB[:, Wd:], Wd, B + self.dd)

@@ -5,6 +5,7 @@ function launches hand-written HIP kernels from libsnerf_hip.so through
 ``_lib.call``; nothing in this file computes on the host or falls back to
 torch ops.
 """
+import ctypes
 import os as _os
 
 import torch
@@ -229,20 +230,48 @@ def fmlp_classic_x_fwd(x, stream, bias, raw):
               x.shape[0], dt, _stream())
 
 
+def _mat_arrays(mats, M, widths, tdt, aligned=False):
+    """the HOST arrays (device pointers, row strides in elements) the fused entries take for a list of stored 16-bit matrices: 2-D views
+    [M, >= widths[i]] of dtype `tdt` with unit column stride; `aligned`: 16-byte aligned with row strides % 8 == 0 asserted here as well"""
+    assert len(mats) == len(widths)
+    for y, w in zip(mats, widths):
+        assert y.dtype == tdt and y.dim() == 2 and y.stride(1) == 1 and y.shape[0] == M and y.shape[1] >= w
+        assert not aligned or (y.data_ptr() % 16 == 0 and y.stride(0) % 8 == 0)
+    return (ctypes.c_void_p * len(mats))(*[y.data_ptr() for y in mats]), (ctypes.c_long * len(mats))(*[y.stride(0) for y in mats])
+
+
+def _mask_array(bits, M, widths):
+    """... and for the ReLU bit masks of M rows of widths[i] columns (contiguous int32, mask_bits_words each)"""
+    assert len(bits) == len(widths)
+    for b, w in zip(bits, widths):
+        assert b.dtype == torch.int32 and b.is_contiguous() and b.numel() >= mask_bits_words(M, w)
+    return (ctypes.c_void_p * len(bits))(*[b.data_ptr() for b in bits])
+
+
+def _bias_array(g_bias, widths):
+    """... and for the fp32 bias gradients (contiguous, exactly widths[i] floats) the gradient chains add to"""
+    assert len(g_bias) == len(widths)
+    for gb, w in zip(g_bias, widths):
+        assert gb.dtype == torch.float32 and gb.is_contiguous() and gb.numel() == w
+    return (ctypes.c_void_p * len(g_bias))(*[g.data_ptr() for g in g_bias])
+
+
+_CLASSIC_WIDTHS = [256] * 9 + [128]                 # pts_linears.0 .. .7, feature_linear, views_linears.0
+_CLASSIC_MASKS = [256] * 8 + [128]                  # pts_linears.0 .. .7, views_linears.0
+
+
 def fmlp_classic_x_train_fwd(x, stream, bias, raw, xin, acts, bits):
     """fmlp_classic_train_fwd on pre-embedded fp32 rows x (as fmlp_classic_x_fwd); additionally writes the rounded inputs into
     `xin` = [E [M, >= 64], skip-buffer head [M, >= 64], view tail [M, >= 32]] (row-major views in the stream's dtype, 16-byte aligned, row
     strides % 8 == 0)."""
-    import ctypes
     _x_rows(x); _chk2d(raw, torch.float32)
     tdt, dt = _fmlp_dt(stream)
     assert bias.dtype == torch.float32 and raw.is_contiguous() and raw.shape == (x.shape[0], 4)
-    assert len(bits) == 9 and len(xin) == 3
     M = x.shape[0]
-    ptrs, lds, bp = _act_arrays(acts, bits, M, [256] * 9 + [128], tdt)
-    xp, xl, _ = _act_arrays(xin, [], M, [64, 64, 32], tdt)
+    ptrs, lds = _mat_arrays(acts, M, _CLASSIC_WIDTHS, tdt, aligned=True)
+    xp, xl = _mat_arrays(xin, M, [64, 64, 32], tdt, aligned=True)
     _lib.call("snerf_fmlp_classic_x_train_fwd_dt", _p(x), max(x.stride(0), 90), _p(stream), stream.shape[0], _p(bias), bias.numel() // 32, _p(raw),
-              ctypes.addressof(xp), ctypes.addressof(xl), ctypes.addressof(ptrs), ctypes.addressof(lds), ctypes.addressof(bp), M, dt, _stream())
+              xp, xl, ptrs, lds, _mask_array(bits, M, _CLASSIC_MASKS), M, dt, _stream())
 
 
 def fmlp_proposal_fwd(E, stream, bias, raw_density):
@@ -255,44 +284,30 @@ def fmlp_proposal_fwd(E, stream, bias, raw_density):
               E.shape[0], dt, _stream())
 
 
-def _act_arrays(acts, bits, M, widths, tdt=torch.bfloat16):
-    import ctypes
-    assert len(acts) == len(widths)
-    for y, w in zip(acts, widths):
-        assert y.dtype == tdt and y.dim() == 2 and y.stride(1) == 1 and y.shape[0] == M and y.shape[1] >= w
-        assert y.data_ptr() % 16 == 0 and y.stride(0) % 8 == 0
-    for i, b in enumerate(bits):
-        assert b.dtype == torch.int32 and b.is_contiguous() and b.numel() >= mask_bits_words(M, 128 if i == 8 else 256)
-    ptrs = (ctypes.c_void_p * len(acts))(*[y.data_ptr() for y in acts])
-    lds = (ctypes.c_long * len(acts))(*[y.stride(0) for y in acts])
-    bp = (ctypes.c_void_p * len(bits))(*[b.data_ptr() for b in bits])
-    return ptrs, lds, bp
-
-
 def fmlp_classic_train_fwd(E, VE, stream, bias, raw, acts, bits):
     """fmlp_classic_fwd that also stores the ten hidden-layer outputs (`acts`: pts_linears.0..7 [M,256], feature [M,256], views
     [M,128], row-major views in the stream's dtype) and the ReLU bit masks of the eight trunk layers (`bits[0..7]`: int32 [mask_bits_words(M, 256)]
     each) and of views_linears.0 (`bits[8]`: [mask_bits_words(M, 128)]) for the backward pass."""
-    import ctypes
     tdt, dt = _fmlp_dt(stream)
     _chk2d(E, tdt); _chk2d(VE, tdt); _chk2d(raw, torch.float32)
+    M = E.shape[0]
     assert bias.dtype == torch.float32 and raw.is_contiguous() and raw.shape[1] == 4
-    assert E.shape[1] >= 64 and VE.shape[1] >= 32 and VE.shape[0] == E.shape[0] == raw.shape[0] and len(bits) == 9
-    ptrs, lds, bp = _act_arrays(acts, bits, E.shape[0], [256] * 9 + [128], tdt)
+    assert E.shape[1] >= 64 and VE.shape[1] >= 32 and VE.shape[0] == M == raw.shape[0]
+    ptrs, lds = _mat_arrays(acts, M, _CLASSIC_WIDTHS, tdt, aligned=True)
     _lib.call("snerf_fmlp_classic_train_fwd_dt", _p(E), E.stride(0), _p(VE), VE.stride(0), _p(stream), stream.shape[0], _p(bias),
-              bias.numel() // 32, _p(raw), ctypes.addressof(ptrs), ctypes.addressof(lds), ctypes.addressof(bp), E.shape[0], dt, _stream())
+              bias.numel() // 32, _p(raw), ptrs, lds, _mask_array(bits, M, _CLASSIC_MASKS), M, dt, _stream())
 
 
 def fmlp_proposal_train_fwd(E, stream, bias, raw_density, acts, bits):
     """fmlp_proposal_fwd that also stores the four hidden-layer outputs (`acts`: [M,256] each, the stream's dtype) and their ReLU bit masks."""
-    import ctypes
     tdt, dt = _fmlp_dt(stream)
     _chk2d(E, tdt)
+    M = E.shape[0]
     assert bias.dtype == torch.float32 and E.shape[1] >= 96
-    assert raw_density.dtype == torch.float32 and raw_density.is_contiguous() and raw_density.numel() == E.shape[0] and len(bits) == 4
-    ptrs, lds, bp = _act_arrays(acts, bits, E.shape[0], [256] * 4, tdt)
+    assert raw_density.dtype == torch.float32 and raw_density.is_contiguous() and raw_density.numel() == M
+    ptrs, lds = _mat_arrays(acts, M, [256] * 4, tdt, aligned=True)
     _lib.call("snerf_fmlp_proposal_train_fwd_dt", _p(E), E.stride(0), _p(stream), stream.shape[0], _p(bias), bias.numel() // 32,
-              _p(raw_density), ctypes.addressof(ptrs), ctypes.addressof(lds), ctypes.addressof(bp), E.shape[0], dt, _stream())
+              _p(raw_density), ptrs, lds, _mask_array(bits, M, [256] * 4), M, dt, _stream())
 
 
 def fmlp_zip_fwd(Fb, D, stream, bias, raw_rgb, raw_d, x32=None):
@@ -314,55 +329,37 @@ def fmlp_zip_train_fwd(Fb, D, stream, bias, raw_rgb, raw_d, acts, bits):
     """The training forward of the zipnerf NeRF MLP in ONE launch (fzip_fwd_kernel<.., STORE>): as fmlp_zip_fwd, plus acts = [H1 [M, >= 64],
     x, h, H3 [M, >= 256]] (compute dtype 2-D views, written) and bits = 3 x int32: the ReLU bit masks of H1 [mask_bits_words(M, 64)], h and H3
     [mask_bits_words(M, 256)]."""
-    import ctypes
     _chk2d(Fb, Fb.dtype); _chk2d(D, Fb.dtype); _chk2d(raw_rgb, torch.float32); _chk2d(raw_d, torch.float32)
     M = Fb.shape[0]
     assert Fb.dtype in (torch.bfloat16, torch.float16) and stream.dtype == Fb.dtype and stream.is_contiguous() and bias.dtype == torch.float32
-    assert D.shape[0] == M and raw_rgb.shape[0] == M and raw_d.shape[0] == M and Fb.shape[1] >= 64 and D.shape[1] >= 16 and len(acts) == 4 and len(bits) == 3
-    for i, y in enumerate(acts):
-        _chk2d(y, Fb.dtype)
-        assert y.shape[0] == M and y.shape[1] >= (64 if i == 0 else 256)
-    for i, b in enumerate(bits):
-        assert b.dtype == torch.int32 and b.is_contiguous() and b.numel() >= mask_bits_words(M, 64 if i == 0 else 256)
-    pa = (ctypes.c_void_p * 4)(*[y.data_ptr() for y in acts])
-    pl = (ctypes.c_long * 4)(*[y.stride(0) for y in acts])
-    pb = (ctypes.c_void_p * 3)(*[b.data_ptr() for b in bits])
+    assert D.shape[0] == M and raw_rgb.shape[0] == M and raw_d.shape[0] == M and Fb.shape[1] >= 64 and D.shape[1] >= 16
+    assert all(y.is_cuda for y in acts)
+    pa, pl = _mat_arrays(acts, M, [64, 256, 256, 256], Fb.dtype)
     _lib.call("snerf_fmlp_zip_train_fwd", _p(Fb), Fb.stride(0), _p(D), D.stride(0), _p(stream), stream.shape[0], _p(bias), bias.numel() // 32,
-              _p(raw_rgb), raw_rgb.stride(0), _p(raw_d), raw_d.stride(0), ctypes.addressof(pa), ctypes.addressof(pl), ctypes.addressof(pb), M,
-              _zip_dt(Fb), _stream())
+              _p(raw_rgb), raw_rgb.stride(0), _p(raw_d), raw_d.stride(0), pa, pl, _mask_array(bits, M, [64, 256, 256]), M, _zip_dt(Fb), _stream())
 
 
 def fmlp_zip_chain_bwd(d_rgb, d_den, stream, bits, dz, g_bias):
     """Data-gradient chain of the zipnerf NeRF MLP in ONE launch (fzip_chain_bwd_kernel): d_rgb [M,3], d_den [M, 1 + C <= 32] fp32 -> dz = [dH3, dh,
     dx ([M, >= 256]), dH1, dF ([M, >= 64])] (compute dtype views, written); bits = the forward's masks of H1, h, H3; the bias gradients of
     lin_second_stage_1 / _0, density_layer.2 / .0 are added to g_bias[0..3] (not bit-reproducible)."""
-    import ctypes
     _chk2d(d_rgb, torch.float32); _chk2d(d_den, torch.float32)
     M = d_rgb.shape[0]
     assert d_den.shape[0] == M and 1 <= d_den.shape[1] <= 32 and stream.dtype in (torch.bfloat16, torch.float16) and stream.is_contiguous()
-    assert len(bits) == 3 and len(dz) == 5 and len(g_bias) == 4
-    for i, b in enumerate(bits):
-        assert b.dtype == torch.int32 and b.is_contiguous() and b.numel() >= mask_bits_words(M, 64 if i == 0 else 256)
-    for i, y in enumerate(dz):
-        _chk2d(y, stream.dtype)
-        assert y.shape[0] == M and y.shape[1] >= (256 if i < 3 else 64)
-    for gb, w in zip(g_bias, (256, 256, 256, 64)):
-        assert gb.dtype == torch.float32 and gb.is_contiguous() and gb.numel() == w
+    assert all(y.is_cuda for y in dz)
+    pb = _mask_array(bits, M, [64, 256, 256])
+    pz, pl = _mat_arrays(dz, M, [256, 256, 256, 64, 64], stream.dtype)
+    pg = _bias_array(g_bias, [256, 256, 256, 64])
     nws = _lib.query("snerf_fmlp_zip_chain_ws_floats", M)
     ws = torch.empty(max(int(nws), 1), dtype=torch.float32, device=d_rgb.device)
-    pb = (ctypes.c_void_p * 3)(*[b.data_ptr() for b in bits])
-    pz = (ctypes.c_void_p * 5)(*[y.data_ptr() for y in dz])
-    pl = (ctypes.c_long * 5)(*[y.stride(0) for y in dz])
-    pg = (ctypes.c_void_p * 4)(*[g.data_ptr() for g in g_bias])
     _lib.call("snerf_fmlp_zip_chain_bwd", _p(d_rgb), d_rgb.stride(0), _p(d_den), d_den.stride(0), d_den.shape[1], _p(stream), stream.shape[0],
-              ctypes.addressof(pb), ctypes.addressof(pz), ctypes.addressof(pl), ctypes.addressof(pg), _p(ws), ws.numel(), M, _zip_dt(stream), _stream())
+              pb, pz, pl, pg, _p(ws), ws.numel(), M, _zip_dt(stream), _stream())
 
 
 def fcolour_fwd(CB, stream, bias, raw_rgb, acts=None, bits=None, variant=0):
     """Fused colour head of the mip path's NeRF MLP (csrc/fmlp.hip): CB [M, >= 1056] = [bottleneck 1024 | view encoding 27 | 0] in the
     stream's dtype (bf16 or fp16) -> raw_rgb [M,3] fp32 in ONE launch.  Training: `acts` = 3 x [M, >= 128] in the same dtype (outputs of
     cond_layers.0..2), `bits` = 3 x int32 [mask_bits_words(M, 128)] (their ReLU bit masks), stored for fcolour_bwd and the weight-gradient GEMMs."""
-    import ctypes
     tdt, dt = _fmlp_dt(stream)
     _chk2d(CB, tdt); _chk2d(raw_rgb, torch.float32)
     M = CB.shape[0]
@@ -370,16 +367,10 @@ def fcolour_fwd(CB, stream, bias, raw_rgb, acts=None, bits=None, variant=0):
     assert raw_rgb.is_contiguous() and raw_rgb.shape == (M, 3)
     pa = pl = pb = None
     if acts is not None:
-        assert len(acts) == 3 and len(bits) == 3
-        for y, b in zip(acts, bits):
-            assert y.dtype == tdt and y.dim() == 2 and y.stride(1) == 1 and y.shape[0] == M and y.shape[1] >= 128
-            assert b.dtype == torch.int32 and b.is_contiguous() and b.numel() >= mask_bits_words(M, 128)
-        pa = (ctypes.c_void_p * 3)(*[y.data_ptr() for y in acts])
-        pl = (ctypes.c_long * 3)(*[y.stride(0) for y in acts])
-        pb = (ctypes.c_void_p * 3)(*[b.data_ptr() for b in bits])
+        pa, pl = _mat_arrays(acts, M, [128] * 3, tdt)
+        pb = _mask_array(bits, M, [128] * 3)
     _lib.call("snerf_fcolour_fwd_dt", _p(CB), CB.stride(0), _p(stream), stream.shape[0], _p(bias), bias.numel() // 32, _p(raw_rgb),
-              None if pa is None else ctypes.addressof(pa), None if pl is None else ctypes.addressof(pl),
-              None if pb is None else ctypes.addressof(pb), M, int(variant), dt, _stream())
+              pa, pl, pb, M, int(variant), dt, _stream())
 
 
 def fcolour_bwd(d_raw_rgb, stream, bits, dC, dB, g_bias):
@@ -387,26 +378,17 @@ def fcolour_bwd(d_raw_rgb, stream, bits, dC, dB, g_bias):
     ([M, >= 1024] view), all in the stream's dtype (bf16 or fp16; in fp16 d_raw_rgb arrives already multiplied by the loss scale);
     bits = ReLU bit masks of [cond_layers.2, .1, .0, bottleneck]; the bias gradients are added to g_bias = [cond_layers.2, .1, .0,
     bottleneck] (fp32 views of the gradient arena) in a fixed order."""
-    import ctypes
     tdt, dt = _fmlp_dt(stream)
     _f32c(d_raw_rgb); _chk2d(dB, tdt)
     M = d_raw_rgb.shape[0]
-    assert d_raw_rgb.shape[1] == 3 and len(bits) == 4 and len(dC) == 3 and len(g_bias) == 4
-    assert dB.shape[0] == M and dB.shape[1] >= 1024
-    for b, n in zip(bits, (128, 128, 128, 1024)):
-        assert b.dtype == torch.int32 and b.is_contiguous() and b.numel() >= mask_bits_words(M, n)
-    for y in dC:
-        assert y.dtype == tdt and y.dim() == 2 and y.stride(1) == 1 and y.shape[0] == M and y.shape[1] >= 128
-    for gb, n in zip(g_bias, (128, 128, 128, 1024)):
-        assert gb.dtype == torch.float32 and gb.is_contiguous() and gb.numel() == n
+    assert d_raw_rgb.shape[1] == 3 and dB.shape[0] == M and dB.shape[1] >= 1024
+    pb = _mask_array(bits, M, [128, 128, 128, 1024])
+    pc, pl = _mat_arrays(dC, M, [128] * 3, tdt)
+    pg = _bias_array(g_bias, [128, 128, 128, 1024])
     nws = _lib.query("snerf_fcolour_bwd_ws_floats", M)
     ws = torch.empty(max(int(nws), 1), dtype=torch.float32, device=dB.device)
-    pb = (ctypes.c_void_p * 4)(*[b.data_ptr() for b in bits])
-    pc = (ctypes.c_void_p * 3)(*[y.data_ptr() for y in dC])
-    pl = (ctypes.c_long * 3)(*[y.stride(0) for y in dC])
-    pg = (ctypes.c_void_p * 4)(*[g.data_ptr() for g in g_bias])
-    _lib.call("snerf_fcolour_bwd_dt", _p(d_raw_rgb), _p(stream), stream.shape[0], ctypes.addressof(pb), ctypes.addressof(pc), ctypes.addressof(pl),
-              _p(dB), dB.stride(0), ctypes.addressof(pg), _p(ws), ws.numel(), M, dt, _stream())
+    _lib.call("snerf_fcolour_bwd_dt", _p(d_raw_rgb), _p(stream), stream.shape[0], pb, pc, pl, _p(dB), dB.stride(0), pg, _p(ws), ws.numel(), M, dt,
+              _stream())
 
 
 CHAIN_CLASSIC, CHAIN_PROPOSAL = 0, 1
@@ -418,28 +400,18 @@ def fchain_bwd(net, d_raw, stream, bits, dz, g_bias):
     masks of pts_linears.0..7 + views_linears.0.  CHAIN_PROPOSAL: d_raw [M] / [M,1] (d raw density) -> dz = [d layers.3 .. .0]; bits =
     masks of layers.0..3.  The bias gradient of step i is added to g_bias[i] (not bit-reproducible: workgroup-level LDS atomics).
     `stream` and every dz carry one 16-bit dtype, bf16 or fp16; in fp16 d_raw arrives already multiplied by the loss scale."""
-    import ctypes
     classic = net == CHAIN_CLASSIC
     d_raw = _f32c(d_raw)
     M = d_raw.shape[0]
     widths = ([128] + [256] * 9) if classic else [256] * 4
     tdt, dt = _fmlp_dt(stream)
     assert d_raw.numel() == M * (4 if classic else 1)
-    assert len(bits) == (9 if classic else 4) and len(dz) == len(widths) == len(g_bias)
-    for i, b in enumerate(bits):
-        assert b.dtype == torch.int32 and b.is_contiguous() and b.numel() >= mask_bits_words(M, 128 if i == 8 else 256)
-    for y, w in zip(dz, widths):
-        assert y.dtype == tdt and y.dim() == 2 and y.stride(1) == 1 and y.shape[0] == M and y.shape[1] >= w
-    for gb, w in zip(g_bias, widths):
-        assert gb.dtype == torch.float32 and gb.is_contiguous() and gb.numel() == w
+    pb = _mask_array(bits, M, _CLASSIC_MASKS if classic else [256] * 4)
+    pz, pl = _mat_arrays(dz, M, widths, tdt)
+    pg = _bias_array(g_bias, widths)
     nws = _lib.query("snerf_fchain_bwd_ws_floats", net, M)
     ws = torch.empty(max(int(nws), 1), dtype=torch.float32, device=d_raw.device)
-    pb = (ctypes.c_void_p * len(bits))(*[b.data_ptr() for b in bits])
-    pz = (ctypes.c_void_p * len(dz))(*[y.data_ptr() for y in dz])
-    pl = (ctypes.c_long * len(dz))(*[y.stride(0) for y in dz])
-    pg = (ctypes.c_void_p * len(dz))(*[g.data_ptr() for g in g_bias])
-    _lib.call("snerf_fchain_bwd_dt", net, _p(d_raw), _p(stream), stream.shape[0], ctypes.addressof(pb), ctypes.addressof(pz), ctypes.addressof(pl),
-              ctypes.addressof(pg), _p(ws), ws.numel(), M, dt, _stream())
+    _lib.call("snerf_fchain_bwd_dt", net, _p(d_raw), _p(stream), stream.shape[0], pb, pz, pl, pg, _p(ws), ws.numel(), M, dt, _stream())
 
 
 # --------------------------------------------------------------- encoders ----
@@ -1018,7 +990,6 @@ def grid_encode_bwd_binned(grad, inputs, offsets, C, L, S, H, out_dtype=torch.fl
 def grid_encode_bwd_binned_plan(B, C, L, offsets_host, half_records, grad_dtype=torch.float16, level_major=False, ws_bytes=None):
     """what snerf_grid_encode_bwd_binned would run on a workspace of ws_bytes (default: the recommended size): dict(chunks, chunk_points,
     levels_per_transposed_group, launches, chunk_record_capacity, bytes_used, ws_bytes)"""
-    import ctypes
     import numpy as np
     oh = np.ascontiguousarray(np.asarray(offsets_host, dtype=np.int32))
     if ws_bytes is None:

@@ -830,7 +830,7 @@ def fmlp_zip_fwd(Fb, D, stream, bias, raw_rgb, raw_d, x32=None):
 
 def fmlp_classic_pts_fwd(pts, viewdirs, S, stream, bias, raw):
     M = pts.shape[0]
-    pad = lambda t, w: torch.cat([t, torch.zeros(M, w - t.shape[1])], -1).to(torch.bfloat16)
+    pad = lambda t, w: torch.cat([t, torch.zeros(M, w - t.shape[1])], -1).to(stream.dtype)
     fmlp_classic_fwd(pad(oc.embed(pts, 10), 64), pad(oc.embed(viewdirs[:, None].expand(-1, S, -1).reshape(-1, 3), 4), 64), stream, bias, raw)
 
 
@@ -860,9 +860,11 @@ def fmlp_proposal_train_fwd(E, stream, bias, raw_density, acts, bits):
 
 
 def fcolour_fwd(CB, stream, bias, raw_rgb, acts=None, bits=None, variant=0):
-    """model of fcolour_fwd_kernel: cond_layers.0 K-MAJOR (66 k-steps x 4 blocks), then two 128-wide layers and the rgb head"""
+    """model of fcolour_fwd_kernel in either flavour: cond_layers.0 K-MAJOR (66 k-steps x 4 blocks), then two 128-wide layers and the rgb head"""
     assert stream.shape[0] == 336 and bias.numel() == 13 * 32
-    st = _FStream(stream, bias)
+    assert CB.dtype == stream.dtype and (acts is None or all(y.dtype == stream.dtype for y in acts))
+    dt = stream.dtype
+    st = _FStream(stream, bias)                       # (its dense / block round to the stream's dtype already)
     M = CB.shape[0]
     acc = [bias[32 * j:32 * j + 32].clone()[None, :].expand(M, 32).clone() for j in range(4)]
     st.nb = 4
@@ -871,7 +873,7 @@ def fcolour_fwd(CB, stream, bias, raw_rgb, acts=None, bits=None, variant=0):
             acc[j] = acc[j] + x @ st.frag().t()
     p = []
     for j in range(4):
-        y = torch.relu(acc[j].to(torch.bfloat16).float())
+        y = torch.relu(acc[j].to(dt).float())
         if acts is not None:
             acts[0][:, 32 * j:32 * j + 32] = y.to(acts[0].dtype)
         p += [y[:, _P], y[:, 16 + _P]]
@@ -885,20 +887,22 @@ def fcolour_fwd(CB, stream, bias, raw_rgb, acts=None, bits=None, variant=0):
 
 
 def fcolour_bwd(d_raw_rgb, stream, bits, dC, dB, g_bias):
-    """model of fcolour_bwd_kernel: the data-gradient chain on the transposed weights; masks, bias gradients (of the masked fp32
-    accumulators), bf16 stores"""
+    """model of fcolour_bwd_kernel in either flavour: the data-gradient chain on the transposed weights; masks, bias gradients (of the masked
+    fp32 accumulators), stores in the stream's 16-bit type"""
     assert stream.shape[0] == 336
+    dt = stream.dtype
+    assert dB.dtype == dt and all(y.dtype == dt for y in dC)
     st = _FStream(stream, torch.zeros(44 * 32))
     M = d_raw_rgb.shape[0]
     g = torch.zeros(M, 16)
-    g[:, :3] = d_raw_rgb.to(torch.bfloat16).float()
+    g[:, :3] = d_raw_rgb.to(dt).float()
 
     def layer(inp, nblocks, mask, out, gb):
         frs = []
         for j in range(nblocks):
             a = st.block([inp], False, to_frags=False) * mask[:, 32 * j:32 * j + 32]
             gb[32 * j:32 * j + 32] += a.sum(0)
-            y = a.to(torch.bfloat16).float()
+            y = a.to(dt).float()
             out[:, 32 * j:32 * j + 32] = y.to(out.dtype)
             frs += [y[:, _P], y[:, 16 + _P]]
         return frs
@@ -911,17 +915,18 @@ def fcolour_bwd(d_raw_rgb, stream, bits, dC, dB, g_bias):
 
 
 def fchain_bwd(net, d_raw, stream, bits, dz, g_bias):
-    """model of fchain_bwd_kernel: the data-gradient chains of the 256-wide networks on the transposed weights (masks, bf16
-    stores, bias gradients = column sums of the stored gradients)"""
+    """model of fchain_bwd_kernel in either flavour: the data-gradient chains of the 256-wide networks on the transposed weights
+    (masks, stores in the stream's 16-bit type, bias gradients = column sums of the stored gradients)"""
     classic = net == 0
     assert stream.shape[0] == (1104 if classic else 400)
+    dt = stream.dtype
     st = _FStream(stream, torch.zeros(80 * 32))
     M = d_raw.shape[0]
     d_raw = d_raw.reshape(M, -1)
 
     def head(cols):
         g = torch.zeros(M, 16)
-        g[:, :len(cols)] = d_raw[:, cols].to(torch.bfloat16).float()
+        g[:, :len(cols)] = d_raw[:, cols].to(dt).float()
         return g
 
     def layer(segs, nblocks, mask, out, gb):
@@ -930,8 +935,8 @@ def fchain_bwd(net, d_raw, stream, bits, dz, g_bias):
             a = st.block(segs, False, to_frags=False)
             if mask is not None:
                 a = a * mask[:, 32 * j:32 * j + 32]
-            y = a.to(torch.bfloat16).float()
-            gb[32 * j:32 * j + 32] += y.sum(0)                    # (the kernel sums the bf16 gradients it stores, on the matrix cores)
+            y = a.to(dt).float()
+            gb[32 * j:32 * j + 32] += y.sum(0)                    # (the kernel sums the rounded gradients it stores)
             out[:, 32 * j:32 * j + 32] = y.to(out.dtype)
             frs += [y[:, _P], y[:, 16 + _P]]
         return frs

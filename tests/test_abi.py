@@ -100,3 +100,170 @@ def test_grid_binned_backward_workspace_query_and_its_limits():
     assert q(1000, 2, off, 0) > 0 and q(1000, 8, off, 1) > 0 and q(1000, 3, off, 0) == -1
     big = [0, 8, 8 + (1 << 23)]                                                   # 2^23 rows at C = 4: 2048 row ranges of 4096
     assert q(1000, 4, big, 1) == -1 and q(1000, 8, big, 0) == -1 and q(1000, 1, big, 1) > 0    # (C = 1: 512 ranges of 16384)
+
+
+# ---- the host statuses of the fused entries (csrc/fmlp.hip), one case list per entry ---------------------------------------------------------
+# Every case below is one that validation refuses or that has M <= 0: nothing reaches a launch, so the list runs on a box without a GPU.
+_F32, _BF16, _F16 = 0, 1, 2
+_HOST = (ctypes.c_char * 64)()
+_A = (ctypes.addressof(_HOST) + 15) & ~15           # a 16-byte aligned host address: the checks never dereference it
+_BIG = 1 << 31
+
+
+def _mats(ptr, ld, widths, min_width=True):
+    """refusals of an array of stored 16-bit matrices: null / misaligned pointer, stride % 8, stride below the width the entry asks for"""
+    out = []
+    for i, w in enumerate(widths):
+        out += [{f"{ptr}[{i}]": None}, {f"{ptr}[{i}]": _A + 8}, {f"{ld}[{i}]": w + 4}]
+        if min_width:
+            out.append({f"{ld}[{i}]": w - 8})
+    return out + [{ptr: None}, {ld: None}]
+
+
+def _ptrs(name, n, aligned):
+    """refusals of an array of bit-mask (aligned) or bias-gradient pointers"""
+    return [{f"{name}[{i}]": None} for i in range(n)] + ([{f"{name}[{i}]": _A + 4} for i in range(n)] if aligned else []) + [{name: None}]
+
+
+def _nulls(*names):
+    return [{n: None} for n in names]
+
+
+_W10 = [256] * 9 + [128]
+_CLASSIC = dict(wstream=_A, n_frags=1184, bias=_A, n_blocks=78, raw=_A, M=256)
+_STREAM_256 = _nulls("wstream", "bias", "raw") + [{"wstream": _A + 8}, {"n_frags": 1168}, {"n_frags": 1200}, {"n_blocks": 77}]
+_ROWS = dict(_CLASSIC, E=_A, ldE=64, VE=_A, ldVE=32)
+_ROWS_BAD = _STREAM_256 + _nulls("E", "VE") + [{"E": _A + 8}, {"VE": _A + 8}, {"ldE": 68}, {"ldVE": 36}, {"raw": _A + 4}]
+_TRAIN = dict(acts=[_A] * 10, act_ld=_W10, bits=[_A] * 9)
+_TRAIN_BAD = _mats("acts", "act_ld", _W10, min_width=False) + _ptrs("bits", 9, True)
+_X = dict(_CLASSIC, x=_A, ldx=90)
+_X_BAD = _STREAM_256 + [{"x": None}, {"x": _A + 2}, {"ldx": 89}, {"raw": _A + 4}, {"M": _BIG}]
+_PROP = dict(E=_A, ldE=96, wstream=_A, n_frags=448, bias=_A, n_blocks=33, raw_density=_A, M=256)
+_PROP_BAD = _nulls("E", "wstream", "bias", "raw_density") + [{"E": _A + 8}, {"ldE": 100}, {"wstream": _A + 8}, {"n_frags": 432}, {"n_blocks": 32}]
+_ZIP = dict(F=_A, ldF=64, D=_A, ldD=16, wstream=_A, n_frags=464, bias=_A, n_blocks=35, raw_rgb=_A, ld_rgb=3, raw_d=_A, ld_d=1, M=256)
+_ZIP_BAD = _nulls("F", "D", "wstream", "bias", "raw_rgb", "raw_d") + [
+    {"ldF": 56}, {"ldD": 8}, {"ldF": 68}, {"ldD": 20}, {"F": _A + 8}, {"D": _A + 8}, {"ld_rgb": 2}, {"ld_d": 0}, {"M": _BIG}, {"n_blocks": 34},
+    {"n_frags": 460}, {"n_frags": 448}]
+_COLOUR_BWD = dict(d_raw_rgb=_A, wstream=_A, n_frags=336, bits=[_A] * 4, dC=[_A] * 3, dC_ld=[128] * 3, dB=_A, dB_ld=1024, g_bias=[_A] * 4, ws=_A,
+                   ws_floats=1 << 40, M=256)
+_CHAIN = dict(d_raw=_A, wstream=_A, ws=_A, ws_floats=1 << 40, M=256)
+_CHAIN_BAD = _nulls("d_raw", "wstream", "ws") + [{"wstream": _A + 8}, {"d_raw": _A + 8}, {"ws_floats": "short"}, {"n_frags": 416}]
+
+# entry (the `_dt` name where there is a bf16 twin) -> (arguments that would reach the launch, refusals: each changes the arguments named)
+_FUSED = {
+    "snerf_fmlp_classic_fwd_dt": (_ROWS, _ROWS_BAD),
+    "snerf_fmlp_classic_train_fwd_dt": (dict(_ROWS, **_TRAIN), _ROWS_BAD + _TRAIN_BAD),
+    "snerf_fmlp_classic_pts_fwd_dt": (dict(_CLASSIC, pts=_A, viewdirs=_A, ldvd=3, S=8),
+                                      _STREAM_256 + _nulls("pts", "viewdirs") + [{"S": 0}, {"ldvd": 2}, {"raw": _A + 4}, {"M": _BIG}]),
+    "snerf_fmlp_classic_x_fwd_dt": (_X, _X_BAD),
+    "snerf_fmlp_classic_x_train_fwd_dt": (dict(_X, xin=[_A] * 3, xin_ld=[64, 64, 32], **_TRAIN),
+                                          _X_BAD + _mats("xin", "xin_ld", [64, 64, 32]) + _TRAIN_BAD),
+    "snerf_fmlp_proposal_fwd_dt": (_PROP, _PROP_BAD),
+    "snerf_fmlp_proposal_train_fwd_dt": (dict(_PROP, acts=[_A] * 4, act_ld=[256] * 4, bits=[_A] * 4),
+                                         _PROP_BAD + _mats("acts", "act_ld", [256] * 4, min_width=False) + _ptrs("bits", 4, False)),
+    "snerf_fmlp_zip_fwd": (dict(_ZIP, x32=None, ld_x=0),
+                           _ZIP_BAD + [{"x32": _A, "ld_x": 28}, {"x32": _A, "ld_x": 34}, {"x32": _A + 4, "ld_x": 32}]),
+    "snerf_fmlp_zip_train_fwd": (dict(_ZIP, acts=[_A] * 4, act_ld=[64, 256, 256, 256], bits=[_A] * 3),
+                                 _ZIP_BAD + _mats("acts", "act_ld", [64, 256, 256, 256]) + _ptrs("bits", 3, True)),
+    "snerf_fcolour_fwd_dt": (dict(CB=_A, ldCB=1056, wstream=_A, n_frags=336, bias=_A, n_blocks=13, raw_rgb=_A, acts=[_A] * 3, act_ld=[128] * 3,
+                                  bits=[_A] * 3, M=256, variant=0),
+                             _nulls("CB", "wstream", "bias", "raw_rgb") + [{"CB": _A + 8}, {"wstream": _A + 8}, {"ldCB": 1060}, {"ldCB": 1048},
+                                                                            {"n_frags": 320}, {"n_blocks": 12}, {"variant": 1, "n_blocks": 14}]
+                             + [c for c in _mats("acts", "act_ld", [128] * 3) if c != {"acts": None}] + _ptrs("bits", 3, False)),
+    "snerf_fcolour_bwd_dt": (_COLOUR_BWD,
+                             _nulls("d_raw_rgb", "wstream", "dB", "ws") + [{"n_frags": 320}, {"wstream": _A + 8}, {"dB": _A + 8}, {"dB_ld": 1028},
+                                                                           {"dB_ld": 1016}, {"ws_floats": "short"}, {"M": _BIG // 12 + 1},
+                                                                           {"d_raw_rgb": _A + 8}]
+                             + _ptrs("bits", 4, True) + _mats("dC", "dC_ld", [128] * 3) + _ptrs("g_bias", 4, False)),
+    "snerf_fchain_bwd_dt": (dict(_CHAIN, net=0, n_frags=1104, bits=[_A] * 9, dz=[_A] * 10, dz_ld=[128] + [256] * 9, g_bias=[_A] * 10),
+                            _CHAIN_BAD + [{"net": 2}, {"net": -1}, {"n_frags": 400}, {"M": _BIG // 16}] + _ptrs("bits", 9, True)
+                            + _mats("dz", "dz_ld", [128] + [256] * 9) + _ptrs("g_bias", 10, False)),
+    "snerf_fchain_bwd_dt proposal": (dict(_CHAIN, net=1, n_frags=400, bits=[_A] * 4, dz=[_A] * 4, dz_ld=[256] * 4, g_bias=[_A] * 4),
+                                     _CHAIN_BAD + [{"n_frags": 1104}, {"M": _BIG // 4}] + _ptrs("bits", 4, True) + _mats("dz", "dz_ld", [256] * 4)
+                                     + _ptrs("g_bias", 4, False)),
+    "snerf_fmlp_zip_chain_bwd": (dict(d_rgb=_A, ld_rgb=3, d_den=_A, ld_den=1, den_cols=1, wstream=_A, n_frags=448, bits=[_A] * 3, dz=[_A] * 5,
+                                      dz_ld=[256, 256, 256, 64, 64], g_bias=[_A] * 4, ws=_A, ws_floats=1 << 40, M=256),
+                                 _nulls("d_rgb", "d_den", "wstream", "ws") + [{"ld_rgb": 2}, {"den_cols": 0}, {"den_cols": 33, "ld_den": 33},
+                                                                              {"den_cols": 4, "ld_den": 3}, {"n_frags": 464}, {"wstream": _A + 8},
+                                                                              {"ws_floats": "short"}, {"M": _BIG}]
+                                 + _ptrs("bits", 3, True) + _mats("dz", "dz_ld", [256, 256, 256, 64, 64]) + _ptrs("g_bias", 4, False)),
+}
+_WS_QUERY = {"snerf_fcolour_bwd_dt": lambda a: ("snerf_fcolour_bwd_ws_floats", a["M"]),
+             "snerf_fchain_bwd_dt": lambda a: ("snerf_fchain_bwd_ws_floats", a["net"], a["M"]),
+             "snerf_fmlp_zip_chain_bwd": lambda a: ("snerf_fmlp_zip_chain_ws_floats", a["M"])}
+
+
+def _fused_status(name, values, dtype):
+    """the raw status of entry `name` for the named argument values (lists become host arrays); dtype None: the twin without the argument"""
+    sig, keep, args = _lib.parse_header()[name], [], []
+    for _, arg in sig:
+        if arg == "stream":
+            args.append(None)
+        elif arg == "dtype":
+            args.append(dtype)
+        elif isinstance(values[arg], list):
+            keep.append(((ctypes.c_long if arg.endswith("_ld") else ctypes.c_void_p) * len(values[arg]))(*values[arg]))
+            args.append(ctypes.addressof(keep[-1]))
+        else:
+            args.append(values[arg])
+    return getattr(_lib.load(), name)(*args)
+
+
+def _changed(name, base, change):
+    values = {k: (list(v) if isinstance(v, list) else v) for k, v in base.items()}
+    for key, v in change.items():
+        if v == "short":
+            v = _lib.query(*_WS_QUERY[name](values)) - 1
+        if key.endswith("]"):
+            arr, i = key[:-1].split("[")
+            values[arr][int(i)] = v
+        else:
+            values[key] = v
+    return values
+
+
+@pytest.mark.parametrize("entry", sorted(_FUSED))
+def test_fused_entries_keep_their_statuses_without_a_gpu(entry):
+    """Every status-returning fused entry of csrc/fmlp.hip: each refusal it has (a dtype the kernels do not have; a null or misaligned pointer
+    in each array; a stride that is no multiple of 8 or is below the width asked for; wrong n_frags / n_blocks; M >= 2^31 where checked; a
+    short workspace) is "bad argument" in both 16-bit flavours and through the bf16 twin, and an empty batch is OK -- with the two precedences:
+    a `_dt` entry refuses a bad dtype before it looks at M, the three zip entries return OK for M <= 0 before they look at anything."""
+    if not os.path.exists(_lib.LIB_PATH):
+        pytest.skip("library not built")
+    name = entry.split()[0]
+    base, refusals = _FUSED[entry]
+    twin = name[:-3] if name.endswith("_dt") else None
+    assert len(refusals) == len({repr(sorted(c.items())) for c in refusals})
+    for change in refusals:
+        values = _changed(name, base, change)
+        for dt in (_BF16, _F16):
+            assert _fused_status(name, values, dt) == 1, (name, dt, change)
+        if twin:
+            assert _fused_status(twin, values, None) == 1, (twin, change)
+    nothing = {k: (None if isinstance(v, list) or v == _A else v) for k, v in base.items()}     # no pointer at all ...
+    for M in (0, -1):
+        for values in (dict(base, M=M), dict(nothing, M=M), dict(nothing, M=M, n_frags=0, n_blocks=0)):    # ... is fine for an empty batch
+            for dt in (_BF16, _F16):
+                assert _fused_status(name, values, dt) == 0, (name, dt, M)
+            if twin:
+                assert _fused_status(twin, values, None) == 0, (twin, M)
+    for dt in (_F32, 3, 4, 5, -1):
+        assert _fused_status(name, base, dt) == 1, (name, dt)
+        assert _fused_status(name, dict(base, M=0), dt) == (1 if twin else 0), (name, dt)       # the precedence of dtype and M
+        assert _fused_status(name, dict(nothing, M=-1), dt) == (1 if twin else 0), (name, dt)
+
+
+def test_fused_workspace_queries_without_a_gpu():
+    """the three workspace queries: 0 for an empty batch (and an unknown net); one / two tiles of 256 rows below any CU count"""
+    if not os.path.exists(_lib.LIB_PATH):
+        pytest.skip("library not built")
+    q = _lib.query
+    assert [q("snerf_fcolour_bwd_ws_floats", M) for M in (-1, 0, 1, 256, 257, 512)] == [0, 0, 1408, 1408, 2816, 2816]
+    assert [q("snerf_fmlp_zip_chain_ws_floats", M) for M in (-1, 0, 1, 256, 257)] == [0, 0, 960, 960, 1856]
+    assert [q("snerf_fchain_bwd_ws_floats", 0, M) for M in (0, 256, 257)] == [0, 2432 + 64, 2 * 2432 + 64]
+    assert [q("snerf_fchain_bwd_ws_floats", 1, M) for M in (0, 256, 257)] == [0, 1024 + 64, 2 * 1024 + 64]
+    assert q("snerf_fchain_bwd_ws_floats", 2, 256) == 0 and q("snerf_fchain_bwd_ws_floats", -1, 256) == 0
+    many = q("snerf_fcolour_bwd_ws_floats", 1 << 24)                  # more tiles than CUs: the grid stops at the CU count
+    assert many % 1408 == 0 and many == q("snerf_fcolour_bwd_ws_floats", 1 << 25)
+    assert q("snerf_fchain_bwd_ws_floats", 1, 1 << 24) == many // 1408 * 1024 + 64
+    assert q("snerf_fmlp_zip_chain_ws_floats", 1 << 24) == many // 1408 * 896 + 64

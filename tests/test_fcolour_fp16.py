@@ -1,6 +1,6 @@
 """The fp16 flavour of the fused colour head (csrc/fmlp.hip: fcolour_fwd_kernel<.., F16>, fcolour_bwd_kernel<F16>): compute="fp16" runs
 cat([bottleneck 1024, view encoding 27]) -> 128 -> 128 -> 128 -> 3 of the mip path's NeRF MLP as ONE launch each way, like compute="bf16".
-"hip": the real kernels; "emulated": the host logic on the CPU models (tests/cpu_ops_emulation_colour_fp16.py).
+"hip": the real kernels; "emulated": the host logic on the CPU models (tests/cpu_ops_emulation.py).
 The per-layer fp16 route (`fused_colour = False`) is the behaviour before these kernels and the partner of every comparison; the bounds are
 the ones tests/test_mlp.py::test_fused_colour_head_matches_per_layer_kernels_and_oracle holds the bf16 flavour to, on its inputs and seeds."""
 import os
@@ -10,7 +10,7 @@ import pytest
 import torch
 
 import test_paths
-from cpu_ops_emulation_colour_fp16 import emulate_ops_colour_fp16
+from cpu_ops_emulation import emulate_ops
 from oracle import common
 from oracle import mip as om
 
@@ -27,7 +27,7 @@ def backend(request):
         yield "hip"
     else:
         DEV = test_paths.DEV = "cpu"
-        with emulate_ops_colour_fp16():
+        with emulate_ops():
             yield "emulated"
     DEV = test_paths.DEV = "cuda"
 

@@ -1,6 +1,6 @@
 """The fp16 flavour of the fused 256-wide networks (csrc/fmlp.hip: fmlp_kernel<.., F16>, fchain_bwd_kernel<.., F16>): compute="fp16" runs the
 classic NeRF 8 x 256 and the mip proposal MLP 4 x 256 as ONE launch per network (inference, training forward, data-gradient chain) like
-compute="bf16" does.  "hip": the real kernels; "emulated": the host logic on the CPU models (tests/cpu_ops_emulation_fp16.py).
+compute="bf16" does.  "hip": the real kernels; "emulated": the host logic on the CPU models (tests/cpu_ops_emulation.py).
 The per-layer fp16 route (`fused = False`) is the behaviour before these kernels and the partner of every comparison; the bounds are
 the ones the bf16 tests of tests/test_mlp.py hold the bf16 flavour to."""
 import os
@@ -10,7 +10,7 @@ import pytest
 import torch
 
 import test_paths
-from cpu_ops_emulation_fp16 import emulate_ops_fp16
+from cpu_ops_emulation import emulate_ops
 from oracle import classic as oc
 from oracle import common
 from oracle import mip as om
@@ -26,7 +26,7 @@ def backend(request):
         yield "hip"
     else:
         DEV = test_paths.DEV = "cpu"
-        with emulate_ops_fp16():
+        with emulate_ops():
             yield "emulated"
     DEV = test_paths.DEV = "cuda"
 
