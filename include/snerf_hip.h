@@ -776,6 +776,31 @@ int snerf_grad_clip_coef(const float* g, long n, float grad_scale, float max_nor
  * (device int); the binned table gradient marks an overflowed feature gradient by a NaN in its first element (snerf_zip_encode_bwd_binned). */
 int snerf_nonfinite_flag(const float* g, long n, int* flag, void* stream);
 
+/* Learned camera pose (pose_refine = True; s-nerf/model/poses.py:6-36 LearnPose, utils/lie_group_helper.py:47-81) applied to a ray
+ * batch: the pose branch of sample_rays (utils/sample_utils.py:421-435).  Row `cam` of the table r [n_cams,3] (axis-angle) / t
+ * [n_cams,3] (NULL = no translation) gives R = I + (sin th / th) K + ((1 - cos th) / th^2) K^2, K = skew(r), th = |r| + 1e-15, formed
+ * in double by every workgroup and rounded once; directions_out = R d, viewdirs_out = R v (fp32, not contracted), origins_out = o + t
+ * (one fp32 add: the reference shifts the origins and does not rotate them).  r = 0 gives R = I exactly: the outputs equal the inputs
+ * bit for bit.  cam_dev: int64 [1] in device memory (a batcher's img_out as it is: no host read), NULL = use cam_host; a device index
+ * outside the table makes the kernel return without a store.  The outputs [n,3] must not overlap the inputs (the backward needs the
+ * untransformed d, v), each other or pose_out.  pose_out [3,4] (nullable) = the transform that was applied.  n = 0 is a no-op; bad arguments (a null required
+ * pointer, n < 0, n_cams < 1, cam_host outside the table, overlap) return 1 before any launch. */
+int snerf_pose_apply(const float* r, const float* t, int n_cams, const long* cam_dev, int cam_host, const float* origins,
+                     const float* directions, const float* viewdirs, long n, float* origins_out, float* directions_out,
+                     float* viewdirs_out, float* pose_out, void* stream);
+/* The ray gradients of a step (g_o, g_d, g_v [n,3] = d loss / d the TRANSFORMED origins / directions / viewdirs) and the untransformed
+ * directions / viewdirs [n,3] reduced to the gradient of table row `cam`: g_t = sum g_o and G[i][j] = sum (g_d[i] d[j] + g_v[i] v[j]),
+ * summed in double in an order that depends on n only (no floating-point atomics: bit-reproducible), then chained through the formula
+ * of snerf_pose_apply as autograd differentiates it (the term through |r| dropped at |r| = 0, torch's subgradient), in double, rounded
+ * once and ADDED into row `cam` of grad_r [n_cams,3] / grad_t [n_cams,3] (either nullable, not both; g_o nullable without grad_t);
+ * other rows are not touched.  ws: >= snerf_pose_grad_ws(n) doubles of device scratch, ws_doubles = its length (short = bad
+ * argument).  Camera index, n = 0 and bad arguments as for snerf_pose_apply.  Linear in the rays: per-slice results add up. */
+int snerf_pose_grad(const float* r, int n_cams, const long* cam_dev, int cam_host, const float* g_o, const float* g_d, const float* g_v,
+                    const float* directions, const float* viewdirs, long n, double* ws, long ws_doubles, float* grad_r, float* grad_t,
+                    void* stream);
+/* doubles of scratch snerf_pose_grad needs for n rays */
+long snerf_pose_grad_ws(long n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,252 @@
+// Learned camera pose on the device (pose_refine = True of both shipped S-NeRF configs): the pose branch of sample_rays
+// (s-nerf/utils/sample_utils.py:421-435) on one row of the LearnPose table (model/poses.py:6-36, utils/lie_group_helper.py:47-81),
+// and the reduction of the step's ray gradients to that row's gradient.
+//
+//   R = I + (sin th / th) K + ((1 - cos th) / th^2) K^2,   K = skew(r),   th = |r| + 1e-15        (lie_group_helper.py:60-70, as written)
+//   directions' = R d,   viewdirs' = R v,   origins' = o + t                                     (the origins are shifted, not rotated)
+//
+// R is formed in double from the fp32 row and rounded once; the per-ray products are separate fp32 ops (this unit is built with
+// -ffp-contract=off).  At r = 0 every entry of K is a zero, so R = I exactly and the transformed rays are the inputs bit for bit.
+// The camera index comes from device memory (int64 [1], the batchers' `img` output: no host read) or from the host; an index outside the
+// table makes the kernels return without a store.
+#include "common.h"
+#include <math.h>
+
+// the [3,3] rotation of an axis-angle row, in double
+__device__ __forceinline__ void pose_rotation(const float* __restrict__ r, double R[9]) {
+  const double x = (double)r[0], y = (double)r[1], z = (double)r[2];
+  const double th = sqrt((x * x + y * y) + z * z) + 1e-15;
+  const double A = sin(th) / th, B = (1.0 - cos(th)) / (th * th);
+  const double K[9] = {0.0, -z, y, z, 0.0, -x, -y, x, 0.0};
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      const double k2 = (K[3 * i] * K[j] + K[3 * i + 1] * K[3 + j]) + K[3 * i + 2] * K[6 + j];
+      R[3 * i + j] = (i == j ? 1.0 : 0.0) + A * K[3 * i + j] + B * k2;
+    }
+}
+
+struct PoseApply {
+  const float *r, *t;               // [n_cams,3]; t nullable
+  int n_cams;
+  const long* cam_dev; int cam_host;
+  const float *o, *d, *v;           // [n,3]
+  long n;
+  float *o_out, *d_out, *v_out;     // [n,3]
+  float* pose_out;                  // [3,4], nullable
+};
+
+__global__ __launch_bounds__(256) void pose_apply_kernel(PoseApply a) {
+  __shared__ float s_R[9], s_t[3];
+  __shared__ int s_ok;
+  if (threadIdx.x == 0) {
+    const long cam = a.cam_dev != nullptr ? a.cam_dev[0] : (long)a.cam_host;
+    s_ok = cam >= 0 && cam < a.n_cams;
+    if (s_ok) {
+      double R[9];
+      pose_rotation(a.r + 3 * cam, R);
+#pragma unroll
+      for (int k = 0; k < 9; ++k) s_R[k] = (float)R[k];
+#pragma unroll
+      for (int k = 0; k < 3; ++k) s_t[k] = a.t != nullptr ? a.t[3 * cam + k] : 0.f;
+      if (blockIdx.x == 0 && a.pose_out != nullptr) {
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+#pragma unroll
+          for (int j = 0; j < 3; ++j) a.pose_out[4 * i + j] = s_R[3 * i + j];
+          a.pose_out[4 * i + 3] = s_t[i];
+        }
+      }
+    }
+  }
+  __syncthreads();
+  if (!s_ok) return;
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= a.n) return;
+  const float d0 = a.d[3 * i], d1 = a.d[3 * i + 1], d2 = a.d[3 * i + 2];
+  const float v0 = a.v[3 * i], v1 = a.v[3 * i + 1], v2 = a.v[3 * i + 2];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const float r0 = s_R[3 * c], r1 = s_R[3 * c + 1], r2 = s_R[3 * c + 2];
+    a.d_out[3 * i + c] = (r0 * d0 + r1 * d1) + r2 * d2;
+    a.v_out[3 * i + c] = (r0 * v0 + r1 * v1) + r2 * v2;
+    a.o_out[3 * i + c] = a.t != nullptr ? a.o[3 * i + c] + s_t[c] : a.o[3 * i + c];
+  }
+}
+
+// do [a, a + la) and [b, b + lb) (bytes) share memory?
+static inline bool pose_overlap(const float* a, uintptr_t la, const float* b, uintptr_t lb) {
+  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+  return a != nullptr && b != nullptr && x < y + lb && y < x + la;
+}
+
+extern "C" int snerf_pose_apply(const float* r, const float* t, int n_cams, const long* cam_dev, int cam_host, const float* origins,
+                                const float* directions, const float* viewdirs, long n, float* origins_out, float* directions_out,
+                                float* viewdirs_out, float* pose_out, void* stream) {
+  if (n == 0) return SNERF_OK;
+  if (n < 0 || n_cams < 1 || r == nullptr) return SNERF_ERR_ARG;
+  if (cam_dev == nullptr && (cam_host < 0 || cam_host >= n_cams)) return SNERF_ERR_ARG;
+  if (origins == nullptr || directions == nullptr || viewdirs == nullptr || origins_out == nullptr || directions_out == nullptr ||
+      viewdirs_out == nullptr)
+    return SNERF_ERR_ARG;
+  // the backward needs the untransformed directions / viewdirs: no output may share memory with an input, nor (a race) with another output
+  const uintptr_t len = (uintptr_t)n * 12;
+  const float* in[3] = {origins, directions, viewdirs};
+  const float* out[3] = {origins_out, directions_out, viewdirs_out};
+  for (int i = 0; i < 3; ++i) {
+    for (int j = 0; j < 3; ++j)
+      if (pose_overlap(out[i], len, in[j], len)) return SNERF_ERR_ARG;
+    for (int j = i + 1; j < 3; ++j)
+      if (pose_overlap(out[i], len, out[j], len)) return SNERF_ERR_ARG;
+    if (pose_overlap(out[i], len, pose_out, 48)) return SNERF_ERR_ARG;
+  }
+  PoseApply a{r, t, n_cams, cam_dev, cam_host, origins, directions, viewdirs, n, origins_out, directions_out, viewdirs_out, pose_out};
+  hipLaunchKernelGGL(pose_apply_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
+  return snerf_check_launch();
+}
+
+// ---------------------------------------------------------------------------
+// Pose gradient.  Twelve sums over the rays, g_t = sum g_o and G[i][j] = sum (g_d[i] d[j] + g_v[i] v[j]) = d loss / d R[i][j] with the
+// UNtransformed d, v, accumulated in double in an order that depends on n only: ray i belongs to thread i mod (256 blocks(n)) and is
+// taken in ascending order, the 64 lanes of a wave fold with shuffles, the 4 waves of a workgroup through LDS in wave order, the
+// workgroups' partials (ws[12 b + k]) in block order by the second launch.  No floating-point atomics: the same bits every run.
+// The second launch (one wave) chains G to the table row in double, as autograd sees the formula above:
+//   dL/dr_k = A <G, E_k> + B <G, E_k K + K E_k> + (A' <G, K> + B' <G, K^2>) r_k / |r|,    E_k = dK/dr_k,
+//   A' = (th cos th - sin th) / th^2,   B' = (th sin th - 2 (1 - cos th)) / th^3,
+// without the last term at |r| = 0 (the norm's subgradient there is 0: training starts there), rounds once to fp32 and ADDS into row
+// `cam` of grad_r / grad_t.
+// ---------------------------------------------------------------------------
+#define POSE_MAX_BLOCKS 256
+static inline int pose_grad_blocks(long n) {
+  const long b = (n + 255) / 256;
+  return b < 1 ? 1 : (b > POSE_MAX_BLOCKS ? POSE_MAX_BLOCKS : (int)b);
+}
+
+extern "C" long snerf_pose_grad_ws(long n) { return n <= 0 ? 0 : 12L * pose_grad_blocks(n); }
+
+struct PoseGrad {
+  const float* r; int n_cams;
+  const long* cam_dev; int cam_host;
+  const float *g_o, *g_d, *g_v, *d, *v;   // [n,3]; g_o nullable (no translation gradient wanted)
+  long n;
+  double* ws;                             // [12 blocks]
+  int blocks;
+  float *grad_r, *grad_t;                 // [n_cams,3], each nullable
+};
+
+__device__ __forceinline__ bool pose_cam(const long* cam_dev, int cam_host, int n_cams, long* cam) {
+  *cam = cam_dev != nullptr ? cam_dev[0] : (long)cam_host;
+  return *cam >= 0 && *cam < n_cams;
+}
+
+__global__ __launch_bounds__(256) void pose_grad_partial_kernel(PoseGrad a) {
+  __shared__ double red[4][12];
+  long cam;
+  if (!pose_cam(a.cam_dev, a.cam_host, a.n_cams, &cam)) return;      // (uniform over the grid)
+  double acc[12];
+#pragma unroll
+  for (int k = 0; k < 12; ++k) acc[k] = 0.0;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < a.n; i += (long)gridDim.x * 256) {
+    double d[3], v[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) { d[c] = (double)a.d[3 * i + c]; v[c] = (double)a.v[3 * i + c]; }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const double gd = (double)a.g_d[3 * i + c], gv = (double)a.g_v[3 * i + c];
+#pragma unroll
+      for (int j = 0; j < 3; ++j) acc[3 * c + j] += gd * d[j] + gv * v[j];
+      if (a.g_o != nullptr) acc[9 + c] += (double)a.g_o[3 * i + c];
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < 12; ++k) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) acc[k] += __shfl_xor(acc[k], o, 64);
+  }
+  if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+    for (int k = 0; k < 12; ++k) red[threadIdx.x >> 6][k] = acc[k];
+  }
+  __syncthreads();
+  if (threadIdx.x < 12) a.ws[12 * (long)blockIdx.x + threadIdx.x] = ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
+}
+
+__device__ __forceinline__ double dot9(const double* a, const double* b) {
+  double s = 0.0;
+#pragma unroll
+  for (int k = 0; k < 9; ++k) s += a[k] * b[k];
+  return s;
+}
+
+__device__ __forceinline__ void mul33(const double* a, const double* b, double* c) {
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) c[3 * i + j] = (a[3 * i] * b[j] + a[3 * i + 1] * b[3 + j]) + a[3 * i + 2] * b[6 + j];
+}
+
+// G [3,3] = d loss / d R and the table row r -> d loss / d r, in double
+__device__ __forceinline__ void pose_chain(const double* G, const float* r, double g[3]) {
+  const double x = (double)r[0], y = (double)r[1], z = (double)r[2];
+  const double rv[3] = {x, y, z};
+  const double nr = sqrt((x * x + y * y) + z * z), th = nr + 1e-15;
+  const double sn = sin(th), cs = cos(th);
+  const double A = sn / th, B = (1.0 - cs) / (th * th);
+  const double dA = (th * cs - sn) / (th * th), dB = (th * sn - 2.0 * (1.0 - cs)) / (th * th * th);
+  const double K[9] = {0.0, -z, y, z, 0.0, -x, -y, x, 0.0};
+  double K2[9];
+  mul33(K, K, K2);
+  const double radial = nr > 0.0 ? dA * dot9(G, K) + dB * dot9(G, K2) : 0.0;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    double E[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    const int p = (k + 1) % 3, q = (k + 2) % 3;           // E_k[q][p] = 1, E_k[p][q] = -1
+    E[3 * q + p] = 1.0; E[3 * p + q] = -1.0;
+    double EK[9], KE[9];
+    mul33(E, K, EK);
+    mul33(K, E, KE);
+#pragma unroll
+    for (int e = 0; e < 9; ++e) EK[e] += KE[e];
+    g[k] = A * dot9(G, E) + B * dot9(G, EK);
+    if (nr > 0.0) g[k] += radial * (rv[k] / nr);
+  }
+}
+
+__global__ __launch_bounds__(64) void pose_grad_finish_kernel(PoseGrad a) {
+  __shared__ double s[12];
+  long cam;
+  if (!pose_cam(a.cam_dev, a.cam_host, a.n_cams, &cam)) return;
+  if (threadIdx.x < 12) {
+    double acc = 0.0;
+    for (int b = 0; b < a.blocks; ++b) acc += a.ws[12 * (long)b + threadIdx.x];
+    s[threadIdx.x] = acc;
+  }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  if (a.grad_t != nullptr) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) a.grad_t[3 * cam + c] += (float)s[9 + c];
+  }
+  if (a.grad_r == nullptr) return;
+  double g[3];
+  pose_chain(s, a.r + 3 * cam, g);
+#pragma unroll
+  for (int k = 0; k < 3; ++k) a.grad_r[3 * cam + k] += (float)g[k];
+}
+
+extern "C" int snerf_pose_grad(const float* r, int n_cams, const long* cam_dev, int cam_host, const float* g_o, const float* g_d,
+                               const float* g_v, const float* directions, const float* viewdirs, long n, double* ws, long ws_doubles,
+                               float* grad_r, float* grad_t, void* stream) {
+  if (n == 0) return SNERF_OK;
+  if (n < 0 || n_cams < 1 || r == nullptr) return SNERF_ERR_ARG;
+  if (cam_dev == nullptr && (cam_host < 0 || cam_host >= n_cams)) return SNERF_ERR_ARG;
+  if (g_d == nullptr || g_v == nullptr || directions == nullptr || viewdirs == nullptr) return SNERF_ERR_ARG;
+  if ((grad_r == nullptr && grad_t == nullptr) || (grad_t != nullptr && g_o == nullptr)) return SNERF_ERR_ARG;
+  const int blocks = pose_grad_blocks(n);
+  if (ws == nullptr || ws_doubles < 12L * blocks) return SNERF_ERR_ARG;
+  PoseGrad a{r, n_cams, cam_dev, cam_host, grad_t != nullptr ? g_o : nullptr, g_d, g_v, directions, viewdirs, n, ws, blocks, grad_r, grad_t};
+  hipLaunchKernelGGL(pose_grad_partial_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(pose_grad_finish_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, a);
+  return snerf_check_launch();
+}

@@ -1448,6 +1448,57 @@ def mip_image_batch(images, depths, poses, intrinsics, near, far, app, extras, i
     return out
 
 
+def _cam_args(cam):
+    """camera index of the pose entries -> (device pointer or None, host index): an int64 [1] device tensor (a batcher's `img`) is read
+    by the kernel, anything else is a python int"""
+    if torch.is_tensor(cam):
+        assert cam.is_cuda and cam.dtype == torch.int64 and cam.numel() == 1, "camera index: a python int or an int64 [1] CUDA tensor"
+        return _p(cam), 0
+    return None, int(cam)
+
+
+def pose_apply(r, t, cam, origins, directions, viewdirs, pose_out=None):
+    """snerf_pose_apply: the pose branch of sample_rays on row `cam` of the LearnPose table r [n_cams,3] / t [n_cams,3] (None = no
+    translation) -> new (origins + t, R directions, R viewdirs); the inputs are left as they are (pose_grad needs them).  `cam`: a python
+    int, or an int64 [1] device tensor that the kernel reads (no host sync).  pose_out: fp32 [3,4], receives the applied transform."""
+    for x in (r, t, origins, directions, viewdirs, pose_out):
+        _f32c(x)
+    n = origins.shape[0]
+    assert r.dim() == 2 and r.shape[1] == 3 and (t is None or t.shape == r.shape)
+    assert tuple(origins.shape) == (n, 3) == tuple(directions.shape) == tuple(viewdirs.shape)
+    assert pose_out is None or pose_out.numel() == 12
+    o2, d2, v2 = torch.empty_like(origins), torch.empty_like(directions), torch.empty_like(viewdirs)
+    cam_dev, cam_host = _cam_args(cam)
+    _lib.call("snerf_pose_apply", _p(r), _p(t), r.shape[0], cam_dev, cam_host, _p(origins), _p(directions), _p(viewdirs), n, _p(o2), _p(d2),
+              _p(v2), _p(pose_out), _stream())
+    return o2, d2, v2
+
+
+def pose_grad_ws(n):
+    """doubles of scratch pose_grad needs for n rays (snerf_pose_grad_ws)"""
+    return int(_lib.query("snerf_pose_grad_ws", int(n)))
+
+
+def pose_grad(r, cam, g_o, g_d, g_v, directions, viewdirs, grad_r, grad_t=None, ws=None):
+    """snerf_pose_grad: d loss / d (transformed origins, directions, viewdirs) [n,3] and the UNtransformed directions / viewdirs reduced
+    to the gradient of table row `cam`, ADDED into grad_r [n_cams,3] (and grad_t, when the translation is trained; either may be None).
+    Deterministic (double sums in a fixed order, no atomics).  ws: fp64 scratch of >= pose_grad_ws(n) elements (allocated when None)."""
+    for x in (r, g_o, g_d, g_v, directions, viewdirs, grad_r, grad_t):
+        _f32c(x)
+    n = g_d.shape[0]
+    assert r.dim() == 2 and r.shape[1] == 3
+    for x in (g_o, g_d, g_v, directions, viewdirs):
+        assert x is None or tuple(x.shape) == (n, 3)
+    for g in (grad_r, grad_t):
+        assert g is None or g.shape == r.shape
+    if ws is None:
+        ws = torch.empty(pose_grad_ws(n), dtype=torch.float64, device=r.device)
+    assert ws.is_cuda and ws.dtype == torch.float64 and ws.is_contiguous()
+    cam_dev, cam_host = _cam_args(cam)
+    _lib.call("snerf_pose_grad", _p(r), r.shape[0], cam_dev, cam_host, _p(g_o), _p(g_d), _p(g_v), _p(directions), _p(viewdirs), n, _p(ws),
+              ws.numel(), _p(grad_r), _p(grad_t), _stream())
+
+
 def zip_ray_batch(images, depths, semantics, masks, pixtocams, camtoworlds, local2global, near, far, border, patch_size, single_image, seed,
                   counter, n, i0, i1, out):
     """snerf_zip_ray_batch: rows [i0, i1) of step counter[0]'s global batch of n rays into the preallocated `out` (dict: origins,

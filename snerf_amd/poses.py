@@ -1,0 +1,81 @@
+"""Learned camera poses (pose_refine = True of both shipped S-NeRF configs): the per-image table of s-nerf/model/poses.py:6-36 with the
+axis-angle map of utils/lie_group_helper.py:47-81.
+
+`LearnPose` keeps the reference's parameter names (`r`, `t`, `init_c2w`), so a `pose/NNNNNN.tar` `model_param` dict loads with
+`load_state_dict`, and its `forward` in torch ops: evaluation and rendering at the refined poses (`c2w @ init_c2w[cam_id]`), and callers
+who keep their own training loop (sample_utils.apply_pose_transform + MipTrainer.step(ray_grads=True)).  Training on the device goes
+through `MipTrainer(pose_net=...)`: the table row is applied to the batch by `snerf_pose_apply` and the ray gradients are reduced to
+the row's gradient by `snerf_pose_grad`; `pose_grad_chain` below is that kernel's host model in float64.
+
+Path C's pose refinement (cal_input_grad, s-nerfpp/zipnerf/train.py:187-224) parameterises the pose differently and is not covered."""
+import torch
+import torch.nn as nn
+
+
+def skew(r):
+    """[3] -> the [3,3] cross-product matrix K with K x = r x x"""
+    z = torch.zeros((), dtype=r.dtype, device=r.device)
+    return torch.stack([torch.stack([z, -r[2], r[1]]), torch.stack([r[2], z, -r[0]]), torch.stack([-r[1], r[0], z])])
+
+
+def rotation(r):
+    """axis-angle [3] -> rotation [3,3], lie_group_helper.Exp as written: I + (sin th / th) K + ((1 - cos th) / th^2) K K with
+    th = |r| + 1e-15 (no small-angle branch: at r = 0 the matrix is I because K is 0)"""
+    K = skew(r)
+    th = r.norm() + 1e-15
+    return torch.eye(3, dtype=r.dtype, device=r.device) + (torch.sin(th) / th) * K + ((1 - torch.cos(th)) / th ** 2) * (K @ K)
+
+
+class LearnPose(nn.Module):
+    def __init__(self, num_cams, learn_R, learn_t, init_c2w=None):
+        """num_cams rows of axis-angle `r` and translation `t` (zeros: the identity), trained when learn_R / learn_t;
+        init_c2w [num_cams,4,4] (optional, never trained): the poses the learned transforms are deltas to"""
+        super().__init__()
+        self.num_cams = int(num_cams)
+        self.init_c2w = None
+        if init_c2w is not None:
+            self.init_c2w = nn.Parameter(torch.as_tensor(init_c2w).detach().clone(), requires_grad=False)
+        self.r = nn.Parameter(torch.zeros(self.num_cams, 3, dtype=torch.float32), requires_grad=bool(learn_R))
+        self.t = nn.Parameter(torch.zeros(self.num_cams, 3, dtype=torch.float32), requires_grad=bool(learn_t))
+
+    def forward(self, cam_id, transform_only=False):
+        """-> [4,4]: the learned transform [R(r) | t] of image cam_id, or (transform_only=False, with init_c2w) that times init_c2w[cam_id]"""
+        r, t = self.r[cam_id], self.t[cam_id]
+        top = torch.cat([rotation(r), t[:, None]], dim=1)
+        c2w = torch.cat([top, torch.tensor([[0, 0, 0, 1]], dtype=top.dtype, device=top.device)], dim=0)
+        if not transform_only and self.init_c2w is not None:
+            c2w = c2w @ self.init_c2w[cam_id]
+        return c2w
+
+
+def pose_grad_chain(r, G):
+    """Host model of snerf_pose_grad's chain, float64: r [3] (one table row), G [3,3] = d loss / d R -> d loss / d r [3], the derivative
+    of `rotation` as autograd takes it:
+        dL/dr_k = A <G, E_k> + B <G, E_k K + K E_k> + (A' <G, K> + B' <G, K K>) r_k / |r|,     E_k = dK/dr_k,
+        A = sin th / th,  B = (1 - cos th) / th^2,  A' = (th cos th - sin th) / th^2,  B' = (th sin th - 2 (1 - cos th)) / th^3,
+    the last term dropped at |r| = 0, where torch's norm has the subgradient 0 (and where training starts)."""
+    r = torch.as_tensor(r, dtype=torch.float64).reshape(3)
+    G = torch.as_tensor(G, dtype=torch.float64).reshape(3, 3)
+    K = skew(r)
+    nr = r.norm()
+    th = nr + 1e-15
+    sn, cs = torch.sin(th), torch.cos(th)
+    A, B = sn / th, (1 - cs) / th ** 2
+    dA, dB = (th * cs - sn) / th ** 2, (th * sn - 2 * (1 - cs)) / th ** 3
+    out = torch.zeros(3, dtype=torch.float64)
+    radial = dA * (G * K).sum() + dB * (G * (K @ K)).sum()
+    for k in range(3):
+        e = torch.zeros(3, dtype=torch.float64)
+        e[k] = 1.0
+        E = skew(e)
+        out[k] = A * (G * E).sum() + B * (G * (E @ K + K @ E)).sum()
+        if float(nr) > 0:
+            out[k] = out[k] + radial * r[k] / nr
+    return out
+
+
+def pose_sums(g_o, g_d, g_v, directions, viewdirs):
+    """the twelve float64 sums snerf_pose_grad forms over a batch -> (G [3,3], g_t [3])"""
+    f = lambda x: torch.as_tensor(x).detach().cpu().to(torch.float64)
+    G = f(g_d).T @ f(directions) + f(g_v).T @ f(viewdirs)
+    return G, f(g_o).sum(0)

@@ -148,13 +148,120 @@ class _AdamState:
             warnings.warn(f"resuming with a static loss scale of {self.loss_scale:g}; the checkpoint was trained with {float(sd['static_loss_scale']):g}")
 
 
+class _PoseAdam:
+    """The learned camera poses of a trainer (poses.LearnPose) and their Adam (utils/model_utils.py:36-42: its own optimiser, lr 1e-4) on
+    the device: the trained parameters -- `r`, then `t` when it is trained -- are moved into one flat fp32 buffer (the module's
+    parameters become views of it, so `pose_net.state_dict()` / `load_state_dict()` keep working), with a gradient buffer and two moment
+    buffers of the same layout; one ops.adam_step covers them.  Dense over the whole table like torch.optim.Adam: a row visited earlier
+    keeps moving on its momentum, a row never visited has m = v = 0 and stays put exactly.  State in the layout of
+    torch.optim.Adam([{'params': [...], 'lr': 1e-4}]).state_dict(): the `optimizer` entry of the reference's pose/NNNNNN.tar.
+    The module must stay where the trainer put it: a later `pose_net.to(...)` / `.float()` that reallocates its parameters would cut
+    them off from the flat buffer (`check_views` raises then, before a step trains a table the module no longer sees)."""
+
+    def __init__(self, pose_net, device, lr, betas, eps):
+        self.net = pose_net
+        pose_net.to(device)
+        self.names = [n for n in ("r", "t") if getattr(pose_net, n).requires_grad]
+        if not self.names:
+            raise ValueError("pose_net: neither r nor t is trained (learn_R / learn_t)")
+        for n in ("r", "t"):
+            p = getattr(pose_net, n)
+            if p.dtype != torch.float32 or tuple(p.shape) != (pose_net.num_cams, 3):
+                raise ValueError(f"pose_net.{n}: fp32 [num_cams, 3] expected")
+        k = 3 * pose_net.num_cams
+        self.flat = torch.zeros(k * len(self.names), dtype=torch.float32, device=device)
+        self.grad, self.m, self.v = torch.zeros_like(self.flat), torch.zeros_like(self.flat), torch.zeros_like(self.flat)
+        self.g = {}
+        for i, n in enumerate(self.names):
+            p = getattr(pose_net, n)
+            view = self.flat[i * k:(i + 1) * k].view(-1, 3)
+            view.copy_(p.data)
+            p.data = view
+            self.g[n] = self.grad[i * k:(i + 1) * k].view(-1, 3)
+        self.lr, self.betas, self.eps, self.t = float(lr), tuple(betas), float(eps), 0
+        self.step_dev = self.lr_dev = None
+        self._ws = None
+
+    def check_views(self):
+        k = 3 * self.net.num_cams
+        for i, n in enumerate(self.names):
+            if getattr(self.net, n).data_ptr() != self.flat.data_ptr() + 4 * i * k:
+                raise RuntimeError(f"pose_net.{n} no longer lives in the trainer's flat pose buffer (was the module moved or cast after MipTrainer took it?)")
+
+    def workspace(self, n):
+        """fp64 scratch of ops.pose_grad for n rays, kept between steps"""
+        need = ops.pose_grad_ws(n)
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = torch.empty(need, dtype=torch.float64, device=self.flat.device)
+        return self._ws
+
+    def snapshot(self):
+        return self.flat.clone(), self.m.clone(), self.v.clone(), self.t
+
+    def restore(self, snap):
+        with torch.no_grad():
+            self.flat.copy_(snap[0]); self.m.copy_(snap[1]); self.v.copy_(snap[2])
+            self.t = snap[3]
+            self.grad.zero_()
+            if self.step_dev is not None:
+                self.step_dev.fill_(self.t)
+
+    def step(self, world, nonfinite):
+        """one fused Adam launch over the trained pose parameters; folds the data-parallel mean and zeroes the gradient buffer"""
+        ops.adam_step(self.flat, self.grad, self.m, self.v, self.lr, self.betas[0], self.betas[1], self.eps, self.t, grad_scale=1.0 / world,
+                      zero_grad=True, nonfinite=nonfinite, step_dev=self.step_dev, lr_dev=self.lr_dev)
+
+    def state_dict(self):
+        k = 3 * self.net.num_cams
+        state = {i: {"step": torch.tensor(float(self.t)), "exp_avg": self.m[i * k:(i + 1) * k].view(-1, 3).clone(),
+                     "exp_avg_sq": self.v[i * k:(i + 1) * k].view(-1, 3).clone()} for i in range(len(self.names))}
+        group = {"lr": self.lr, "betas": tuple(self.betas), "eps": self.eps, "weight_decay": 0, "amsgrad": False, "maximize": False,
+                 "foreach": None, "capturable": False, "differentiable": False, "fused": None, "params": list(range(len(self.names)))}
+        return {"state": state, "param_groups": [group]}
+
+    def load_state_dict(self, sd):
+        k = 3 * self.net.num_cams
+        groups = sd["param_groups"]
+        order = [i for g in groups for i in g["params"]]
+        if len(groups) != 1 or len(order) != len(self.names):
+            raise ValueError(f"pose optimizer state: one param group over {len(self.names)} parameters ({', '.join(self.names)}) expected")
+        g0 = groups[0]
+        if float(g0.get("weight_decay", 0) or 0) != 0 or g0.get("amsgrad", False):
+            raise ValueError("the fused Adam launch has no weight decay / amsgrad")
+        new_betas, new_eps = tuple(float(b) for b in g0["betas"]), float(g0["eps"])
+        if self.step_dev is not None and (new_betas != tuple(float(b) for b in self.betas) or new_eps != float(self.eps)):
+            raise ValueError("load_state_dict after capture(): the checkpoint's betas / eps differ from the captured step's -- load before capturing")
+        steps = set()
+        with torch.no_grad():
+            for i, pos in enumerate(order):
+                st = sd["state"].get(pos, sd["state"].get(str(pos)))
+                if st is None:                              # (the saved optimizer never stepped)
+                    self.m[i * k:(i + 1) * k].zero_(); self.v[i * k:(i + 1) * k].zero_()
+                    continue
+                if tuple(st["exp_avg"].shape) != (self.net.num_cams, 3):
+                    raise ValueError(f"pose optimizer state of {self.names[i]}: shape {tuple(st['exp_avg'].shape)}, the table has {(self.net.num_cams, 3)}")
+                self.m[i * k:(i + 1) * k].copy_(st["exp_avg"].reshape(-1).to(self.m.device, torch.float32))
+                self.v[i * k:(i + 1) * k].copy_(st["exp_avg_sq"].reshape(-1).to(self.v.device, torch.float32))
+                steps.add(int(float(st["step"])))
+        if len(steps) > 1:
+            raise ValueError(f"one Adam launch covers the pose parameters: the saved parameters disagree on the step count ({sorted(steps)})")
+        self.t = steps.pop() if steps else 0
+        self.lr, self.betas, self.eps = float(g0["lr"]), new_betas, new_eps
+        if self.step_dev is not None:
+            self.step_dev.fill_(self.t)
+
+
 class MipTrainer(_AdamState):
     def __init__(self, model, lr=5e-4, betas=(0.9, 0.999), eps=1e-8, depth_lambda=0.2, coarse_depth_mult=0.2,
                  proposal_loss=False, proposal_lambda=0.05, disparity_depth=True, process_group=None,
-                 nonfinite="zero", grad_max_val=0.0, grad_max_norm=0.0, exchange_when_single=False):
+                 nonfinite="zero", grad_max_val=0.0, grad_max_norm=0.0, exchange_when_single=False,
+                 pose_net=None, pose_lr=1e-4, pose_betas=(0.9, 0.999), pose_eps=1e-8):
         """`nonfinite` / `grad_max_val` / `grad_max_norm`: gradient hygiene folded into the Adam launch (ops.adam_step).  The s-nerf
         reference has none (train.py:212-215 drops into pdb on a failing backward); the default "zero" keeps one NaN / Inf gradient
-        (1/(depth + eps), a bf16 overflow) from poisoning m, v and the parameters of the whole arena on every rank.  "keep" = plain Adam."""
+        (1/(depth + eps), a bf16 overflow) from poisoning m, v and the parameters of the whole arena on every rank.  "keep" = plain Adam.
+        `pose_net` (poses.LearnPose; configs: pose_refine = True): the learned camera poses are trained inside the step -- see `step`'s
+        `img_i`.  The module is moved to the model's device and its trained parameters into one flat buffer (`self.pose`, _PoseAdam);
+        `pose_lr` / `pose_betas` / `pose_eps`: their own Adam (utils/model_utils.py:36-42: lr 1e-4, no schedule)."""
         self.model = model
         self.lr, self.betas, self.eps = lr, betas, eps
         self.nonfinite, self.grad_max_val, self.grad_max_norm = nonfinite, float(grad_max_val), float(grad_max_norm)
@@ -169,11 +276,30 @@ class MipTrainer(_AdamState):
         self.single_rank_exchange = bool(exchange_when_single) and dist.is_available() and dist.is_initialized()
         self._step_dev = self._lr_dev = self._graph = None
         a.grad.zero_()
+        self.pose = None if pose_net is None else _PoseAdam(pose_net, a.flat.device, pose_lr, pose_betas, pose_eps)
 
     def broadcast_parameters(self, src=0):
         if self.world > 1:
             dist.broadcast(self.model.arena.flat, src=src, group=self.pg)
             self.model.arena.bump()
+            if self.pose is not None:                    # the whole table: an untrained t (learn_t=False) is applied to the rays all the same
+                for p in (self.pose.net.r, self.pose.net.t):
+                    dist.broadcast(p.data, src=src, group=self.pg)
+
+    def pose_state_dict(self):
+        """the pose optimiser's state in torch.optim.Adam's layout (the `optimizer` entry of the reference's pose/NNNNNN.tar; the table
+        itself is `pose_net.state_dict()`, its `model_param` entry)"""
+        return self.pose.state_dict()
+
+    def load_pose_state_dict(self, sd):
+        self.pose.load_state_dict(sd)
+
+    def _pose_adam(self):
+        """the pose table's Adam step (after the model's): the rank's pose gradients are summed like the model's, 1 / world folded in"""
+        if self.world > 1:
+            dist.all_reduce(self.pose.grad, op=dist.ReduceOp.SUM, group=self.pg)
+        self.pose.t += 1
+        self.pose.step(self.world, self.nonfinite)
 
     def _adam(self):
         """One fused Adam launch over the flat arena; folds the data-parallel mean, the gradient hygiene and zero_grad."""
@@ -197,19 +323,29 @@ class MipTrainer(_AdamState):
         self.last_losses = out[:4]                               # {#valid depth rays, rgb, depth, proposal}: stays on the device
         return out[4], (g_dist0, None, g_w0, g_rgb1, g_dist1, None, None)      # out[4]: their sum, formed by the same launch
 
-    def step(self, rays, target_rgb, target_depth=None, conf=None, randomized=True, s_rand=None, u=None, ray_grads=False, viewc=None):
+    def step(self, rays, target_rgb, target_depth=None, conf=None, randomized=True, s_rand=None, u=None, ray_grads=False, viewc=None, img_i=None):
         """`ray_grads=True` (pose refinement, configs: pose_refine = True): `last_ray_grads` = d loss / d (origins, directions, viewdirs)
         of this rank's rays, for the caller's pose optimiser (`rays.origins.backward(g_o)` etc. chains them into the pose parameters).
         `viewc` (fn = 0 models, the view-centred warp): the warp centre the reference passes to every forward (train.py:36,112); a model
-        built with fn = 0 refuses to step until a centre has been given here or through `model.set_viewc`."""
+        built with fn = 0 refuses to step until a centre has been given here or through `model.set_viewc`.
+        With a `pose_net`: `rays` are the UNtransformed rays of image `img_i` (a python int, or the batcher's int64 [1] device tensor,
+        which is never read on the host); the step applies row img_i of the pose table to them (ops.pose_apply: sample_rays' pose
+        branch), runs forward, loss tail and backward with ray gradients (`last_ray_grads` as above), reduces those to the row's gradient
+        (ops.pose_grad) and follows the model's Adam with the pose table's -- no torch op, autograd graph or host sync in between."""
         self._set_viewc(viewc)
+        if self.pose is not None and img_i is None:
+            raise ValueError("MipTrainer with a pose_net: step() needs img_i= (the image the rays belong to)")
+        if self.pose is None and img_i is not None:
+            raise ValueError("MipTrainer: img_i= given without a pose_net")
         ex = _GradExchange(self.model.arena, self.world, self.pg, self.single_rank_exchange)
         # every block of the gradient arena goes on the wire as soon as the backward pass has finished it (heads, then trunk layer by
         # trunk layer, then the proposal network): the collectives run under the remaining backward kernels
-        loss, outs = self._forward_backward(rays, target_rgb, target_depth, conf, randomized, s_rand, u, ray_grads, ex)
+        loss, outs = self._forward_backward(rays, target_rgb, target_depth, conf, randomized, s_rand, u, ray_grads, ex, img_i)
         ex.finish()
         self.t += 1
         self._adam()                                      # graph mode: step count and lr live on the device (capture / replay below)
+        if self.pose is not None:
+            self._pose_adam()
         return loss, outs
 
     def _set_viewc(self, viewc):
@@ -219,21 +355,34 @@ class MipTrainer(_AdamState):
         elif m.fn == 0 and not getattr(m, "_viewc_given", False):
             raise ValueError("MipTrainer: the model warps around a view centre (fn = 0): pass viewc= (train.py:36,112) or call model.set_viewc first")
 
-    def _forward_backward(self, rays, target_rgb, target_depth, conf, randomized, s_rand, u, ray_grads, on_done):
-        """draws, both levels forward, the fused loss tail, the backward pass into the gradient arena (no exchange, no optimiser)"""
+    def _forward_backward(self, rays, target_rgb, target_depth, conf, randomized, s_rand, u, ray_grads, on_done, img_i=None):
+        """draws, both levels forward, the fused loss tail, the backward pass into the gradient arena (no exchange, no optimiser); with a
+        pose table: its row applied to the rays in front, the ray gradients reduced into its gradient buffer behind"""
         m = self.model
         dev = m.arena.flat.device
         n = rays.origins.shape[0]
+        ps = self.pose
+        if ps is not None:
+            ps.check_views()
+            f32 = lambda x: x.detach().to(dev, torch.float32).contiguous()
+            o, d, v = f32(rays.origins), f32(rays.directions), f32(rays.viewdirs)
+            cam = img_i.to(dev) if torch.is_tensor(img_i) else int(img_i)
+            rays = rays._replace(**dict(zip(("origins", "directions", "viewdirs"), ops.pose_apply(ps.net.r.data, ps.net.t.data, cam, o, d, v))))
+            ray_grads = True
         ds_rand, du, noise0, noise1 = m._draws(n, randomized, dev)
         s_rand = ds_rand if s_rand is None else s_rand
         u = du if u is None else u
         outs, ctx = m._run(rays, True, False, s_rand, u.contiguous(), noise0, noise1)
         loss, g = self.loss_and_grads(outs, target_rgb, target_depth, conf)
         self.last_ray_grads = m._backward(ctx, *g, on_done=on_done, ray_grads=ray_grads)
+        if ps is not None:
+            g_o, g_d, g_v = self.last_ray_grads
+            ops.pose_grad(ps.net.r.data, cam, g_o, g_d, g_v, d, v, ps.g.get("r"), ps.g.get("t"), ws=ps.workspace(n))
         return loss, outs
 
     # ---- hipGraph capture of the whole step --------------------------------------------------------------------------------------
-    def capture(self, rays, target_rgb, target_depth=None, conf=None, randomized=True, warmup=3, viewc=None, batcher=None, conf_extra=None):
+    def capture(self, rays, target_rgb, target_depth=None, conf=None, randomized=True, warmup=3, viewc=None, batcher=None, conf_extra=None,
+                img_i=None):
         """Capture one full training step (draws, forward, loss tail, backward, Adam: ~130 launches) in a hipGraph over the GIVEN tensors;
         afterwards `replay()` runs a step with one graph launch -- the caller refreshes the batch by copying into those tensors
         (`rays.origins.copy_(...)` etc.).  Worth it when the step is launch-bound: at 512 rays per GPU (the 8-GPU split of the
@@ -254,14 +403,24 @@ class MipTrainer(_AdamState):
         rays and targets are the batcher's buffers (`rays` / `target_rgb` / `target_depth` are ignored; `conf_extra` = index of the
         batcher's extra map that serves as the per-ray confidence, or None): every `replay()` trains on a fresh batch, the k-th on the
         batch an eager batcher draws at step s0 + k (s0 = the batcher's step at this call).  The warm-up restores the batcher's counter
-        like the parameters.  `self.batch` holds the captured batch tensors (rays, target_rgb, target_depth, sel_coords, img_i, extras)."""
+        like the parameters.  `self.batch` holds the captured batch tensors (rays, target_rgb, target_depth, sel_coords, img_i, extras).
+
+        With a `pose_net` the captured step is the draw, ops.pose_apply fed by the batch's `img` tensor (without a batcher: `img_i`, an
+        int64 [1] device tensor the caller refreshes like the rays), forward, backward with ray gradients, ops.pose_grad and both Adams
+        (world > 1: both Adams and the two all-reduces follow the graph); the pose table, its moments and step count are snapshotted and
+        restored around the warm-up like the model's."""
         self._set_viewc(viewc)                           # (fn = 0: the centre is a kernel argument, i.e. a constant of the captured graph)
         a = self.model.arena
         dev = a.flat.device
         snap = (a.flat.clone(), self.m.clone(), self.v.clone(), self.t)
+        ps = self.pose
+        p_snap = None if ps is None else ps.snapshot()
         if self.world == 1:
             self._step_dev = torch.tensor([self.t], dtype=torch.int32, device=dev)
             self._lr_dev = torch.tensor([self.lr], dtype=torch.float32, device=dev)
+            if ps is not None:
+                ps.step_dev = torch.tensor([ps.t], dtype=torch.int32, device=dev)
+                ps.lr_dev = torch.tensor([ps.lr], dtype=torch.float32, device=dev)
         self._batcher = batcher
         if batcher is not None:
             buf = batcher.buffers()
@@ -269,6 +428,9 @@ class MipTrainer(_AdamState):
             rays, target_rgb, target_depth, _, _, extras = self.batch
             conf = None if conf_extra is None else extras[conf_extra]
             b_snap = (batcher.counter.clone(), batcher.step)
+            img_i = self.batch[4] if ps is not None else None
+        if ps is not None and not (torch.is_tensor(img_i) and img_i.is_cuda):
+            raise ValueError("capture() with a pose_net: img_i= must be an int64 [1] device tensor (a python int would be frozen into the graph)")
         args = (rays, target_rgb, target_depth, conf)
 
         def draw():
@@ -279,7 +441,7 @@ class MipTrainer(_AdamState):
         with torch.cuda.stream(side):                    # warm-up on a side stream
             for _ in range(warmup):
                 draw()
-                self.step(*args, randomized=randomized)
+                self.step(*args, randomized=randomized, img_i=img_i)
         torch.cuda.current_stream(dev).wait_stream(side)
         with torch.no_grad():
             a.flat.copy_(snap[0]); self.m.copy_(snap[1]); self.v.copy_(snap[2])
@@ -289,18 +451,22 @@ class MipTrainer(_AdamState):
             a.grad.zero_()
             if batcher is not None:                      # capturing uses up no draws
                 batcher.counter.copy_(b_snap[0])
+        if ps is not None:
+            ps.restore(p_snap)
         a.bump()
         self._graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self._graph):
             draw()
             if self.world == 1:
-                self._graph_loss, self._graph_outs = self.step(*args, randomized=randomized)
+                self._graph_loss, self._graph_outs = self.step(*args, randomized=randomized, img_i=img_i)
             else:
-                self._graph_loss, self._graph_outs = self._forward_backward(*args, randomized, None, None, False, None)
+                self._graph_loss, self._graph_outs = self._forward_backward(*args, randomized, None, None, False, None, img_i)
         if batcher is not None:
             batcher._step = b_snap[1]
         if self.world == 1:
             self.t -= 1                                  # capturing records the step, it does not run it
+            if ps is not None:
+                ps.t -= 1
         return self._graph_loss
 
     def replay(self):
@@ -309,6 +475,9 @@ class MipTrainer(_AdamState):
             self._batcher.advance_host(1)                # the graph's first node drew the batch and advanced the device counter
         if self.world == 1:
             self._lr_dev.fill_(self.lr)                  # the graph reads the learning rate from the device
+            if self.pose is not None:
+                self.pose.lr_dev.fill_(self.pose.lr)
+                self.pose.t += 1
             self._graph.replay()
             self.t += 1
             return self._graph_loss, self._graph_outs
@@ -317,6 +486,8 @@ class MipTrainer(_AdamState):
         ex.finish()                                      # one all-reduce of the flat gradient arena
         self.t += 1
         self._adam()
+        if self.pose is not None:
+            self._pose_adam()
         return self._graph_loss, self._graph_outs
 
 
