@@ -20,6 +20,7 @@
 #include "common.h"
 #include <cstdlib>
 #include <type_traits>
+#include <utility>
 
 #define ACT_NONE 0
 #define ACT_RELU 1
@@ -90,6 +91,12 @@ template <bool F16> __device__ __forceinline__ void mma32t(f32x16& acc, const bf
   else acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, acc, 0, 0, 0);
 }
 template <bool F16> __device__ __forceinline__ void mma32t(f32x16& acc, const f32x4& a, const f32x4& b) { mma32(acc, a, b); }
+// the 16 x 16 x 32 shape of the same 16-bit MFMA (gemm_tn8_kernel's MSHAPE = 16): lane l holds A[row l & 15][k = 8 (l >> 4) + j],
+// B[k = 8 (l >> 4) + j][col l & 15] and D[row 4 (l >> 4) + reg][col l & 15]
+template <bool F16> __device__ __forceinline__ void mma16t(f32x4& acc, const bf16x8& a, const bf16x8& b) {
+  if constexpr (F16) acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), acc, 0, 0, 0);
+  else acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, acc, 0, 0, 0);
+}
 // The CORRECTION tile of the fp16 + fp8 split mode (GemmNT::split == 2): 32 x 32 x 64 e4m3 products per instruction -- two 16-byte fragments
 // per operand, read exactly like two bf16 fragments (the byte -> k map inside a lane is the same for both operands, so it does not matter)
 // -- on the block-scaled MFMA with constant E8M0 scale bytes 116 = 2^-11 on both sides: the operands were scaled by 2^22 in total.
@@ -1680,9 +1687,29 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(GemmTN p) {
 // with fp32 atomics at the end; rows past the slice read as zeros through the buffer descriptor.
 //     dZ half h, local column lc  <->  tile column (lc>>6)*128 + h*64 + (lc&63)     (wave row wr = lc>>6)
 //     X  half g, local column lc  <->  tile column (lc>>5)*64  + g*32 + (lc&31)     (wave col wc = lc>>5)
+//
+// MSHAPE = 16 (plain 16-bit operands only): the same wave tile, registers and phases on v_mfma_f32_16x16x32 -- a k-tile is two reduction steps
+// of 32 rows; per half a wave holds 4 blocks x 2 steps of dZ fragments and 2 x 2 of X (16 columns each), the accumulators are 8 x 4 blocks of
+// f32x4, every phase issues 16 MFMAs, and a dZ fragment is replaced in place after its two MFMAs.  A 32-lane half of a transposing read takes
+// the SAME 16 columns of two 4-row blocks 8 rows apart there, so the LDS image also separates those: chunk c of row r sits at
+// c ^ (4 (r & 3) | 2 ((r >> 3) & 1)).  Row bit 2 stays out of it: the second read of a fragment (+4 rows) is offset:1024 from the first in
+// every lane (tools/probes/tn8_lds_bank_check.py evaluates the bank rule for both flavours and replays every read on a numbered tile).
 // ---------------------------------------------------------------------------
-template <bool SPLIT, bool F16 = false>
+template <int... I, class F> __device__ __forceinline__ void static_for_seq(std::integer_sequence<int, I...>, F&& f) {
+  (f(std::integral_constant<int, I>{}), ...);
+}
+template <int N, class F> __device__ __forceinline__ void static_for(F&& f) { static_for_seq(std::make_integer_sequence<int, N>{}, f); }
+// one MFMA fragment by two transposing reads at compile-time offsets from one address register (inline asm: see lds_frag in gemm_tn8_kernel)
+template <int OFF> __device__ __forceinline__ bf16x8 lds_frag_tr(unsigned addr) {
+  static_assert(OFF >= 0 && OFF + 1024 < 65536, "ds offset field");
+  bf16x4 lo, hi;
+  asm volatile("ds_read_b64_tr_b16 %0, %2 offset:%3\n\tds_read_b64_tr_b16 %1, %2 offset:%4" : "=&v"(lo), "=&v"(hi) : "v"(addr), "n"(OFF), "n"(OFF + 1024));
+  return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+}
+
+template <bool SPLIT, bool F16 = false, int MSHAPE = 32>
 __global__ __launch_bounds__(512) void gemm_tn8_kernel(GemmTN p) {
+  static_assert(MSHAPE == 32 || (MSHAPE == 16 && !SPLIT), "the split-bf16 instantiation stays on 32x32x16");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   typedef __bf16 T;
   typedef __attribute__((address_space(3))) bf16x4* lds_b4;
@@ -1709,7 +1736,7 @@ __global__ __launch_bounds__(512) void gemm_tn8_kernel(GemmTN p) {
 
   // ---- staging stream: wave w owns pieces 2w, 2w+1 (4 rows x 256 B) of every half-tile -------------------------------
   const int lrow = lane >> 4, lch = lane & 15;
-  const int lc = (lch ^ (4 * lrow)) * 8;               // logical column of this lane's 16 bytes inside the half
+  const int lc = (lch ^ (MSHAPE == 16 ? 4 * lrow | ((wave & 1) << 1) : 4 * lrow)) * 8;   // logical column of this lane's 16 bytes inside the half
   // split-bf16 operands ([hi 64 | lo 64] per 128 physical columns): X's 32-column blocks are dealt so that EVERY wave column gets one hi
   // block (half 0) and the lo block of the same logical columns (half 1) -- tile column (wc, g, c) <-> physical column
   // (wc >> 1) * 128 + g * 64 + (wc & 1) * 32 + c -- while dZ's halves are hi / lo by themselves (half h = 64 columns).  The quadrant
@@ -1742,6 +1769,147 @@ __global__ __launch_bounds__(512) void gemm_tn8_kernel(GemmTN p) {
       __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_ptr_t)(dst + 1024), 16, xrel[1] + (which - 2) * xhalf, 0, 0, 0);
     }
   };
+
+  // One barrier per phase.  Wave row 1 runs [load section, MFMA section], wave row 0 [MFMA section, load section] between two
+  // barriers, so on every SIMD one wave stages while the other multiplies, and they swap roles mid-interval without meeting.
+  // A load section = stage this phase's half, vmcnt(10) (five halves in flight), lgkmcnt(0).  Ordering: a half retired in the
+  // load section of phase j (by the end of interval j for both rows) is first read in MFMA section j+1; a half last read in
+  // MFMA section p is restaged in load section p+2: row 1's reads (end of interval p) are retired by its lgkmcnt(0) at the
+  // start of interval p+1, row 0's (start of interval p) by its lgkmcnt(0) at the end of interval p -- a barrier lies between
+  // either and every DMA of phase p+2.
+  auto wait_load = [&]() __attribute__((always_inline)) {
+    asm volatile("s_waitcnt vmcnt(10)" ::: "memory");
+    __builtin_amdgcn_s_waitcnt(0xC07F);
+    __builtin_amdgcn_sched_barrier(0);
+  };
+  auto end_phase = [&]() __attribute__((always_inline)) {
+    __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_sched_barrier(0);
+  };
+
+  // k-tiles 0 and 1 of the stream (tiles past the slice read zeros), the first of them landed
+  auto stage_prologue = [&]() __attribute__((always_inline)) {
+    stage(0, 2); stage(0, 0); stage(0, 3); stage(0, 1);
+    ++s_kt;
+    stage(1, 3); stage(1, 0); stage(1, 2); stage(1, 1);
+    ++s_kt;
+    asm volatile("s_waitcnt vmcnt(10)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+  };
+
+  if constexpr (MSHAPE == 16) {                          // (a whole instantiation, not a branch; the 32 x 32 x 16 flavour follows it)
+    // ---- 16 x 16 x 32 flavour.  Fragment addresses: 16-lane group g4 takes reduction rows 8 g4 .. 8 g4 + 7 of a 32-row step, every group the same
+    // 16 columns; byte offset of (half `which`, step ks, second read) = which * HALF + ks * 8192 (+ 1024) goes into the instruction, the buffer
+    // (db * 4 * HALF) into the address register
+    const int g4 = lane >> 4, pl = lane & 15, prow = pl >> 2, fsub = (pl & 1) << 3;
+    const unsigned lds0 = (unsigned)(size_t)smem;
+    const int fbase = (8 * g4 + prow) * 256 + fsub, fxor = (prow << 2) | ((g4 & 1) << 1);
+    unsigned zb[2][4], xb[2][2];
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+      zb[0][b] = lds0 + fbase + (((wr * 8 + b * 2 + ((pl & 3) >> 1)) ^ fxor) << 4);
+      zb[1][b] = zb[0][b] + 4 * HALF;
+    }
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+      xb[0][c] = lds0 + fbase + (((wc * 4 + c * 2 + ((pl & 3) >> 1)) ^ fxor) << 4);
+      xb[1][c] = xb[0][c] + 4 * HALF;
+    }
+    bf16x8 zF[4][2], xF[2][2][2];                        // dZ [block][step]; X [half][block][step]
+    f32x4 acc16[8][4];                                   // [n block 4 h + b][k block 2 g + c] of the wave tile
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) acc16[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    stage_prologue();
+    static_for<2>([&](auto ks_t) __attribute__((always_inline)) {
+      constexpr int ks = decltype(ks_t)::value;
+      static_for<4>([&](auto b_t) __attribute__((always_inline)) {
+        constexpr int b = decltype(b_t)::value;
+        zF[b][ks] = lds_frag_tr<ks * 8192>(zb[0][b]);
+      });
+      static_for<2>([&](auto c_t) __attribute__((always_inline)) {
+        constexpr int c = decltype(c_t)::value;
+        xF[0][c][ks] = lds_frag_tr<2 * HALF + ks * 8192>(xb[0][c]);
+      });
+    });
+    __builtin_amdgcn_s_waitcnt(0xC07F);
+    __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_s_barrier();
+
+    auto ktile = [&](auto db_tag) __attribute__((always_inline)) {
+      constexpr int db = decltype(db_tag)::value;
+      constexpr int F = db, S = 1 - db;
+      // P1: Z0 x X_F; fetch X_S
+      if (wr == 1) { stage(db, 2 + F); wait_load(); }
+      static_for<4>([&](auto q_t) __attribute__((always_inline)) {
+        constexpr int ks = decltype(q_t)::value >> 1, c = decltype(q_t)::value & 1;
+        xF[S][c][ks] = lds_frag_tr<(2 + S) * HALF + ks * 8192>(xb[db][c]);
+#pragma unroll
+        for (int b = 0; b < 4; ++b) mma16t<F16>(acc16[b][2 * F + c], zF[b][ks], xF[F][c][ks]);
+        __builtin_amdgcn_sched_barrier(0);
+      });
+      if (wr == 0) { stage(db, 2 + F); wait_load(); }
+      end_phase();
+      // P2: Z0 x X_S; Z0 fragments replaced by Z1 in place, each after its two MFMAs
+      if (wr == 1) { stage(db, 0); wait_load(); }
+      static_for<8>([&](auto q_t) __attribute__((always_inline)) {
+        constexpr int ks = decltype(q_t)::value >> 2, b = decltype(q_t)::value & 3;
+        mma16t<F16>(acc16[b][2 * S], zF[b][ks], xF[S][0][ks]);
+        mma16t<F16>(acc16[b][2 * S + 1], zF[b][ks], xF[S][1][ks]);
+        zF[b][ks] = lds_frag_tr<HALF + ks * 8192>(zb[db][b]);
+        __builtin_amdgcn_sched_barrier(0);
+      });
+      if (wr == 0) { stage(db, 0); wait_load(); }
+      end_phase();
+      // P3: Z1 x X_S; X_S replaced by the first X half of the next k-tile
+      if (wr == 1) { stage(db, 2 + S); wait_load(); }
+      static_for<4>([&](auto q_t) __attribute__((always_inline)) {
+        constexpr int ks = decltype(q_t)::value >> 1, c = decltype(q_t)::value & 1;
+#pragma unroll
+        for (int b = 0; b < 4; ++b) mma16t<F16>(acc16[4 + b][2 * S + c], zF[b][ks], xF[S][c][ks]);
+        xF[S][c][ks] = lds_frag_tr<(2 + S) * HALF + ks * 8192>(xb[db ^ 1][c]);
+        __builtin_amdgcn_sched_barrier(0);
+      });
+      if (wr == 0) { stage(db, 2 + S); wait_load(); }
+      end_phase();
+      // P4: Z1 x X_F; Z1 replaced by Z0 of the next k-tile
+      if (wr == 1) { stage(db, 1); ++s_kt; wait_load(); }
+      static_for<8>([&](auto q_t) __attribute__((always_inline)) {
+        constexpr int ks = decltype(q_t)::value >> 2, b = decltype(q_t)::value & 3;
+        mma16t<F16>(acc16[4 + b][2 * F], zF[b][ks], xF[F][0][ks]);
+        mma16t<F16>(acc16[4 + b][2 * F + 1], zF[b][ks], xF[F][1][ks]);
+        zF[b][ks] = lds_frag_tr<ks * 8192>(zb[db ^ 1][b]);
+        __builtin_amdgcn_sched_barrier(0);
+      });
+      if (wr == 0) { stage(db, 1); ++s_kt; wait_load(); }
+      end_phase();
+    };
+    for (int t = 0; t < KT; t += 2) {
+      ktile(std::integral_constant<int, 0>{});
+      if (t + 1 < KT) ktile(std::integral_constant<int, 1>{});
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+
+    // D[i' = n][j' = k]: j' = lane&15, i' = 4*(lane>>4) + r; acc16[i][j]: 16-row n block i, 16-column k block j of the wave tile
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int k = k0 + wc * 64 + j * 16 + (lane & 15);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int n = n0 + wr * 128 + i * 16 + 4 * (lane >> 4) + r;
+          if (n < p.n_valid && k < p.k_valid) {
+            if (p.part != nullptr) p.part[(long)chunk * p.part_stride + (long)n * p.part_ld + k] = acc16[i][j][r];
+            else atomicAdd(p.dW + (long)n * p.ldw + k, acc16[i][j][r]);
+          }
+        }
+      }
+    return;                                            // compile-time: every lane of this instantiation ends here, none earlier
+  }
 
   // ---- fragments: per 16-lane group, lane pl supplies the address of 4 consecutive bf16 of row (pl>>2) of a 4-row block and
   // receives column pl of that 4 x 16 block; two reads (rows +0..3, +4..7) make the 8 reduction indices of an MFMA operand
@@ -1778,31 +1946,8 @@ __global__ __launch_bounds__(512) void gemm_tn8_kernel(GemmTN p) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
-  // One barrier per phase.  Wave row 1 runs [load section, MFMA section], wave row 0 [MFMA section, load section] between two
-  // barriers, so on every SIMD one wave stages while the other multiplies, and they swap roles mid-interval without meeting.
-  // A load section = stage this phase's half, vmcnt(10) (five halves in flight), lgkmcnt(0).  Ordering: a half retired in the
-  // load section of phase j (by the end of interval j for both rows) is first read in MFMA section j+1; a half last read in
-  // MFMA section p is restaged in load section p+2: row 1's reads (end of interval p) are retired by its lgkmcnt(0) at the
-  // start of interval p+1, row 0's (start of interval p) by its lgkmcnt(0) at the end of interval p -- a barrier lies between
-  // either and every DMA of phase p+2.
-  auto wait_load = [&]() __attribute__((always_inline)) {
-    asm volatile("s_waitcnt vmcnt(10)" ::: "memory");
-    __builtin_amdgcn_s_waitcnt(0xC07F);
-    __builtin_amdgcn_sched_barrier(0);
-  };
-  auto end_phase = [&]() __attribute__((always_inline)) {
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-  };
-
   // ---- prologue: k-tiles 0 and 1 (tiles past the slice read zeros) ------------------------------------------------------
-  stage(0, 2); stage(0, 0); stage(0, 3); stage(0, 1);
-  ++s_kt;
-  stage(1, 3); stage(1, 0); stage(1, 2); stage(1, 1);
-  ++s_kt;
-  asm volatile("s_waitcnt vmcnt(10)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
+  stage_prologue();
 #pragma unroll
   for (int ks = 0; ks < 4; ++ks) {
     aF[0][ks] = lds_a(0, 0, 0, ks);
@@ -1961,13 +2106,32 @@ struct TnPlan {
   int m_chunk;        // rows per slice
   int part_ld;        // row length of a partial tile image (K rounded up to the tile)
   long part_stride;   // floats per slice in the deterministic workspace
+  int mshape;         // 256 x 256 kernel: 32 = v_mfma_f32_32x32x16, 16 = v_mfma_f32_16x16x32 (gemm_tn8_kernel's MSHAPE)
 };
+
+// The MFMA shape of the 256 x 256 weight-gradient kernel, per operand dtype.  Two environment switches, read at every launch (A/B runs,
+// tests/test_wgrad_mfma_shape.py): SNERF_WGRAD_MFMA = 16 | 32 picks the flavour and nothing else -- the plan stays the default's, so a run under
+// "32" is the plain 32 flavour launch for launch; SNERF_WGRAD_TN8 = 1 sends a launch to the 256 x 256 kernel wherever it CAN run (tn_plan's rules
+// on M are about speed), so that a test reaches it with a handful of k-tiles.  The split-bf16 instantiation has the 32 flavour only.
+static int tn8_forced_mshape() {
+  const char* e = getenv("SNERF_WGRAD_MFMA");
+  if (e == nullptr) return 0;
+  const int v = atoi(e);
+  return v == 16 || v == 32 ? v : 0;
+}
+static bool tn8_forced_kernel() {
+  const char* e = getenv("SNERF_WGRAD_TN8");
+  return e != nullptr && atoi(e) == 1;
+}
+// Defaults, by measurement on the 4096-ray step (profiles/r9_a_tn8_mfma_shape.txt): bf16 runs the 16 flavour (the part holds 1.58-1.66 GHz under
+// it against 1.42-1.48 GHz under the 32 flavour: -2 % per launch, -0.5 ms per step); in fp16 the two could not be told apart, so it stays on 32.
+static int tn8_default_mshape(bool f16) { return f16 ? 32 : 16; }
 
 // fold: the launch stores partial tiles (deterministic / default fold mode) instead of adding with atomics -- two rules that exist to amortise a
 // workgroup's atomics then do not apply to SMALL M (<= 131 072 rows, where the fixed cost of a launch is what is left of it): the 128 x 128 kernel
 // may cut slices of 256 instead of >= 1024 rows, and a launch the 256 x 256 kernel would cut into slices of fewer than eight k-tiles (one or two output
 // tiles: M = 32 768 -> 256 slices of two k-tiles, a 256 KB partial tile each) goes to the 128 x 128 kernel instead.
-static TnPlan tn_plan(int M, int N, int K, long ldz, long ldx, int dtype, int variant, bool fold = false) {
+static TnPlan tn_plan(int M, int N, int K, long ldz, long ldx, int dtype, int variant, bool fold = false, bool f16 = false, bool split = false) {
   static int n_cu = 0;
   if (n_cu == 0) {
     int dev = 0;
@@ -1977,8 +2141,10 @@ static TnPlan tn_plan(int M, int N, int K, long ldz, long ldx, int dtype, int va
       n_cu = prop.multiProcessorCount;
   }
   TnPlan pl{};
+  const int forced = tn8_forced_mshape();
+  const bool force8 = tn8_forced_kernel();
   // variant 2 (bf16): 256 x 256 tiles, 8-phase schedule; M is cut into as many slices as keep every CU busy
-  if ((variant & 2) && dtype == SNERF_DT_BF16 && N % 256 == 0 && K >= 256 && M >= 4096 && ldz * 2 * 65 < (1L << 31) && ldx * 2 * 65 < (1L << 31)) {
+  if ((variant & 2) && dtype == SNERF_DT_BF16 && N % 256 == 0 && K >= 256 && (M >= 4096 || force8) && ldz * 2 * 65 < (1L << 31) && ldx * 2 * 65 < (1L << 31)) {
     const int t8 = (N / 256) * ((K + 255) / 256);
     int ch = n_cu / t8;
     ch = ch < 1 ? 1 : ch;
@@ -1986,8 +2152,9 @@ static TnPlan tn_plan(int M, int N, int K, long ldz, long ldx, int dtype, int va
     mc = ((mc + 127) / 128) * 128;                    // whole k-tile pairs
     const long lim = (1L << 30) / ((ldz > ldx ? ldz : ldx) * 2);   // slice bytes stay inside 32-bit buffer offsets
     if (mc > lim) mc = lim / 128 * 128;
-    if (!(fold && M <= 131072 && mc < 512)) {
+    if (force8 || !(fold && M <= 131072 && mc < 512)) {
       pl.use8 = true; pl.m_chunk = (int)mc; pl.slices = (int)((M + mc - 1) / mc);
+      pl.mshape = split ? 32 : forced ? forced : tn8_default_mshape(f16);
       pl.part_ld = ((K + 255) / 256) * 256; pl.part_stride = (long)N * pl.part_ld;
       return pl;
     }
@@ -2026,7 +2193,7 @@ static int wgrad_launch(const void* Z, long ldz, const void* X, long ldx, float*
   if (f16) dtype = SNERF_DT_BF16;
   const int epc = dtype == SNERF_DT_F32 ? 4 : 8;
   if (N < epc || K < epc || N % epc || K % epc || ldz % epc || ldx % epc || zeros == nullptr) return SNERF_ERR_ARG;
-  const TnPlan pl = tn_plan(M, N, K, ldz, ldx, dtype, variant, ws != nullptr);
+  const TnPlan pl = tn_plan(M, N, K, ldz, ldx, dtype, variant, ws != nullptr, f16, split != 0);
   if (ws != nullptr && ws_floats < pl.part_stride * pl.slices) return SNERF_ERR_ARG;
   GemmTN p{Z, ldz, X, ldx, dW, ldw, zeros, M, N, K, n_valid, k_valid, pl.m_chunk, 0, pl.slices, split ? 1 : (xhi ? 2 : 0), ws, pl.part_stride, pl.part_ld};
   if (pl.use8) {
@@ -2037,7 +2204,16 @@ static int wgrad_launch(const void* Z, long ldz, const void* X, long ldx, float*
       attr_set = true;
     }
     const int t8 = (N / 256) * ((K + 255) / 256);
-    if (f16) {
+    if (pl.mshape == 16) {
+      static bool attr_m16 = false;
+      if (!attr_m16) {
+        hipFuncSetAttribute((const void*)gemm_tn8_kernel<false, false, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, 8 * 64 * 256);
+        hipFuncSetAttribute((const void*)gemm_tn8_kernel<false, true, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, 8 * 64 * 256);
+        attr_m16 = true;
+      }
+      if (f16) hipLaunchKernelGGL((gemm_tn8_kernel<false, true, 16>), dim3(t8 * pl.slices), dim3(512), 8 * 64 * 256, (hipStream_t)stream, p);
+      else hipLaunchKernelGGL((gemm_tn8_kernel<false, false, 16>), dim3(t8 * pl.slices), dim3(512), 8 * 64 * 256, (hipStream_t)stream, p);
+    } else if (f16) {
       static bool attr16 = false;
       if (!attr16) { hipFuncSetAttribute((const void*)gemm_tn8_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 8 * 64 * 256); attr16 = true; }
       hipLaunchKernelGGL((gemm_tn8_kernel<false, true>), dim3(t8 * pl.slices), dim3(512), 8 * 64 * 256, (hipStream_t)stream, p);

@@ -156,7 +156,10 @@ def linear_wgrad(dZ, X, dW, n_valid, k_valid, dt, variant=0, deterministic=False
     """dW[:n_valid, :k_valid] += dZ^T @ X.  dZ [M,N], X [M,K] views, dW fp32 view.  The M slices of a launch either add with fp32 atomics (order varies
     run to run) or store partial tiles into a workspace that a second launch folds in slice order (bit-reproducible): `deterministic`
     forces the fold; it is also the default for the wide layers (below).  `x_split_hi` (dt bf16): X is an activation a split-bf16 forward
-    saved ([M, 2 K] interleaved hi / lo) and its hi half is multiplied."""
+    saved ([M, 2 K] interleaved hi / lo) and its hi half is multiplied.
+    The 256 x 256 kernel has two MFMA flavours (16 x 16 x 32: the bf16 default; 32 x 32 x 16: fp16, split-bf16).  The library reads two environment
+    variables at every launch (A/B runs, tests): SNERF_WGRAD_MFMA = 16 | 32 runs that flavour where the 256 x 256 kernel is launched anyway;
+    SNERF_WGRAD_TN8 = 1 launches the 256 x 256 kernel wherever it can run, whatever the rules on M say."""
     _chk2d(dZ, _TORCH_DT[dt]); _chk2d(X, _TORCH_DT[dt]); _chk2d(dW, torch.float32)
     assert dZ.shape[0] == X.shape[0] and dW.shape[0] >= n_valid and dW.shape[1] >= k_valid
     Kx = X.shape[1]
