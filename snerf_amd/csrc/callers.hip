@@ -899,10 +899,7 @@ extern "C" int snerf_zip_loss_tail(const float* rgb, const float* tgt, const flo
   const size_t lds = (size_t)64 * 4 * (((S2 + 1) | 1) + (S2 | 1) + ((Spm + 1) | 1) + (Spm | 1));
   const bool staged = inter && lds <= 160 * 1024;
   hipLaunchKernelGGL(zip_loss_tail_kernel, dim3((unsigned)((R + 63) / 64), inter && !staged ? 3 : 1), dim3(64), 0, (hipStream_t)stream, a);
-  if (staged) {
-    if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)zip_interlevel_lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    hipLaunchKernelGGL(zip_interlevel_lds_kernel, dim3((unsigned)((R + 63) / 64), 2), dim3(64), lds, (hipStream_t)stream, a);
-  }
+  if (staged) snerf_launch<zip_interlevel_lds_kernel>(dim3((unsigned)((R + 63) / 64), 2), dim3(64), lds, 160 * 1024, (hipStream_t)stream, a);
   return snerf_check_launch();
 }
 

@@ -27,6 +27,32 @@ static inline int snerf_check_launch() {
   return e == hipSuccess ? SNERF_OK : SNERF_ERR_LAUNCH;
 }
 
+// The one way to launch a kernel that takes more than the default 64 KiB of dynamic LDS: the first launch of an instantiation raises
+// its limit to `limit` bytes (a function-local static per kernel: once per process, thread-safe), so no kernel can be launched by
+// code that has not raised its limit.  `limit` must be one constant per kernel (>= every `lds` passed for it): the first launch latches
+// it.  The call is made once and not repeated: if it fails (no device, a limit the kernel cannot have), every launch of that kernel
+// that needs the raised limit fails for the rest of the process and its entry returns SNERF_ERR_LAUNCH.
+template <auto Kernel> static inline void snerf_raise_lds_limit(int limit) {
+  static const hipError_t raised = hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, limit);
+  (void)raised;
+}
+template <auto Kernel, typename... Args>
+static inline void snerf_launch(dim3 grid, dim3 block, size_t lds, int limit, hipStream_t stream, const Args&... args) {
+  snerf_raise_lds_limit<Kernel>(limit);
+  hipLaunchKernelGGL(Kernel, grid, block, lds, stream, args...);
+}
+
+// compute units of the current device (asked once; 256, the MI355X's, when the query fails)
+static inline int snerf_cu_count() {
+  static const int n_cu = [] {
+    int dev = 0, n = 0;
+    hipDeviceProp_t prop;
+    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) n = prop.multiProcessorCount;
+    return n > 0 ? n : 256;
+  }();
+  return n_cu;
+}
+
 // Bijective XCD-aware remap of a 1-D block id (MI355X: 8 XCDs, block b runs on
 // XCD b % 8).  Blocks that land on one XCD get a contiguous range of logical
 // ids so that neighbouring tiles share that XCD's L2.

@@ -611,9 +611,7 @@ __global__ __launch_bounds__(1024) void lds_scribble_kernel(unsigned seed, unsig
   if (scribble[(seed + threadIdx.x) % (160 * 1024 / 4)] == 0x5eed5eedu && sink != nullptr) sink[0] = seed;   // (keeps the stores alive)
 }
 extern "C" int snerf_debug_lds_scribble(int seed, void* stream) {
-  static bool attr = false;
-  if (!attr) { (void)hipFuncSetAttribute((const void*)lds_scribble_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr = true; }
-  hipLaunchKernelGGL(lds_scribble_kernel, dim3(4096), dim3(1024), 160 * 1024, (hipStream_t)stream, (unsigned)seed, (unsigned*)nullptr);
+  snerf_launch<lds_scribble_kernel>(dim3(4096), dim3(1024), 160 * 1024, 160 * 1024, (hipStream_t)stream, (unsigned)seed, (unsigned*)nullptr);
   return snerf_check_launch();
 }
 

@@ -1366,27 +1366,16 @@ static int fmlp_tiles(long M) { return (int)((M + FM_TILE_ROWS - 1) / FM_TILE_RO
 
 // one persistent workgroup per tile, at most wg_per_cu per CU of the current device (asked once; 256 CUs when the query fails)
 static int fmlp_grid(int tiles, int wg_per_cu = 1) {
-  static int n_cu = 0;
-  if (n_cu == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    n_cu = 256;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
-      n_cu = prop.multiProcessorCount;
-  }
+  const int n_cu = snerf_cu_count();
   return tiles < n_cu * wg_per_cu ? tiles : n_cu * wg_per_cu;
 }
 
-// launches the bf16 (KB) or the fp16 (KH) instantiation of a kernel, whichever dtype names; the first launch of a pair raises the
-// dynamic-LDS limit of both (the static below exists once per pair)
+// launches the bf16 (KB) or the fp16 (KH) instantiation of a kernel, whichever dtype names (a pair's `lds` is one constant: it is the
+// limit snerf_launch raises, too)
 template <typename Args, void (*KB)(Args), void (*KH)(Args)>
 static void fmlp_launch_pair(int dtype, int grid, int lds, void* stream, const Args& a) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    for (auto k : {KB, KH}) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(dtype == SNERF_DT_F16 ? KH : KB, dim3(grid), dim3(64 * FM_WAVES), lds, (hipStream_t)stream, a);
+  if (dtype == SNERF_DT_F16) snerf_launch<KH>(dim3(grid), dim3(64 * FM_WAVES), lds, lds, (hipStream_t)stream, a);
+  else snerf_launch<KB>(dim3(grid), dim3(64 * FM_WAVES), lds, lds, (hipStream_t)stream, a);
 }
 
 // HOST arrays of n device pointers / row strides (elements) of stored 16-bit matrices: every pointer non-null and 16-byte aligned, every

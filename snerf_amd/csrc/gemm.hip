@@ -1258,155 +1258,99 @@ __global__ __launch_bounds__(256) void colsum_split_kernel(const __bf16* __restr
     if (c0 + e < n_store) atomicAdd(out + c0 + e, acc[e]);
 }
 
+// the bias-gradient fold behind the 16-byte epilogues: colsum[n] += the `rows` partial rows the launch left in the workspace
+// (det: one chunk per column, so the additions run in row order)
+static void colsum_fold(int rows, int det, int n_store, int N, const float* ws, float* colsum, hipStream_t stream) {
+  int ychunks = rows / 8;
+  ychunks = (ychunks < 1 || det) ? 1 : (ychunks > 64 ? 64 : ychunks);
+  hipLaunchKernelGGL(colsum_reduce_kernel, dim3((n_store + 255) / 256, ychunks), dim3(256), 0, stream, ws, rows, N, n_store, colsum);
+}
+
 template <typename T, int BM, int BN, int WM, int WN, bool F16 = false>
 static int launch_nt(const GemmNT& p, hipStream_t stream) {
   constexpr int LDS = 2 * (BM + BN) * 128;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipFuncSetAttribute((const void*)gemm_nt_kernel<T, BM, BN, WM, WN, F16>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    attr_set = true;
-  }
   const int tiles_m = (p.M + BM - 1) / BM;
   const int tiles = tiles_m * (p.N / BN);
-  hipLaunchKernelGGL((gemm_nt_kernel<T, BM, BN, WM, WN, F16>), dim3(tiles), dim3(64 * WM * WN), LDS, stream, p);
-  if (p.fast_epi && p.colsum_ws != nullptr) {
-    const int rows = tiles_m * WM;
-    int ychunks = rows / 8;
-    ychunks = (ychunks < 1 || p.det) ? 1 : (ychunks > 64 ? 64 : ychunks);
-    hipLaunchKernelGGL(colsum_reduce_kernel, dim3((p.n_store + 255) / 256, ychunks), dim3(256), 0, stream, p.colsum_ws, rows, p.N, p.n_store, p.colsum);
-  }
+  snerf_launch<gemm_nt_kernel<T, BM, BN, WM, WN, F16>>(dim3(tiles), dim3(64 * WM * WN), LDS, LDS, stream, p);
+  if (p.fast_epi && p.colsum_ws != nullptr) colsum_fold(tiles_m * WM, p.det, p.n_store, p.N, p.colsum_ws, p.colsum, stream);
   return snerf_check_launch();
 }
 
 template <bool F16 = false>
 static int launch_nt8(const GemmNT& p, hipStream_t stream) {
   constexpr int LDS = 8 * 128 * 128;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipFuncSetAttribute((const void*)gemm_nt8_kernel<F16>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    attr_set = true;
-  }
   const int tiles_m = (p.M + 255) / 256;
   const int tiles = tiles_m * (p.N / 256);
-  hipLaunchKernelGGL((gemm_nt8_kernel<F16>), dim3(tiles), dim3(512), LDS, stream, p);
-  if (p.fast_epi && p.colsum_ws != nullptr) {
-    const int rows = tiles_m * 2;
-    int ychunks = rows / 8;
-    ychunks = (ychunks < 1 || p.det) ? 1 : (ychunks > 64 ? 64 : ychunks);
-    hipLaunchKernelGGL(colsum_reduce_kernel, dim3((p.n_store + 255) / 256, ychunks), dim3(256), 0, stream, p.colsum_ws, rows, p.N, p.n_store, p.colsum);
-  }
+  snerf_launch<gemm_nt8_kernel<F16>>(dim3(tiles), dim3(512), LDS, LDS, stream, p);
+  if (p.fast_epi && p.colsum_ws != nullptr) colsum_fold(tiles_m * 2, p.det, p.n_store, p.N, p.colsum_ws, p.colsum, stream);
   return snerf_check_launch();
+}
+
+// One flavour of the persistent kernel, as a function the table below can point at.
+typedef void (*Nt8pLaunch)(int grid, const GemmNT& p, hipStream_t stream);
+template <int ACT, bool COLSUM, int SPLIT, bool F16, bool KT2 = false>
+static void nt8p_go(int grid, const GemmNT& p, hipStream_t stream) {
+  constexpr int LDS = 8 * 128 * 128 + 4 * 4096 + 2048 + 8192;
+  snerf_launch<gemm_nt8p_kernel<ACT, COLSUM, SPLIT, F16, KT2>>(dim3(grid), dim3(512), LDS, LDS, stream, p);
+}
+
+// Every (act, column sums, split flavour, K = 128) the persistent kernel is compiled for, per 16-bit format; anything else is refused
+// (nullptr).  The plain operands first, each flavour also in the K = 128 form (KT2: two k-tiles per tile, the bias / mask DMAs ordered
+// by hand).  (The kernels stand in the code object in the order in which this text and tn8_flavour / tn_flavour below mention them.
+// Nothing the library does depends on that order: it is kept only so that a code object can be compared line for line with the one
+// built before these selections existed, and an edit that moves a line moves kernels, it changes none.)
+template <bool F16, bool KT2>
+static Nt8pLaunch nt8p_plain(int act, bool cs) {
+  if (act == ACT_NONE && !cs) return nt8p_go<ACT_NONE, false, 0, F16, KT2>;
+  if (act == ACT_RELU && !cs) return nt8p_go<ACT_RELU, false, 0, F16, KT2>;
+  if (act == ACT_NONE && cs) return nt8p_go<ACT_NONE, true, 0, F16, KT2>;
+  if (act == ACT_MASK && !cs) return nt8p_go<ACT_MASK, false, 0, F16, KT2>;
+  if (act == ACT_MASK && cs) return nt8p_go<ACT_MASK, true, 0, F16, KT2>;
+  if (act == ACT_RELU_BITS && !cs) return nt8p_go<ACT_RELU_BITS, false, 0, F16, KT2>;
+  if (act == ACT_MASK_BITS && !cs) return nt8p_go<ACT_MASK_BITS, false, 0, F16, KT2>;
+  if (act == ACT_MASK_BITS && cs) return nt8p_go<ACT_MASK_BITS, true, 0, F16, KT2>;
+  return nullptr;
+}
+template <bool F16>
+static Nt8pLaunch nt8p_flavour(int act, bool cs, int split, bool kt2) {
+  if (split == 0) return !kt2 ? nt8p_plain<F16, false>(act, cs) : nt8p_plain<F16, true>(act, cs);
+  if (split == 2 && F16 && !cs) {                        // fp16 + fp8: forward activations only, no column sums
+    if (act == ACT_NONE) return nt8p_go<ACT_NONE, false, 2, true>;
+    if (act == ACT_RELU) return nt8p_go<ACT_RELU, false, 2, true>;
+    if (act == ACT_RELU_BITS) return nt8p_go<ACT_RELU_BITS, false, 2, true>;
+  }
+  if (split == 1 && !F16) {                              // split-bf16 (no bf16-aux mask: the data gradients use the bit masks;
+    if (act == ACT_NONE && !cs) return nt8p_go<ACT_NONE, false, 1, false>;          //  MASK_BITS leaves its column sums to launch_nt8p)
+    if (act == ACT_NONE && cs) return nt8p_go<ACT_NONE, true, 1, false>;
+    if (act == ACT_RELU && !cs) return nt8p_go<ACT_RELU, false, 1, false>;
+    if (act == ACT_RELU_BITS && !cs) return nt8p_go<ACT_RELU_BITS, false, 1, false>;
+    if (act == ACT_MASK_BITS && !cs) return nt8p_go<ACT_MASK_BITS, false, 1, false>;
+  }
+  return nullptr;
 }
 
 template <bool F16 = false>
 static int launch_nt8p(const GemmNT& p, hipStream_t stream) {
-  constexpr int LDS = 8 * 128 * 128 + 4 * 4096 + 2048 + 8192;
-  static bool attr_set = false;
-  static int n_cu = 256;
-  if (!attr_set) {
-    hipFuncSetAttribute((const void*)gemm_nt8p_kernel<ACT_NONE, false, false, F16>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    hipFuncSetAttribute((const void*)gemm_nt8p_kernel<ACT_RELU, false, false, F16>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    hipFuncSetAttribute((const void*)gemm_nt8p_kernel<ACT_NONE, true, false, F16>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    hipFuncSetAttribute((const void*)gemm_nt8p_kernel<ACT_MASK, false, false, F16>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    hipFuncSetAttribute((const void*)gemm_nt8p_kernel<ACT_MASK, true, false, F16>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    hipFuncSetAttribute((const void*)gemm_nt8p_kernel<ACT_RELU_BITS, false, false, F16>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    hipFuncSetAttribute((const void*)gemm_nt8p_kernel<ACT_MASK_BITS, false, false, F16>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    hipFuncSetAttribute((const void*)gemm_nt8p_kernel<ACT_MASK_BITS, true, false, F16>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    // the K = 128 flavours (two k-tiles per tile: see KT2 in the kernel)
-    hipFuncSetAttribute((const void*)gemm_nt8p_kernel<ACT_NONE, false, false, F16, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    hipFuncSetAttribute((const void*)gemm_nt8p_kernel<ACT_RELU, false, false, F16, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    hipFuncSetAttribute((const void*)gemm_nt8p_kernel<ACT_NONE, true, false, F16, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    hipFuncSetAttribute((const void*)gemm_nt8p_kernel<ACT_MASK, false, false, F16, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    hipFuncSetAttribute((const void*)gemm_nt8p_kernel<ACT_MASK, true, false, F16, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    hipFuncSetAttribute((const void*)gemm_nt8p_kernel<ACT_RELU_BITS, false, false, F16, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    hipFuncSetAttribute((const void*)gemm_nt8p_kernel<ACT_MASK_BITS, false, false, F16, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    hipFuncSetAttribute((const void*)gemm_nt8p_kernel<ACT_MASK_BITS, true, false, F16, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
-      n_cu = prop.multiProcessorCount;
-    attr_set = true;
-  }
   const int tiles_m = (p.M + 255) / 256;
   const int tiles = tiles_m * (p.N / 256);
-  int grid = tiles < n_cu ? tiles : n_cu;
+  int grid = tiles < snerf_cu_count() ? tiles : snerf_cu_count();
 #if SNERF_PROBE
   // PROBE builds: SNERF_NT8P_GRID caps the number of persistent workgroups (tools/gemm_grid_probe.py: what a tile's row stores cost
   // when only a part of the chip is working)
   if (const char* e = getenv("SNERF_NT8P_GRID")) { const int g = atoi(e); if (g > 0 && g < grid) grid = g; }
 #endif
   const bool cs = p.colsum_ws != nullptr;
-  const dim3 g(grid), b(512);
-  if (p.split == 2) {                                    // fp16 + fp8 flavours (forward activations only)
-    if constexpr (F16) {
-      static bool s8attr = false;
-      if (!s8attr) {
-        hipFuncSetAttribute((const void*)gemm_nt8p_kernel<ACT_NONE, false, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        hipFuncSetAttribute((const void*)gemm_nt8p_kernel<ACT_RELU, false, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        hipFuncSetAttribute((const void*)gemm_nt8p_kernel<ACT_RELU_BITS, false, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        s8attr = true;
-      }
-      if (cs) return SNERF_ERR_ARG;
-      if (p.act == ACT_RELU_BITS) hipLaunchKernelGGL((gemm_nt8p_kernel<ACT_RELU_BITS, false, 2, true>), g, b, LDS, stream, p);
-      else if (p.act == ACT_RELU) hipLaunchKernelGGL((gemm_nt8p_kernel<ACT_RELU, false, 2, true>), g, b, LDS, stream, p);
-      else if (p.act == ACT_NONE) hipLaunchKernelGGL((gemm_nt8p_kernel<ACT_NONE, false, 2, true>), g, b, LDS, stream, p);
-      else return SNERF_ERR_ARG;
-      return snerf_check_launch();
-    } else return SNERF_ERR_ARG;
-  }
-  if (p.split && F16) return SNERF_ERR_ARG;
-  if (p.split) {                                         // split-bf16 flavours (no bf16-aux mask: the data gradients use the bit masks)
-    static bool sattr = false;
-    if (!sattr) {
-      hipFuncSetAttribute((const void*)gemm_nt8p_kernel<ACT_NONE, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-      hipFuncSetAttribute((const void*)gemm_nt8p_kernel<ACT_NONE, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-      hipFuncSetAttribute((const void*)gemm_nt8p_kernel<ACT_RELU, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-      hipFuncSetAttribute((const void*)gemm_nt8p_kernel<ACT_RELU_BITS, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-      hipFuncSetAttribute((const void*)gemm_nt8p_kernel<ACT_MASK_BITS, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-      sattr = true;
-    }
-    if (p.act == ACT_MASK_BITS) {
-      // (with a bias gradient: the plain flavour, then colsum_split_kernel over the output -- see there)
-      GemmNT q = p;
-      q.colsum_ws = nullptr;
-      hipLaunchKernelGGL((gemm_nt8p_kernel<ACT_MASK_BITS, false, true>), g, b, LDS, stream, q);
-      if (cs) {
-        const int g8 = (p.n_store + 7) / 8;
-        hipLaunchKernelGGL(colsum_split_kernel, dim3((p.M + 1023) / 1024, (g8 + 255) / 256), dim3(256), 0, stream, (const __bf16*)p.Y, p.ldy, p.M, p.n_store, p.colsum);
-      }
-      return snerf_check_launch();
-    } else if (p.act == ACT_RELU_BITS && !cs) hipLaunchKernelGGL((gemm_nt8p_kernel<ACT_RELU_BITS, false, true>), g, b, LDS, stream, p);
-    else if (p.act == ACT_RELU && !cs) hipLaunchKernelGGL((gemm_nt8p_kernel<ACT_RELU, false, true>), g, b, LDS, stream, p);
-    else if (p.act == ACT_NONE && cs) hipLaunchKernelGGL((gemm_nt8p_kernel<ACT_NONE, true, true>), g, b, LDS, stream, p);
-    else if (p.act == ACT_NONE) hipLaunchKernelGGL((gemm_nt8p_kernel<ACT_NONE, false, true>), g, b, LDS, stream, p);
-    else return SNERF_ERR_ARG;
-  } else {
-    const bool kt2 = (p.K >> 6) == 2;                    // K = 128: the flavour that orders the bias / mask DMAs by hand
-#define NT8P(A_, C_) do { if (kt2) hipLaunchKernelGGL((gemm_nt8p_kernel<A_, C_, false, F16, true>), g, b, LDS, stream, p); \
-                          else hipLaunchKernelGGL((gemm_nt8p_kernel<A_, C_, false, F16, false>), g, b, LDS, stream, p); } while (0)
-    if (p.act == ACT_MASK) {
-      if (cs) NT8P(ACT_MASK, true); else NT8P(ACT_MASK, false);
-    } else if (p.act == ACT_MASK_BITS) {
-      if (cs) NT8P(ACT_MASK_BITS, true); else NT8P(ACT_MASK_BITS, false);
-    } else if (p.act == ACT_RELU_BITS) {
-      if (cs) return SNERF_ERR_ARG;
-      NT8P(ACT_RELU_BITS, false);
-    } else if (cs) {
-      if (p.act != ACT_NONE) return SNERF_ERR_ARG;
-      NT8P(ACT_NONE, true);
-    } else if (p.act == ACT_RELU) {
-      NT8P(ACT_RELU, false);
-    } else {
-      NT8P(ACT_NONE, false);
-    }
-#undef NT8P
-  }
-  if (p.colsum_ws != nullptr) {
-    const int rows = grid * 2;                            // one partial row per (workgroup, wave row)
-    int ychunks = rows / 8;
-    ychunks = (ychunks < 1 || p.det) ? 1 : (ychunks > 64 ? 64 : ychunks);
-    hipLaunchKernelGGL(colsum_reduce_kernel, dim3((p.n_store + 255) / 256, ychunks), dim3(256), 0, stream, p.colsum_ws, rows, p.N, p.n_store, p.colsum);
-  }
+  // split-bf16 data gradient with a bias gradient: the flavour without column sums, then colsum_split_kernel over the output (see there)
+  const bool cs_after = cs && p.split == 1 && p.act == ACT_MASK_BITS;
+  const Nt8pLaunch go = nt8p_flavour<F16>(p.act, cs && !cs_after, p.split, (p.K >> 6) == 2);
+  if (go == nullptr) return SNERF_ERR_ARG;
+  GemmNT q = p;
+  if (cs_after) q.colsum_ws = nullptr;
+  go(grid, q, stream);
+  if (cs_after) {
+    const int g8 = (p.n_store + 7) / 8;
+    hipLaunchKernelGGL(colsum_split_kernel, dim3((p.M + 1023) / 1024, (g8 + 255) / 256), dim3(256), 0, stream, (const __bf16*)p.Y, p.ldy, p.M, p.n_store, p.colsum);
+  } else if (cs) colsum_fold(grid * 2, p.det, p.n_store, p.N, p.colsum_ws, p.colsum, stream);   // one partial row per (workgroup, wave row)
   return snerf_check_launch();
 }
 
@@ -2132,14 +2076,7 @@ static int tn8_default_mshape(bool f16) { return f16 ? 32 : 16; }
 // may cut slices of 256 instead of >= 1024 rows, and a launch the 256 x 256 kernel would cut into slices of fewer than eight k-tiles (one or two output
 // tiles: M = 32 768 -> 256 slices of two k-tiles, a 256 KB partial tile each) goes to the 128 x 128 kernel instead.
 static TnPlan tn_plan(int M, int N, int K, long ldz, long ldx, int dtype, int variant, bool fold = false, bool f16 = false, bool split = false) {
-  static int n_cu = 0;
-  if (n_cu == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    n_cu = 256;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
-      n_cu = prop.multiProcessorCount;
-  }
+  const int n_cu = snerf_cu_count();
   TnPlan pl{};
   const int forced = tn8_forced_mshape();
   const bool force8 = tn8_forced_kernel();
@@ -2177,6 +2114,53 @@ static TnPlan tn_plan(int M, int N, int K, long ldz, long ldx, int dtype, int va
   return pl;
 }
 
+// One instantiation of a weight-gradient kernel, as a function the selections below can return.
+typedef void (*TnLaunch)(int grid, const GemmTN& p, hipStream_t stream);
+template <bool SPLIT, bool F16, int MSHAPE>
+static void tn8_go(int grid, const GemmTN& p, hipStream_t stream) {
+  snerf_launch<gemm_tn8_kernel<SPLIT, F16, MSHAPE>>(dim3(grid), dim3(512), 8 * 64 * 256, 8 * 64 * 256, stream, p);
+}
+// (the double buffer's 32 KiB need no raised limit; going through the helper all the same sets that kernel's limit to the 32 KiB it uses)
+template <typename T, bool TR, int TN_STAGES, bool F16>
+static void tn_go(int grid, const GemmTN& p, hipStream_t stream) {
+  snerf_launch<gemm_tn_kernel<T, TR, TN_STAGES, F16>>(dim3(grid), dim3(256), TN_STAGES * 2 * 8192, TN_STAGES * 2 * 8192, stream, p);
+}
+
+// the 256 x 256 kernel: the 16x16x32 flavour exists for plain bf16 / fp16 operands, the split-bf16 instantiation has the 32 flavour only
+static TnLaunch tn8_flavour(int mshape, bool f16, bool split) {
+  if (!f16 && mshape != 16) return !split ? tn8_go<false, false, 32> : tn8_go<true, false, 32>;
+  if (mshape == 16) return !f16 ? tn8_go<false, false, 16> : tn8_go<false, true, 16>;
+  return tn8_go<false, true, 32>;
+}
+
+// the 128 x 128 kernel (f16 arrives with dtype bf16).  tr (variant 1): operands via ds_read_b64_tr_b16 (needs whole 128-column tiles:
+// the source swizzle permutes chunks inside a 256-byte row), else 16-bit LDS gathers.  deep (variant bit 128): a ring of four staging
+// slots (three stages in flight) instead of the double buffer.  Measured with the XCD-aware placement (round 3,
+// tools/gemm_tn_narrow_probe.py): the ring LOSES (64 KiB of LDS per workgroup halve the residency: N = 128, K = 1051: 472 vs 325 us;
+// N = 1: 341 vs 295), so the double buffer stays the default and the ring is the probe's alternative.
+static TnLaunch tn_flavour(int dtype, bool f16, bool tr, bool deep) {
+  if (dtype != SNERF_DT_F32 && dtype != SNERF_DT_BF16) return nullptr;
+  if (deep) {
+    if (dtype == SNERF_DT_F32) return tn_go<float, false, 4, false>;
+    if (!f16) return tr ? tn_go<__bf16, true, 4, false> : tn_go<__bf16, false, 4, false>;
+    return tr ? tn_go<__bf16, true, 4, true> : tn_go<__bf16, false, 4, true>;
+  }
+  if (f16) return tr ? tn_go<__bf16, true, 2, true> : tn_go<__bf16, false, 2, true>;
+  if (dtype == SNERF_DT_F32) return tn_go<float, false, 2, false>;
+  return tr ? tn_go<__bf16, true, 2, false> : tn_go<__bf16, false, 2, false>;
+}
+
+// the fold behind a launch that stored partial tiles: dW += the slices in slice order
+static void tn_fold(const TnPlan& pl, int n_valid, int k_valid, float* dW, long ldw, const float* ws, hipStream_t stream) {
+  // (the same sums in the same order either way: the vector flavour only needs 16-byte aligned rows)
+  const bool vec = k_valid % 4 == 0 && pl.part_ld % 4 == 0 && pl.part_stride % 4 == 0 && ldw % 4 == 0 && ((size_t)dW & 15) == 0 && ((size_t)ws & 15) == 0;
+  const int kq = vec ? k_valid / 4 : k_valid;           // pieces (VEC: 4 floats) per output row
+  const bool many = pl.slices > 32;                     // (the 128 x 128 kernel's launches; the wide layers run 16 slices)
+  const auto kernel = many ? (vec ? tn_fold_many_kernel<true> : tn_fold_many_kernel<false>) : (vec ? tn_fold_kernel<true> : tn_fold_kernel<false>);
+  const dim3 grid = many ? dim3((unsigned)(((long)n_valid * kq + 63) / 64)) : dim3((kq + 255) / 256, n_valid);
+  hipLaunchKernelGGL(kernel, grid, dim3(many ? 1024 : 256), 0, stream, ws, pl.part_stride, pl.part_ld, pl.slices, n_valid, k_valid, dW, ldw);
+}
+
 static int wgrad_launch(const void* Z, long ldz, const void* X, long ldx, float* dW, long ldw, const void* zeros, int M, int N, int K,
                         int n_valid, int k_valid, int dtype, int variant, float* ws, long ws_floats, void* stream) {
   if (M <= 0) return SNERF_OK;
@@ -2196,86 +2180,15 @@ static int wgrad_launch(const void* Z, long ldz, const void* X, long ldx, float*
   const TnPlan pl = tn_plan(M, N, K, ldz, ldx, dtype, variant, ws != nullptr, f16, split != 0);
   if (ws != nullptr && ws_floats < pl.part_stride * pl.slices) return SNERF_ERR_ARG;
   GemmTN p{Z, ldz, X, ldx, dW, ldw, zeros, M, N, K, n_valid, k_valid, pl.m_chunk, 0, pl.slices, split ? 1 : (xhi ? 2 : 0), ws, pl.part_stride, pl.part_ld};
-  if (pl.use8) {
-    static bool attr_set = false;
-    if (!attr_set) {
-      hipFuncSetAttribute((const void*)gemm_tn8_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 8 * 64 * 256);
-      hipFuncSetAttribute((const void*)gemm_tn8_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 8 * 64 * 256);
-      attr_set = true;
-    }
-    const int t8 = (N / 256) * ((K + 255) / 256);
-    if (pl.mshape == 16) {
-      static bool attr_m16 = false;
-      if (!attr_m16) {
-        hipFuncSetAttribute((const void*)gemm_tn8_kernel<false, false, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, 8 * 64 * 256);
-        hipFuncSetAttribute((const void*)gemm_tn8_kernel<false, true, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, 8 * 64 * 256);
-        attr_m16 = true;
-      }
-      if (f16) hipLaunchKernelGGL((gemm_tn8_kernel<false, true, 16>), dim3(t8 * pl.slices), dim3(512), 8 * 64 * 256, (hipStream_t)stream, p);
-      else hipLaunchKernelGGL((gemm_tn8_kernel<false, false, 16>), dim3(t8 * pl.slices), dim3(512), 8 * 64 * 256, (hipStream_t)stream, p);
-    } else if (f16) {
-      static bool attr16 = false;
-      if (!attr16) { hipFuncSetAttribute((const void*)gemm_tn8_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 8 * 64 * 256); attr16 = true; }
-      hipLaunchKernelGGL((gemm_tn8_kernel<false, true>), dim3(t8 * pl.slices), dim3(512), 8 * 64 * 256, (hipStream_t)stream, p);
-    } else if (split) hipLaunchKernelGGL(gemm_tn8_kernel<true>, dim3(t8 * pl.slices), dim3(512), 8 * 64 * 256, (hipStream_t)stream, p);
-    else hipLaunchKernelGGL(gemm_tn8_kernel<false>, dim3(t8 * pl.slices), dim3(512), 8 * 64 * 256, (hipStream_t)stream, p);
-  } else {
-    const int tiles = ((N + 127) / 128) * ((K + 127) / 128);
-    p.tiles = tiles;
-    // variant bit 128: a ring of four staging slots (three stages in flight) instead of the double buffer.  Measured with the XCD-aware
-    // placement (round 3, tools/gemm_tn_narrow_probe.py): the ring LOSES (64 KiB of LDS per workgroup halve the residency: N = 128,
-    // K = 1051: 472 vs 325 us; N = 1: 341 vs 295), so the double buffer stays the default and the ring is the probe's alternative.
-    const bool deep = (variant & 128) != 0;
-    const int lds = (deep ? 4 : 2) * 2 * 8192;
-    static bool tn_attr_set = false;
-    if (!tn_attr_set) {
-      hipFuncSetAttribute((const void*)gemm_tn_kernel<float, false, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 2 * 8192);
-      hipFuncSetAttribute((const void*)gemm_tn_kernel<__bf16, true, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 2 * 8192);
-      hipFuncSetAttribute((const void*)gemm_tn_kernel<__bf16, false, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 2 * 8192);
-      tn_attr_set = true;
-    }
-    dim3 grid(8 * ((pl.slices + 7) / 8) * tiles);        // every XCD gets room for the largest share of slices
-    // variant 1 (bf16): operands via ds_read_b64_tr_b16 (needs whole 128-column tiles: the source swizzle permutes chunks
-    // inside a 256-byte row); variant 0: 16-bit LDS gathers
-    const bool tr = (variant & 1) && dtype == SNERF_DT_BF16 && (N % 128 == 0) && (K % 128 == 0);
-    hipStream_t st = (hipStream_t)stream;
-    if (f16) {
-      static bool tn16_attr = false;
-      if (!tn16_attr) {
-        hipFuncSetAttribute((const void*)gemm_tn_kernel<__bf16, true, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 2 * 8192);
-        hipFuncSetAttribute((const void*)gemm_tn_kernel<__bf16, false, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 2 * 8192);
-        tn16_attr = true;
-      }
-      if (tr) { if (deep) hipLaunchKernelGGL((gemm_tn_kernel<__bf16, true, 4, true>), grid, dim3(256), lds, st, p);
-                else hipLaunchKernelGGL((gemm_tn_kernel<__bf16, true, 2, true>), grid, dim3(256), lds, st, p); }
-      else { if (deep) hipLaunchKernelGGL((gemm_tn_kernel<__bf16, false, 4, true>), grid, dim3(256), lds, st, p);
-             else hipLaunchKernelGGL((gemm_tn_kernel<__bf16, false, 2, true>), grid, dim3(256), lds, st, p); }
-    } else if (dtype == SNERF_DT_F32) {
-      if (deep) hipLaunchKernelGGL((gemm_tn_kernel<float, false, 4>), grid, dim3(256), lds, st, p);
-      else hipLaunchKernelGGL((gemm_tn_kernel<float, false, 2>), grid, dim3(256), lds, st, p);
-    } else if (dtype == SNERF_DT_BF16 && tr) {
-      if (deep) hipLaunchKernelGGL((gemm_tn_kernel<__bf16, true, 4>), grid, dim3(256), lds, st, p);
-      else hipLaunchKernelGGL((gemm_tn_kernel<__bf16, true, 2>), grid, dim3(256), lds, st, p);
-    } else if (dtype == SNERF_DT_BF16) {
-      if (deep) hipLaunchKernelGGL((gemm_tn_kernel<__bf16, false, 4>), grid, dim3(256), lds, st, p);
-      else hipLaunchKernelGGL((gemm_tn_kernel<__bf16, false, 2>), grid, dim3(256), lds, st, p);
-    } else return SNERF_ERR_ARG;
+  const TnLaunch go = pl.use8 ? tn8_flavour(pl.mshape, f16, split != 0)
+                            : tn_flavour(dtype, f16, (variant & 1) && dtype == SNERF_DT_BF16 && (N % 128 == 0) && (K % 128 == 0), (variant & 128) != 0);
+  if (go == nullptr) return SNERF_ERR_ARG;
+  if (pl.use8) go((N / 256) * ((K + 255) / 256) * pl.slices, p, (hipStream_t)stream);
+  else {
+    p.tiles = ((N + 127) / 128) * ((K + 127) / 128);
+    go(8 * ((pl.slices + 7) / 8) * p.tiles, p, (hipStream_t)stream);   // every XCD gets room for the largest share of slices
   }
-  if (ws != nullptr) {
-    // (the same sums in the same order either way: the vector flavour only needs 16-byte aligned rows)
-    const bool vec = k_valid % 4 == 0 && pl.part_ld % 4 == 0 && pl.part_stride % 4 == 0 && ldw % 4 == 0 && ((size_t)dW & 15) == 0 && ((size_t)ws & 15) == 0;
-    if (pl.slices > 32) {                                  // (the 128 x 128 kernel's launches; the wide layers run 16 slices)
-      const long pieces = (long)n_valid * (vec ? k_valid / 4 : k_valid);
-      const dim3 fg((unsigned)((pieces + 63) / 64));
-      if (vec) hipLaunchKernelGGL(tn_fold_many_kernel<true>, fg, dim3(1024), 0, (hipStream_t)stream, ws, pl.part_stride, pl.part_ld, pl.slices, n_valid, k_valid, dW, ldw);
-      else hipLaunchKernelGGL(tn_fold_many_kernel<false>, fg, dim3(1024), 0, (hipStream_t)stream, ws, pl.part_stride, pl.part_ld, pl.slices, n_valid, k_valid, dW, ldw);
-    } else if (vec)
-      hipLaunchKernelGGL(tn_fold_kernel<true>, dim3((k_valid / 4 + 255) / 256, n_valid), dim3(256), 0, (hipStream_t)stream, ws, pl.part_stride,
-                         pl.part_ld, pl.slices, n_valid, k_valid, dW, ldw);
-    else
-      hipLaunchKernelGGL(tn_fold_kernel<false>, dim3((k_valid + 255) / 256, n_valid), dim3(256), 0, (hipStream_t)stream, ws, pl.part_stride,
-                         pl.part_ld, pl.slices, n_valid, k_valid, dW, ldw);
-  }
+  if (ws != nullptr) tn_fold(pl, n_valid, k_valid, dW, ldw, ws, (hipStream_t)stream);
   return snerf_check_launch();
 }
 

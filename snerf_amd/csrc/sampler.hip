@@ -83,11 +83,9 @@ extern "C" int snerf_classic_sample_pdf(const float* bins, long ld_bins, int mid
   const int stride = nc | 1;
   const size_t lds = (size_t)LPR_THREADS * stride * sizeof(float);
   if (lds > 160 * 1024) return SNERF_ERR_ARG;
-  static bool attr = false;
-  if (!attr) { hipFuncSetAttribute((const void*)classic_sample_pdf_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr = true; }
   const int blocks = (int)((N + LPR_THREADS - 1) / LPR_THREADS);
-  hipLaunchKernelGGL(classic_sample_pdf_kernel, dim3(blocks), dim3(LPR_THREADS), lds, (hipStream_t)stream, bins, ld_bins, mid_mode, weights,
-                     ld_w, nc, u, u_stride, N, Nf, samples, inds, z_std);
+  snerf_launch<classic_sample_pdf_kernel>(dim3(blocks), dim3(LPR_THREADS), lds, 160 * 1024, (hipStream_t)stream, bins, ld_bins, mid_mode, weights,
+                                          ld_w, nc, u, u_stride, N, Nf, samples, inds, z_std);
   return snerf_check_launch();
 }
 
@@ -219,17 +217,11 @@ extern "C" int snerf_mip_resample(const float* s_vals, const float* weights, con
   const int rays = N <= 16384 ? 16 : 64;
   const size_t lds = (size_t)rays * (stride + (S + 1) + Nf) * sizeof(float);
   if ((size_t)64 * (stride + (S + 1) + Nf) * sizeof(float) > 160 * 1024) return SNERF_ERR_ARG;       // (one limit for every batch size)
-  static bool attr = false;
-  if (!attr) {
-    hipFuncSetAttribute((const void*)mip_resample_kernel<64>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    hipFuncSetAttribute((const void*)mip_resample_kernel<16>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr = true;
-  }
   const int blocks = (int)((N + rays - 1) / rays);
-  if (rays == 16) hipLaunchKernelGGL(mip_resample_kernel<16>, dim3(blocks), dim3(MRS_THREADS), lds, (hipStream_t)stream, s_vals, weights, u, u_stride, N, S,
-                                     Nf, resample_padding, out, idx_out);
-  else hipLaunchKernelGGL(mip_resample_kernel<64>, dim3(blocks), dim3(MRS_THREADS), lds, (hipStream_t)stream, s_vals, weights, u, u_stride, N, S,
-                          Nf, resample_padding, out, idx_out);
+  if (rays == 64) snerf_launch<mip_resample_kernel<64>>(dim3(blocks), dim3(MRS_THREADS), lds, 160 * 1024, (hipStream_t)stream, s_vals, weights, u, u_stride, N, S,
+                                                        Nf, resample_padding, out, idx_out);
+  else snerf_launch<mip_resample_kernel<16>>(dim3(blocks), dim3(MRS_THREADS), lds, 160 * 1024, (hipStream_t)stream, s_vals, weights, u, u_stride, N, S,
+                                             Nf, resample_padding, out, idx_out);
   return snerf_check_launch();
 }
 

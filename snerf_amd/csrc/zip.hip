@@ -898,14 +898,10 @@ static int zip_enc_launch(ZipEnc a, int C, int lds_levels, size_t lds_bytes, int
   if (BWD && lds_levels > 0) {
     const dim3 grid(256, lds_slabs);
     switch (C) {
-      case 1: (void)hipFuncSetAttribute((const void*)zip_encode_bwd_lds_kernel<OT, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-              hipLaunchKernelGGL((zip_encode_bwd_lds_kernel<OT, 1>), grid, blk, lds_bytes, s, a, lds_rows); break;
-      case 2: (void)hipFuncSetAttribute((const void*)zip_encode_bwd_lds_kernel<OT, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-              hipLaunchKernelGGL((zip_encode_bwd_lds_kernel<OT, 2>), grid, blk, lds_bytes, s, a, lds_rows); break;
-      case 4: (void)hipFuncSetAttribute((const void*)zip_encode_bwd_lds_kernel<OT, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-              hipLaunchKernelGGL((zip_encode_bwd_lds_kernel<OT, 4>), grid, blk, lds_bytes, s, a, lds_rows); break;
-      case 8: (void)hipFuncSetAttribute((const void*)zip_encode_bwd_lds_kernel<OT, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-              hipLaunchKernelGGL((zip_encode_bwd_lds_kernel<OT, 8>), grid, blk, lds_bytes, s, a, lds_rows); break;
+      case 1: snerf_launch<zip_encode_bwd_lds_kernel<OT, 1>>(grid, blk, lds_bytes, 160 * 1024, s, a, lds_rows); break;
+      case 2: snerf_launch<zip_encode_bwd_lds_kernel<OT, 2>>(grid, blk, lds_bytes, 160 * 1024, s, a, lds_rows); break;
+      case 4: snerf_launch<zip_encode_bwd_lds_kernel<OT, 4>>(grid, blk, lds_bytes, 160 * 1024, s, a, lds_rows); break;
+      case 8: snerf_launch<zip_encode_bwd_lds_kernel<OT, 8>>(grid, blk, lds_bytes, 160 * 1024, s, a, lds_rows); break;
       default: return SNERF_ERR_ARG;
     }
   }
@@ -1946,8 +1942,7 @@ extern "C" int snerf_zip_bin_scale(const void* grad_feat, long ld, long rows, in
 static int zb_accumulate_launch(const ZipEnc& a, const ZipBin& b, int C, int L, bool hrec, hipStream_t s) {
   const size_t lds = (size_t)(1 << b.bshift) * C * 8;
   const dim3 grid(ZB_NBMAX, L);
-#define ZBA(CC, HH) do { (void)hipFuncSetAttribute((const void*)zip_bin_accumulate_kernel<CC, HH, float>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-                         hipLaunchKernelGGL((zip_bin_accumulate_kernel<CC, HH, float>), grid, dim3(1024), lds, s, a, b); } while (0)
+#define ZBA(CC, HH) snerf_launch<zip_bin_accumulate_kernel<CC, HH, float>>(grid, dim3(1024), lds, 160 * 1024, s, a, b)
   if (hrec && C == 4) ZBA(4, true);
   else if (hrec && C == 1) ZBA(1, true);
   else if (C == 4) ZBA(4, false);
@@ -2908,8 +2903,7 @@ extern "C" int snerf_grid_encode_bwd_binned(const void* grad, const float* input
       a.starts = starts + (long)c * ZB_NBMAX;
       const long nwg_c = pl.nwg_total - (long)c * pl.wgs_per_chunk < pl.wgs_per_chunk ? pl.nwg_total - (long)c * pl.wgs_per_chunk : pl.wgs_per_chunk;
       const dim3 wgrid((unsigned)nwg_c);
-#define G3WR(GT, CC, HH) do { (void)hipFuncSetAttribute((const void*)g3_write_staged_kernel<GT, CC, HH>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)G3Cfg<CC, HH>::LDS); \
-                              hipLaunchKernelGGL((g3_write_staged_kernel<GT, CC, HH>), wgrid, dim3(G3_WT), (G3Cfg<CC, HH>::LDS), s, a); } while (0)
+#define G3WR(GT, CC, HH) snerf_launch<g3_write_staged_kernel<GT, CC, HH>>(wgrid, dim3(G3_WT), (G3Cfg<CC, HH>::LDS), (int)G3Cfg<CC, HH>::LDS, s, a)
       if (gsz == 2) {
         if (C == 4) { if (hrec) G3WR(_Float16, 4, true); else G3WR(_Float16, 4, false); }
         else if (C == 1) { if (hrec) G3WR(_Float16, 1, true); else G3WR(_Float16, 1, false); }
@@ -2921,8 +2915,7 @@ extern "C" int snerf_grid_encode_bwd_binned(const void* grad, const float* input
       }
 #undef G3WR
       ac.counts = counts_l + (long)c * ZB_NBMAX; ac.starts = a.starts; ac.first = c == 0; ac.last = c == pl.nck - 1;
-#define G3AC(CC, HH, GT) do { (void)hipFuncSetAttribute((const void*)g3_accumulate_kernel<CC, HH, GT>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-                              hipLaunchKernelGGL((g3_accumulate_kernel<CC, HH, GT>), dim3(ZB_NBMAX), dim3(1024), lds, s, ac); } while (0)
+#define G3AC(CC, HH, GT) snerf_launch<g3_accumulate_kernel<CC, HH, GT>>(dim3(ZB_NBMAX), dim3(1024), lds, 160 * 1024, s, ac)
       if (out_dtype == SNERF_DT_F16) {
         if (C == 4) { if (hrec) G3AC(4, true, _Float16); else G3AC(4, false, _Float16); }
         else if (C == 1) { if (hrec) G3AC(1, true, _Float16); else G3AC(1, false, _Float16); }

@@ -267,3 +267,142 @@ def test_fused_workspace_queries_without_a_gpu():
     assert many % 1408 == 0 and many == q("snerf_fcolour_bwd_ws_floats", 1 << 25)
     assert q("snerf_fchain_bwd_ws_floats", 1, 1 << 24) == many // 1408 * 1024 + 64
     assert q("snerf_fmlp_zip_chain_ws_floats", 1 << 24) == many // 1408 * 896 + 64
+
+
+# ---- the host statuses of the GEMM entries (csrc/gemm.hip) -----------------------------------------------------------------------------------
+_GEMM_M, _GEMM_N = 300, 256
+# snerf_linear_fwd over (dtype, variant) x (K in 128, 192, 256) x (act 0 .. 4) x (without, with column sums), M = 300, N = n_store = 256, a 16-bit
+# output: `x` = refused ("bad argument"), `.` = reaches a launch.  Read off the library before its launch code was folded into one table.
+_FWD_OTHER = "......xxxx" * 3          # no persistent kernel: no bit-mask activations
+_FWD_P8 = ".......x.." * 3             # the persistent kernel: everything but ReLU + bit mask with column sums
+_FWD_F8 = ".x.xxxxxxx" * 3             # fp16 + fp8: forward activations only, no column sums
+_FWD_REFUSED = {(dt, v): (_FWD_F8 if dt == 5 else _FWD_OTHER) for dt in (0, 1, 2, 4, 5) for v in (0, 1, 4, 8)}
+_FWD_REFUSED.update({(1, 8): _FWD_P8, (2, 8): _FWD_P8, (4, 8): _FWD_P8, (5, 8): ".x.xxx.xxx" * 3})
+
+
+def _gemm_ptr(mib=4):
+    """one buffer for EVERY operand of a case below: a zeroed device allocation of `mib` MiB where there is a GPU -- an accepted case, and a refused
+    one that a regression accepts, then runs on real memory --, else the aligned host address no refusal looks behind.  All pointers of a call
+    alias that one buffer on purpose: every layout in the lists fits into it, so whatever a kernel reads or writes stays inside the allocation;
+    the values it computes mean nothing and are not looked at (these tests are about statuses and launchability)."""
+    import torch
+    if not torch.cuda.is_available():
+        return _A, None
+    buf = torch.zeros(mib << 18, dtype=torch.float32, device="cuda")
+    return buf.data_ptr(), buf
+
+
+def _linear_fwd_status(P, dt, variant, K, act, cs, **over):
+    N = _GEMM_N
+    a = dict(A=P, lda=2 * K if dt in (4, 5) else K, W=P, ldw=3 * K if dt == 4 else 2 * K if dt == 5 else K, bias=None if act in (2, 4) else P,
+             Y=P, ldy=N if dt == 0 else 2 * N, aux=P if act >= 2 else None, ldaux=256 if act == 2 else 0, colsum=P if cs else None,
+             colsum_ws=P if cs else None, M=_GEMM_M, N=N, K=K, n_store=N, act=act, dtype=dt, out_f32=0, variant=variant, stream=None)
+    a.update(over)
+    return _lib.load().snerf_linear_fwd(*[a[name] for _, name in _lib.parse_header()["snerf_linear_fwd"]])
+
+
+def test_linear_fwd_keeps_its_refusals():
+    """snerf_linear_fwd refuses exactly the recorded (dtype, variant, K, act, column sums) combinations -- 258 of 600 -- and every
+    single-argument refusal it has; M <= 0 is OK before anything is looked at.  What is not refused reaches a launch ("launch failed"
+    without a device), so those cases get real device buffers where there is a GPU, and there every one of them launches."""
+    if not os.path.exists(_lib.LIB_PATH):
+        pytest.skip("library not built")
+    P, keep = _gemm_ptr()
+    n_refused = 0
+    for (dt, v), row in sorted(_FWD_REFUSED.items()):
+        cases = [(K, act, cs) for K in (128, 192, 256) for act in range(5) for cs in (False, True)]
+        for (K, act, cs), mark in zip(cases, row):
+            rc = _linear_fwd_status(P, dt, v, K, act, cs)
+            assert rc == (1 if mark == "x" else 2 if keep is None else 0), (dt, v, K, act, cs, rc)
+            n_refused += rc == 1
+    assert n_refused == 258
+    if keep is not None:
+        import torch
+        torch.cuda.synchronize()
+    bf16_p8 = dict(dt=1, variant=8, K=128)
+    for what, case in {
+            "N % 128": dict(dt=1, variant=0, K=128, act=0, cs=False, N=192, n_store=192),
+            "N <= 0": dict(dt=1, variant=0, K=128, act=0, cs=False, N=0),
+            "n_store > N": dict(dt=1, variant=0, K=128, act=0, cs=False, n_store=264),
+            "n_store <= 0": dict(dt=1, variant=0, K=128, act=0, cs=False, n_store=0),
+            "K % 64 (16-bit)": dict(dt=1, variant=0, K=96, act=0, cs=False),
+            "K % 32 (fp32)": dict(dt=0, variant=0, K=80, act=0, cs=False),
+            "K % 64 (split)": dict(dt=4, variant=8, K=96, act=0, cs=False),
+            "lda % 8": dict(dt=1, variant=0, K=128, act=0, cs=False, lda=132),
+            "ldw % 8": dict(dt=1, variant=0, K=128, act=0, cs=False, ldw=132),
+            "unknown dtype": dict(dt=3, variant=0, K=128, act=0, cs=False),
+            "unknown act": dict(dt=1, variant=0, K=128, act=5, cs=False),
+            "mask without aux": dict(dt=1, variant=0, K=128, act=2, cs=False, aux=None),
+            "mask with a bias": dict(dt=1, variant=0, K=128, act=2, cs=False, bias=P),
+            "misaligned bit mask (producer)": dict(bf16_p8, act=3, cs=False, aux=P + 2),
+            "misaligned bit mask (consumer)": dict(bf16_p8, act=4, cs=False, aux=P + 2),
+            "det without the 16-byte epilogue (ldy)": dict(dt=1, variant=256, K=128, act=0, cs=True, ldy=516),
+            "det without the 16-byte epilogue (no workspace)": dict(dt=1, variant=256, K=128, act=0, cs=True, colsum_ws=None),
+            "det without the 16-byte epilogue (ablation bit)": dict(dt=1, variant=256 | 128, K=128, act=0, cs=True),
+            "bit mask: no persistent variant": dict(dt=1, variant=4, K=128, act=3, cs=False),
+            "bit mask: N % 256": dict(bf16_p8, act=3, cs=False, N=384, n_store=384, ldy=768),
+            "bit mask: K < 128": dict(dt=1, variant=8, K=64, act=3, cs=False),
+            "bit mask: no 16-byte epilogue": dict(bf16_p8, act=4, cs=False, n_store=252),
+            "bit mask: fp32": dict(dt=0, variant=8, K=128, act=3, cs=False),
+            "split mask source with split operands": dict(dt=4, variant=8 | 1 << 14, K=128, act=2, cs=False),
+            "split mask source without a mask": dict(dt=1, variant=1 << 14, K=128, act=0, cs=False),
+            "fp16 + fp8: partial 64-column group": dict(dt=5, variant=8, K=256, act=0, cs=False, n_store=200),
+    }.items():
+        assert _linear_fwd_status(P, case.pop("dt"), case.pop("variant"), case.pop("K"), case.pop("act"), case.pop("cs"), **case) == 1, what
+    for M in (0, -1):                                                 # an empty batch: OK whatever else is passed
+        assert _linear_fwd_status(None, 1, 0, 128, 0, False, M=M) == 0
+        assert _linear_fwd_status(None, 3, 0, 100, 7, True, M=M, N=100, n_store=0) == 0
+
+
+def _wgrad_status(P, det=False, **over):
+    a = dict(Z=P, ldz=_GEMM_N, X=P, ldx=128, dW=P, ldw=128, zeros=P, M=_GEMM_M, N=_GEMM_N, K=128, n_valid=_GEMM_N, k_valid=128, dtype=1, variant=0,
+             ws=P, ws_floats=1 << 40, stream=None)
+    a.update(over)
+    if a["ws_floats"] == "short":
+        a["ws_floats"] = _lib.query("snerf_linear_wgrad_ws_floats", a["M"], a["N"], a["K"], a["ldz"], a["ldx"], a["dtype"], a["variant"]) - 1
+    name = "snerf_linear_wgrad_det" if det else "snerf_linear_wgrad"
+    return getattr(_lib.load(), name)(*[a[arg] for _, arg in _lib.parse_header()[name]])
+
+
+def test_linear_wgrad_keeps_its_refusals():
+    """snerf_linear_wgrad / snerf_linear_wgrad_det: every refusal of the weight-gradient host path, through both entries where both have it"""
+    if not os.path.exists(_lib.LIB_PATH):
+        pytest.skip("library not built")
+    # refusals and empty batches only: nothing is launched.  Where there is a GPU the pointers are still a device allocation that covers the
+    # largest case (the 8192 x 1024 16-bit operands: 16 MiB; the 64 MiB of partial tiles of the 1024-wide plans), so that a regression which
+    # accepts one of them runs on real memory
+    P, keep = _gemm_ptr(80)
+    both = {"no kernels for fp64": dict(dtype=3), "no kernels for fp16 + fp8": dict(dtype=5),
+            "split-bf16: N % 128": dict(dtype=4, N=192, ldz=192, n_valid=96), "split-bf16: K % 128": dict(dtype=4, K=192, ldx=192, k_valid=96),
+            "hi half of a split activation: fp32": dict(dtype=0, variant=1 << 14), "hi half of a split activation: split operands": dict(dtype=4, variant=1 << 14),
+            "N % 8": dict(N=260, ldz=264), "K % 8": dict(K=132, ldx=136), "ldz % 8": dict(ldz=260), "ldx % 8": dict(ldx=132),
+            "N % 4 (fp32)": dict(dtype=0, N=258, ldz=260), "K % 4 (fp32)": dict(dtype=0, K=130, ldx=132), "ldz % 4 (fp32)": dict(dtype=0, ldz=258),
+            "ldx % 4 (fp32)": dict(dtype=0, ldx=130), "N below a vector": dict(N=0), "K below a vector": dict(K=4), "no zero page": dict(zeros=None, M=320)}      # (whole 32-row stages: no row would be read from it)
+    for what, change in both.items():
+        for det in (False, True):
+            assert _wgrad_status(P, det, **change) == 1, (what, det)
+    assert _wgrad_status(P, True, dtype=4, N=256, K=128) == 1        # the split-bf16 operands have no deterministic fold
+    assert _wgrad_status(P, True, ws=None) == 1 and _wgrad_status(P, True, ws=None, M=0) == 1
+    for dt, variant in ((0, 0), (1, 0), (1, 2), (2, 3), (1, 128)):
+        assert _wgrad_status(P, True, dtype=dt, variant=variant, ws_floats="short") == 1, (dt, variant)
+    for M in (4096, 8192):                                            # the 1024-wide layer: 128 x 128 tiles below 512 rows per slice, 256 x 256 from there
+        assert _wgrad_status(P, True, M=M, N=1024, K=1024, ldz=1024, ldx=1024, n_valid=1024, k_valid=1024, ldw=1024, variant=2, ws_floats="short") == 1, M
+    for M in (0, -1):
+        assert _wgrad_status(None, False, M=M, dtype=3, N=1, K=1) == 0 and _wgrad_status(P, True, M=M, dtype=3, ws_floats=0) == 0
+    if keep is not None:
+        import torch
+        torch.cuda.synchronize()
+
+
+def test_linear_wgrad_workspace_query_pins_the_plan():
+    """snerf_linear_wgrad_ws_floats = slices x floats per slice of the launch plan (tn_plan), on both sides of each of its rules, at the 256 CUs
+    of an MI355X (also what the library assumes without a device): the 256 x 256 kernel (variant bit 1) from M = 4096 and from eight k-tiles per
+    slice up to M = 131072, the 128 x 128 kernel's 256-row floor below that.  ld = width, bf16."""
+    if not os.path.exists(_lib.LIB_PATH):
+        pytest.skip("library not built")
+    q = lambda M, N, K, variant: _lib.query("snerf_linear_wgrad_ws_floats", M, N, K, N, K, _BF16, variant)
+    for (M, N, K), expect in {(4096, 1024, 1024): (16777216, 16777216), (512, 1024, 1024): (2097152, 2097152), (32768, 256, 256): (8388608, 8388608),
+                              (700, 64, 128): (49152, 49152), (70001, 1024, 1152): (17694720, 15728640)}.items():
+        assert (q(M, N, K, 0), q(M, N, K, 3)) == expect, (M, N, K)
+    assert q(0, 256, 256, 0) == 0 and q(256, 0, 256, 0) == 0 and q(256, 256, -1, 3) == 0
+    assert _lib.query("snerf_linear_wgrad_ws_floats", 70001, 1024, 1152, 1024, 1152, _F16, 3) == 15728640      # fp16 runs the bf16 plan

@@ -83,13 +83,16 @@ def test_linear_dgrad_mask_colsum(ops, dt, variant, M):
 @pytest.mark.parametrize("dt,M,N,K,nv,kv", [(0, 700, 96, 128, 90, 127), (0, 5000, 256, 1120, 256, 1120), (1, 700, 64, 128, 3, 128),
                                             (1, 5000, 256, 320, 256, 283), (1, 3000, 1024, 1152, 1024, 1120), (1, 4100, 256, 128, 256, 96), (1, 2077, 128, 1024, 128, 1024),
                                             (1, 70001, 1024, 1152, 1024, 1120), (1, 9000, 256, 320, 256, 283), (1, 33000, 512, 256, 500, 256),
-                                            (2, 700, 64, 128, 3, 128), (2, 5000, 256, 320, 256, 283), (2, 70001, 1024, 1152, 1024, 1120), (2, 33000, 512, 256, 500, 256)])
+                                            (2, 700, 64, 128, 3, 128), (2, 5000, 256, 320, 256, 283), (2, 70001, 1024, 1152, 1024, 1120), (2, 33000, 512, 256, 500, 256),
+                                            (1, 700, 128, 128, 100, 128), (2, 700, 128, 128, 100, 128)])
 def test_linear_wgrad(ops, dt, M, N, K, nv, kv):
     tdt = ops.torch_dtype(dt)
     dZ = gen(M, N, seed=7).to(tdt).cuda()
     X = gen(M, K, seed=8).to(tdt).cuda()
     ref = 1.0 + (dZ.double().cpu().t() @ X.double().cpu())[:nv, :kv]
-    for variant in (0, 1, 2):                                       # 1 = transposing LDS reads (bf16, whole 128-column tiles), 2 = 8-phase 256x256
+    # 1 = transposing LDS reads (16-bit, whole 128-column tiles), 2 = 8-phase 256x256, bit 128 = the four-slot staging ring of the 128 x 128 kernel
+    # (the smallest shapes: each of its instantiations -- fp32, bf16 / fp16 with and without the transposing reads -- is launched once)
+    for variant in (0, 1, 2) + ((128, 129) if M == 700 else ()):
         dW = torch.ones(nv, kv, dtype=torch.float32, device="cuda")   # accumulates on top of existing content
         ops.linear_wgrad(dZ, X, dW, nv, kv, dt, variant=variant)
         close(dW, ref, 1e-4, 1e-3 * (M / 1000) ** 0.5, f"wgrad variant {variant}")
@@ -259,6 +262,48 @@ def test_relu_bit_mask_roundtrip(ops, M, N, K, dt):
         assert torch.equal(d1, d2)
         if with_cs:
             assert torch.allclose(cs1, cs2, rtol=1e-5, atol=1e-3)
+
+
+@pytest.mark.parametrize("K", [128, 192])
+@pytest.mark.parametrize("dt", [1, 2])
+def test_every_plain_16bit_gemm_flavour_launches(ops, dt, K):
+    """Every (activation, column sums) flavour the persistent kernel has for plain bf16 / fp16 operands, in the two-k-tile form (K = 128: its
+    own instantiations) and the general one, at the smallest shape that reaches them (two row tiles, the second ragged): against the float64
+    product of the rounded operands at the tolerances of test_linear_fwd / test_linear_dgrad_mask_colsum; the bit masks bit for bit."""
+    M, N = 300, 256
+    h16 = ops.torch_dtype(dt)
+    A = gen(M, K, seed=31).to(h16).cuda()
+    W = (gen(N, K, seed=32) / K ** 0.5).to(h16).cuda()
+    bias = gen(N, seed=33).cuda()
+    prod = A.double().cpu() @ W.double().cpu().t()
+    biased = prod + bias.double().cpu()
+    tol = {1: 1e-2, 2: 1.5e-3}[dt]
+
+    def run(act, bias=None, aux=None, colsum=False):
+        Y = torch.full((M, N), 7.0, dtype=h16, device="cuda")
+        cs = torch.zeros(N, dtype=torch.float32, device="cuda") if colsum else None
+        ops.linear_fwd(A, W, bias, Y, K, N, act, dt, aux=aux, colsum=cs, variant=8)
+        return Y, cs
+
+    assert ops.relu_bits_ok(A, W, torch.empty(M, N, dtype=h16, device="cuda"), K, N, dt, 8)      # the persistent kernel's conditions hold
+    close(run(ops.ACT_NONE, bias)[0], biased, tol, tol, "none")
+    y, cs = run(ops.ACT_NONE, colsum=True)
+    close(y, prod, tol, tol, "none + colsum")
+    close(cs, prod.sum(0), 2e-2, 5e-2, "colsum of none")
+    h_ref = run(ops.ACT_RELU, bias)[0]
+    close(h_ref, torch.relu(biased), tol, tol, "relu")
+    bits = torch.zeros(ops.mask_bits_words(M, N), dtype=torch.int32, device="cuda")
+    assert torch.equal(run(ops.ACT_RELU_BITS, bias, aux=bits)[0], h_ref)
+    masked = prod * (h_ref.double().cpu() > 0)
+    assert 0.2 < float((h_ref > 0).float().mean()) < 0.8
+    for with_cs in (False, True):
+        d1, cs1 = run(ops.ACT_MASK, aux=h_ref, colsum=with_cs)
+        d2, cs2 = run(ops.ACT_MASK_BITS, aux=bits, colsum=with_cs)
+        close(d1, masked, tol, tol, "mask")
+        assert torch.equal(d1, d2)
+        if with_cs:
+            close(cs1, masked.sum(0), 2e-2, 5e-2, "colsum of mask")
+            close(cs2, masked.sum(0), 2e-2, 5e-2, "colsum of bit mask")
 
 
 def test_gemm_operands_as_column_ranges(ops):
