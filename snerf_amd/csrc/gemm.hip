@@ -643,8 +643,13 @@ typedef __attribute__((address_space(3))) void* lds_ptr_t;
 // SPLIT: 0 = plain operands, 1 = split-bf16 (three bf16 passes), 2 = fp16 + fp8 (GemmNT::split == 2: fp16 tiles and e4m3 correction tiles
 // alternate -- virtual tile v is an fp16 tile for even v and lands in staging buffer v & 1, so the kind of a k-tile is its buffer index,
 // a compile-time constant of each copy of the k-tile body)
-template <int ACT, bool COLSUM, int SPLIT = 0, bool F16 = false, bool KT2 = false>
+// MSHAPE = 16 (plain 16-bit operands, three or more k-tiles): the same wave tile, registers, phases and LDS images on v_mfma_f32_16x16x32 -- a
+// 32-row block is two 16-row sub-blocks, a k-tile two reduction steps of 32, a 32 x 32 accumulator block four 16 x 16 quads (16 MFMAs per
+// phase instead of 8); the blocks marked MSHAPE == 16 below replace the fragment addresses, the accumulator <-> slab / bias maps and the k-tile
+// body, everything else is shared.  SNERF_NT_MFMA and nt8p_default_mshape below select it.
+template <int ACT, bool COLSUM, int SPLIT = 0, bool F16 = false, bool KT2 = false, int MSHAPE = 32>
 __global__ __launch_bounds__(512) void gemm_nt8p_kernel(GemmNT p) {
+  static_assert(MSHAPE == 32 || (MSHAPE == 16 && SPLIT == 0 && !KT2), "the split modes and the K = 128 instantiations stay on 32x32x16");
   static_assert(!(SPLIT && ACT == ACT_MASK), "split-bf16 data gradients take their ReLU masks from the bit masks");
   static_assert(SPLIT != 1 || !F16, "the three-pass split mode is a bf16 construction");
   static_assert(SPLIT != 2 || (F16 && !COLSUM && !KT2 && (ACT == ACT_NONE || ACT == ACT_RELU || ACT == ACT_RELU_BITS)),
@@ -761,6 +766,11 @@ __global__ __launch_bounds__(512) void gemm_nt8p_kernel(GemmNT p) {
   int cof[4];
 #pragma unroll
   for (int ks = 0; ks < 4; ++ks) cof[ks] = (lane & 31) * 128 + (((2 * ks + (lane >> 5)) ^ sw) << 4);
+  if constexpr (MSHAPE == 16) {
+    // fragment f = 2 sub + step: row 16 sub + (lane & 15), 16-byte chunk 4 step + (lane >> 4) (k = 32 step + 8 (lane >> 4) .. + 7), same image
+#pragma unroll
+    for (int f = 0; f < 4; ++f) cof[f] = ((f >> 1) * 16 + (lane & 15)) * 128 + (((4 * (f & 1) + (lane >> 4)) ^ ((lane & 15) >> 1)) << 4);
+  }
   const int fa = wr * 64 * 128, fb = wc * 32 * 128;
   bf16x8 aF[2][4], bS[2][4];                          // one A register set (replaced in place), two B sets
   auto lds_a = [&](int db, int h, int i2, int ks) __attribute__((always_inline)) {
@@ -776,6 +786,8 @@ __global__ __launch_bounds__(512) void gemm_nt8p_kernel(GemmNT p) {
     for (int j = 0; j < 2; ++j)
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  // MSHAPE 16: quad 2 ms + ns of block [i][j]: lane l holds row 16 ms + (l & 15), columns 16 ns + 4 (l >> 4) .. + 3 of the 32 x 32 block
+  f32x4 acc16[MSHAPE == 16 ? 4 : 1][2][4];
   int c_i = 0, c_kt = 0;                              // tile / k-tile the MFMAs are working on
   // ---- epilogue units --------------------------------------------------------------------------------------------
   char* const slab = smem + SCRATCH + (wave & 3) * 4096;
@@ -835,6 +847,37 @@ __global__ __launch_bounds__(512) void gemm_nt8p_kernel(GemmNT p) {
 #pragma unroll
     for (int part = 0; part < (SPLIT ? 2 : 1); ++part) {
     if (SPLIT && part == 1) __builtin_amdgcn_sched_barrier(0);   // nothing of the second pass may be scheduled into the first (its values would be live across it)
+    if constexpr (MSHAPE == 16) {
+      // the same two passes on the quads: quad c = (jj, ms, ns) is row 16 ms + (ln & 15), columns 32 jj + 16 ns + 4 (ln >> 4) .. + 3 -- chunk
+      // 4 jj + 2 ns + (ln >> 5) of the slab row, its upper 8 bytes for odd ln >> 4; the bias quad is the same for both ms
+      const int r16 = ln & 15, g4 = ln >> 4;
+      char* const s16 = slab + r16 * 128 + 8 * (g4 & 1);
+      const char* bl16 = smem + BIAS + (par ^ 1) * 1024 + wc * 256 + g4 * 16;
+#pragma unroll
+      for (int c = 0; c < 8; ++c) {
+        const int jj = c >> 2, ms = (c >> 1) & 1, ns = c & 1;
+        const f32x4 v = acc16[u][jj][2 * ms + ns];
+        const f32x2 v01 = {v[0], v[1]}, v23 = {v[2], v[3]};
+        u32x2 o;
+        if constexpr (F16) {
+          typedef __attribute__((ext_vector_type(2))) _Float16 f16x2;
+          o = u32x2{__builtin_bit_cast(unsigned, __builtin_convertvector(v01, f16x2)), __builtin_bit_cast(unsigned, __builtin_convertvector(v23, f16x2))};
+        } else {
+          o = u32x2{__builtin_bit_cast(unsigned, __builtin_convertvector(v01, bf16x2)), __builtin_bit_cast(unsigned, __builtin_convertvector(v23, bf16x2))};
+        }
+        if (ACT == ACT_RELU || ACT == ACT_RELU_BITS) {
+          typedef short s16x4 __attribute__((ext_vector_type(4)));
+          asm("" : "+v"(o));
+          o = __builtin_bit_cast(u32x2, __builtin_elementwise_max(__builtin_bit_cast(s16x4, o), s16x4{0, 0, 0, 0}));
+        }
+        *(u32x2*)(s16 + ms * 2048 + (((4 * jj + 2 * ns + (g4 >> 1)) ^ (r16 & 7)) << 4)) = o;
+      }
+#pragma unroll
+      for (int c = 0; c < 8; ++c) {
+        const int jj = c >> 2, ms = (c >> 1) & 1, ns = c & 1;
+        acc16[u][jj][2 * ms + ns] = *(const f32x4*)(bl16 + (32 * jj + 16 * ns) * 4);
+      }
+    } else {
 #pragma unroll
     for (int c = 0; c < 8; ++c) {
       const int jj = c >> 2, q = c & 3;
@@ -888,6 +931,7 @@ __global__ __launch_bounds__(512) void gemm_nt8p_kernel(GemmNT p) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) acc[u][c >> 2][4 * (c & 3) + e] = b[e];
       }
+    }
     }
     // No wait between the slab writes and the read-back: the LDS executes one wave's instructions in order, so the four reads below
     // queue right behind the writes (and behind the bias reads) and their latencies overlap -- one exposed LDS round trip per unit
@@ -1035,6 +1079,15 @@ __global__ __launch_bounds__(512) void gemm_nt8p_kernel(GemmNT p) {
         for (int e = 0; e < 4; ++e) acc[i][c >> 2][4 * (c & 3) + e] = b[e];
     }
   }
+  if constexpr (MSHAPE == 16) {
+    const char* bl0 = smem + BIAS + wc * 256 + (lane >> 4) * 16;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const f32x4 b = *(const f32x4*)(bl0 + c * 64);      // columns 16 c + 4 (lane >> 4) .. + 3
+#pragma unroll
+      for (int i = 0; i < 4; ++i) { acc16[i][c >> 1][c & 1] = b; acc16[i][c >> 1][2 + (c & 1)] = b; }
+    }
+  }
   __builtin_amdgcn_s_waitcnt(0xC07F);
   __builtin_amdgcn_sched_barrier(0);
   __builtin_amdgcn_s_barrier();
@@ -1044,6 +1097,109 @@ __global__ __launch_bounds__(512) void gemm_nt8p_kernel(GemmNT p) {
   origin(0, m0, n0);
   int em0 = 0, en0 = 0, epar = 0;
   bool pending = false, pending_mask = false;
+
+  if constexpr (MSHAPE == 16) {
+    // ---- 16 x 16 x 32 flavour: the load sections are those of the k-tile body below, the MFMA sections hold 16 MFMAs.  Fragment f = 2 sub + step
+    // (see cof); a fragment is replaced in place right after its last MFMA: an A fragment serves the two column sub-blocks (P2, P4), a B
+    // fragment the four row sub-blocks (P3); an accumulator quad is touched again eight MFMAs later at the earliest.
+    auto ktile16 = [&](auto db_tag) __attribute__((always_inline)) {
+      constexpr int db = decltype(db_tag)::value;
+      constexpr int F = db, S = 1 - db;
+      const bool last = c_kt == KT - 1;
+      // P1: A0 x B_F; fetch B_S of this k-tile
+      stage(db, 2 + F);
+      if (pending) unit(2, em0, en0, epar);
+      end_load();
+#pragma unroll
+      for (int f = 0; f < 4; ++f) bS[S][f] = lds_b(db, S, f);
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+        for (int q = 0; q < 8; ++q)                      // q = (i2, ms, ns)
+          mma16t<F16>(acc16[q >> 2][F][q & 3], bS[F][2 * (q & 1) + ks], aF[q >> 2][(q & 2) + ks]);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+        __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
+      }
+      end_mfma();
+      // P2: A0 x B_S; every A0 fragment is replaced by the A1 fragment of the same position
+      stage(db, 0);
+      if (pending) { unit(3, em0, en0, epar); if (en0 != n0) flush_colsum(em0, en0); pending = false; }
+      end_load();
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {                    // q = (i2, ms)
+          mma16t<F16>(acc16[q >> 1][S][2 * (q & 1)], bS[S][ks], aF[q >> 1][2 * (q & 1) + ks]);
+          mma16t<F16>(acc16[q >> 1][S][2 * (q & 1) + 1], bS[S][2 + ks], aF[q >> 1][2 * (q & 1) + ks]);
+          aF[q >> 1][2 * (q & 1) + ks] = lds_a(db, 1, q >> 1, 2 * (q & 1) + ks);
+        }
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
+        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+      }
+      end_mfma();
+      // P3: A1 x B_S; B_S is replaced by the first B half of the next k-tile
+      stage(db, 2 + S);
+      if (last) unit(0, m0, n0, c_i & 1);
+      if (pending_mask) { stage_mask(c_i); pending_mask = false; }
+      end_load();
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+        for (int ns = 0; ns < 2; ++ns) {
+#pragma unroll
+          for (int q = 0; q < 4; ++q)                    // q = (i2, ms)
+            mma16t<F16>(acc16[2 + (q >> 1)][S][2 * (q & 1) + ns], bS[S][2 * ns + ks], aF[q >> 1][2 * (q & 1) + ks]);
+          bS[S][2 * ns + ks] = lds_b(db ^ 1, S, 2 * ns + ks);
+        }
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
+        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+      }
+      end_mfma();
+      // P4: A1 x B_F; A1 is replaced by A0 of the next k-tile
+      stage(db, 1);
+      stream_next();
+      if (last) unit(1, m0, n0, c_i & 1);
+      if (c_kt == 0) stage_bias(c_i + 1);
+      end_load();
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          mma16t<F16>(acc16[2 + (q >> 1)][F][2 * (q & 1)], bS[F][ks], aF[q >> 1][2 * (q & 1) + ks]);
+          mma16t<F16>(acc16[2 + (q >> 1)][F][2 * (q & 1) + 1], bS[F][2 + ks], aF[q >> 1][2 * (q & 1) + ks]);
+          aF[q >> 1][2 * (q & 1) + ks] = lds_a(db ^ 1, 0, q >> 1, 2 * (q & 1) + ks);
+        }
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
+        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+      }
+      end_mfma();
+      if (last) {
+        pending = true; pending_mask = true; em0 = m0; en0 = n0; epar = c_i & 1;
+        c_kt = 0; ++c_i;
+        origin(c_i < n_my ? c_i : n_my - 1, m0, n0);
+      } else {
+        ++c_kt;
+      }
+    };
+    for (long t = 0; t < NT; t += 2) {
+      ktile16(std::integral_constant<int, 0>{});
+      if (t + 1 < NT) ktile16(std::integral_constant<int, 1>{});
+    }
+    if (wr == 0) __builtin_amdgcn_s_barrier();
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if (wr == 0) { unit(2, em0, en0, epar); unit(3, em0, en0, epar); flush_colsum(em0, en0); __builtin_amdgcn_s_waitcnt(0xC07F); }
+    __builtin_amdgcn_s_barrier();
+    if (wr == 1) { unit(2, em0, en0, epar); unit(3, em0, en0, epar); flush_colsum(em0, en0); }
+    return;
+  }
 
   auto ktile = [&](auto db_tag) __attribute__((always_inline)) {
     constexpr int db = decltype(db_tag)::value;
@@ -1288,10 +1444,27 @@ static int launch_nt8(const GemmNT& p, hipStream_t stream) {
 
 // One flavour of the persistent kernel, as a function the table below can point at.
 typedef void (*Nt8pLaunch)(int grid, const GemmNT& p, hipStream_t stream);
-template <int ACT, bool COLSUM, int SPLIT, bool F16, bool KT2 = false>
+template <int ACT, bool COLSUM, int SPLIT, bool F16, bool KT2 = false, int MSHAPE = 32>
 static void nt8p_go(int grid, const GemmNT& p, hipStream_t stream) {
   constexpr int LDS = 8 * 128 * 128 + 4 * 4096 + 2048 + 8192;
-  snerf_launch<gemm_nt8p_kernel<ACT, COLSUM, SPLIT, F16, KT2>>(dim3(grid), dim3(512), LDS, LDS, stream, p);
+  snerf_launch<gemm_nt8p_kernel<ACT, COLSUM, SPLIT, F16, KT2, MSHAPE>>(dim3(grid), dim3(512), LDS, LDS, stream, p);
+}
+
+// The MFMA shape of the persistent kernel's plain bf16 launches with three or more k-tiles (gemm_nt8p_kernel's MSHAPE).  SNERF_NT_MFMA = 16 | 32,
+// read at every launch (A/B runs, tests/test_nt_mfma_shape.py), picks the flavour and nothing else; fp16, the split modes and K = 128 have
+// the 32 flavour only, and so have the two (activation, column sums) pairs nt8p_plain does not list under 16.
+static int nt8p_forced_mshape() {
+  const char* e = getenv("SNERF_NT_MFMA");
+  if (e == nullptr) return 0;
+  const int v = atoi(e);
+  return v == 16 || v == 32 ? v : 0;
+}
+// Defaults per launch kind, by measurement on the 4096-ray step (profiles/r11_a_nt8p_mfma_shape.txt; the rule: below the parent's fastest round in
+// every round, per launch and on the headline).  bf16 forward flavours: 16 (-1.1 to -1.9 % per launch); bf16 data-gradient flavours: 16 (-2.6 to
+// -2.9 %); both together -0.33 to -0.45 ms per step.  fp16 has no 16 instantiation (not measured).
+static int nt8p_default_mshape(bool f16, int act, bool cs) {
+  (void)act; (void)cs;                                   // (both launch kinds met the rule; the arguments stay so that one kind can go back alone)
+  return f16 ? 32 : 16;
 }
 
 // Every (act, column sums, split flavour, K = 128) the persistent kernel is compiled for, per 16-bit format; anything else is refused
@@ -1300,7 +1473,17 @@ static void nt8p_go(int grid, const GemmNT& p, hipStream_t stream) {
 // Nothing the library does depends on that order: it is kept only so that a code object can be compared line for line with the one
 // built before these selections existed, and an edit that moves a line moves kernels, it changes none.)
 template <bool F16, bool KT2>
-static Nt8pLaunch nt8p_plain(int act, bool cs) {
+static Nt8pLaunch nt8p_plain(int act, bool cs, int mshape) {
+  if constexpr (!F16 && !KT2) {
+    if (mshape == 16) {                                  // (a pair without a 16 flavour falls through to its 32 flavour)
+      if (act == ACT_NONE && !cs) return nt8p_go<ACT_NONE, false, 0, false, false, 16>;
+      if (act == ACT_RELU && !cs) return nt8p_go<ACT_RELU, false, 0, false, false, 16>;
+      if (act == ACT_MASK && !cs) return nt8p_go<ACT_MASK, false, 0, false, false, 16>;
+      if (act == ACT_RELU_BITS && !cs) return nt8p_go<ACT_RELU_BITS, false, 0, false, false, 16>;
+      if (act == ACT_MASK_BITS && !cs) return nt8p_go<ACT_MASK_BITS, false, 0, false, false, 16>;
+      if (act == ACT_MASK_BITS && cs) return nt8p_go<ACT_MASK_BITS, true, 0, false, false, 16>;
+    }
+  }
   if (act == ACT_NONE && !cs) return nt8p_go<ACT_NONE, false, 0, F16, KT2>;
   if (act == ACT_RELU && !cs) return nt8p_go<ACT_RELU, false, 0, F16, KT2>;
   if (act == ACT_NONE && cs) return nt8p_go<ACT_NONE, true, 0, F16, KT2>;
@@ -1312,8 +1495,8 @@ static Nt8pLaunch nt8p_plain(int act, bool cs) {
   return nullptr;
 }
 template <bool F16>
-static Nt8pLaunch nt8p_flavour(int act, bool cs, int split, bool kt2) {
-  if (split == 0) return !kt2 ? nt8p_plain<F16, false>(act, cs) : nt8p_plain<F16, true>(act, cs);
+static Nt8pLaunch nt8p_flavour(int act, bool cs, int split, bool kt2, int mshape) {
+  if (split == 0) return !kt2 ? nt8p_plain<F16, false>(act, cs, mshape) : nt8p_plain<F16, true>(act, cs, 32);
   if (split == 2 && F16 && !cs) {                        // fp16 + fp8: forward activations only, no column sums
     if (act == ACT_NONE) return nt8p_go<ACT_NONE, false, 2, true>;
     if (act == ACT_RELU) return nt8p_go<ACT_RELU, false, 2, true>;
@@ -1342,7 +1525,8 @@ static int launch_nt8p(const GemmNT& p, hipStream_t stream) {
   const bool cs = p.colsum_ws != nullptr;
   // split-bf16 data gradient with a bias gradient: the flavour without column sums, then colsum_split_kernel over the output (see there)
   const bool cs_after = cs && p.split == 1 && p.act == ACT_MASK_BITS;
-  const Nt8pLaunch go = nt8p_flavour<F16>(p.act, cs && !cs_after, p.split, (p.K >> 6) == 2);
+  const int forced = nt8p_forced_mshape();
+  const Nt8pLaunch go = nt8p_flavour<F16>(p.act, cs && !cs_after, p.split, (p.K >> 6) == 2, forced ? forced : nt8p_default_mshape(F16, p.act, cs));
   if (go == nullptr) return SNERF_ERR_ARG;
   GemmNT q = p;
   if (cs_after) q.colsum_ws = nullptr;

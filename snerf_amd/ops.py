@@ -74,7 +74,9 @@ def zero_page(device):
 def linear_fwd(A, W, bias, Y, K, n_store, act, dt, out_f32=False, aux=None, colsum=None, variant=0, deterministic=False, aux_split=False):
     """Y[:, :n_store] = act(A[:, :K] @ W[:, :K]^T + bias); A/W/Y are 2-D views (row stride = ld).  `deterministic`: the bias-gradient
     partials (`colsum`) are folded in a fixed order.  `aux_split` (plain bf16 launch, ACT_MASK): the mask source is an activation a
-    split-bf16 forward saved (interleaved hi / lo; its hi half is tested)."""
+    split-bf16 forward saved (interleaved hi / lo; its hi half is tested).
+    The persistent kernel's plain bf16 launches with K >= 192 have two MFMA flavours (16 x 16 x 32: the default; 32 x 32 x 16: everything else);
+    the library reads SNERF_NT_MFMA = 16 | 32 at every launch (A/B runs, tests) and runs that flavour where both exist."""
     if deterministic:
         variant |= 256
     if aux_split and act == ACT_MASK:
