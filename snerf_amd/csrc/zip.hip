@@ -15,6 +15,7 @@
 //                         colour activations of MLP.forward (models.py:586, 689-703).
 #include "common.h"
 #include <stdlib.h>
+#include <type_traits>
 #include <hip/hip_fp16.h>
 
 #define ZIP_LANES 64
@@ -222,6 +223,52 @@ struct ZipEnc {
 #define ZIP_BX(a) ((a).lf ? blockIdx.x / (unsigned)(a).lf : blockIdx.x)
 #define ZIP_BY(a) ((a).lf ? blockIdx.x % (unsigned)(a).lf : blockIdx.y)
 #define ZIP_GX(a) ((a).lf ? gridDim.x / (unsigned)(a).lf : gridDim.x)
+
+// the one place a ZipEnc is filled in (host): the ray arrays, the grid and the scalars every entry has; what an entry does not set stays zero
+struct ZipRays { const float *tdist, *origins, *directions, *radii, *base_x, *base_y, *deg_jitter; };
+struct ZipGrid { const void* table; const int *offsets, *grid_sizes; };
+struct ZipDims { long R; int S, L, n, m; float Sl; int H; float std_scale; };
+static ZipEnc zip_enc(const ZipRays& r, const ZipGrid& g, const ZipDims& d) {
+  ZipEnc a{};
+  a.tdist = r.tdist; a.origins = r.origins; a.directions = r.directions; a.radii = r.radii; a.base_x = r.base_x; a.base_y = r.base_y;
+  a.deg_jitter = r.deg_jitter; a.table = g.table; a.offsets = g.offsets; a.grid_sizes = g.grid_sizes;
+  a.R = d.R; a.S = d.S; a.L = d.L; a.n = d.n; a.m = d.m; a.Sl = d.Sl; a.H = d.H; a.std_scale = d.std_scale;
+  return a;
+}
+
+// Host dispatch of this file: a runtime dtype, channel count or flag becomes a compile-time tag handed to a generic lambda, and whatever is
+// not listed is SNERF_ERR_ARG.  An entry nests these around its launch, so the instantiations an entry has are the lists written at its own
+// call and nowhere else (they differ per entry on purpose).  A lambda that only launches returns nothing: that counts as SNERF_OK.
+template <typename T> struct ZipType { using type = T; };
+template <typename Tag> using zip_t = typename Tag::type;
+static inline int zip_launched(int rc) { return rc != SNERF_OK ? rc : snerf_check_launch(); }     // a dispatch's refusal, else its launch's status
+template <typename F, typename... Tags> static inline int zip_with(F& f, Tags... tags) {
+  if constexpr (std::is_void_v<decltype(f(tags...))>) return f(tags...), SNERF_OK; else return f(tags...);
+}
+// H16: what an fp16 table is read as -- __half by the zip kernels, _Float16 by the g3 kernels, the same dtype number
+template <typename H16 = __half, typename F> static inline int zip_table_type(int dt, F f) {
+  return dt == SNERF_DT_F32 ? zip_with(f, ZipType<float>{}) : dt == SNERF_DT_F16 ? zip_with(f, ZipType<H16>{}) : SNERF_ERR_ARG;
+}
+template <typename F> static inline int zip_feat_type(int dt, F f) {
+  return dt == SNERF_DT_F32 ? zip_with(f, ZipType<float>{}) : dt == SNERF_DT_BF16 ? zip_with(f, ZipType<__bf16>{})
+       : dt == SNERF_DT_F16 ? zip_with(f, ZipType<_Float16>{}) : SNERF_ERR_ARG;
+}
+template <int... Vs, typename F> static inline int zip_one_of(int v, F f) {
+  int rc = SNERF_ERR_ARG;
+  (void)((v == Vs && ((rc = zip_with(f, std::integral_constant<int, Vs>{})), true)) || ...);
+  return rc;
+}
+template <typename F> static inline int zip_flag(bool on, F f) { return on ? zip_with(f, std::true_type{}) : zip_with(f, std::false_type{}); }
+// half records exist for C = 1 and C = 4 only: for other channel counts the half-record instantiation (G3Cfg<2, true>) is never named
+template <int C, typename F> static inline int zip_record_type(bool hrec, F f) {
+  if constexpr (C == 1 || C == 4) return zip_flag(hrec, f); else return zip_with(f, std::false_type{});
+}
+// the zip encode kernels' (table type, feature type, channels): fp32 / fp16 tables x fp32 / bf16 / fp16 features x the entry's own channel counts
+template <int... Cs, typename F> static inline int zip_enc_types(int table_dtype, int feat_dtype, int C, F f) {
+  return zip_table_type(table_dtype, [&](auto tt) {
+    return zip_feat_type(feat_dtype, [&](auto ot) { return zip_one_of<Cs...>(C, [&](auto c) { return zip_with(f, tt, ot, c); }); });
+  });
+}
 
 __device__ __forceinline__ uint32_t zip_hash3(const uint32_t* p) { return p[0] ^ (p[1] * 2654435761u) ^ (p[2] * 805459861u); }
 
@@ -485,6 +532,18 @@ struct ZipBin {
   // evaluation of the interval's multisamples (ngrp = 0: one level per thread, blockIdx.y = level); see snerf_zip_encode_fwd_count
   int ngrp; signed char grp[16][2];
 };
+// (host) bshift and ksplit of a C = 1 / 4 grid.  A level's bins = row ranges x replicas must fit the ZB_NBMAX-entry histograms of the
+// kernels (LDS cnt / base, counts [L, ZB_NBMAX], the accumulate grid): a table past 2^22 (C = 4) / 2^24 (C = 1) rows per level has more row
+// ranges than that -- refused here instead of corrupting LDS and dropping gradients (the caller falls back to the atomic scatter)
+static int zip_bin_levels(ZipBin& b, int C, int L, const int* level_rows_host, const int* ksplit_host) {
+  b.bshift = C == 4 ? 12 : 14;
+  for (int l = 0; l < L; ++l) {
+    const long rowbins = ((long)level_rows_host[l] + (1L << b.bshift) - 1) >> b.bshift;
+    if (level_rows_host[l] <= 0 || ksplit_host[l] < 1 || rowbins * ksplit_host[l] > ZB_NBMAX) return SNERF_ERR_ARG;
+    b.ksplit[l] = ksplit_host[l];
+  }
+  return SNERF_OK;
+}
 // HALF RECORDS (HREC; passes 5 / 6 / 7): the record's values travel as fp16 of value * 2^(scale_exp - ZB_HALF_SHIFT) -- the largest
 // |grad_feat| entry lands in [2^14, 2^15), fp16's subnormals reach 2^-39 of it, below the 2^-34 fixed-point grid -- 10 instead of 18
 // bytes per record of a four-channel grid ({row u16} + {4 x fp16}), 4 instead of 8 for a single-channel one ({row u16 | fp16} in one
@@ -825,14 +884,13 @@ extern "C" int snerf_zip_encode_prop_fwd(const float* tdist, const float* origin
   if (S <= 0 || L <= 0 || L > 16 || n <= 0 || n > 8 || hidden <= 0 || hidden > 1024 || table == nullptr || grid_sizes == nullptr || w1 == nullptr ||
       b1 == nullptr || w2 == nullptr || b2 == nullptr || raw_density == nullptr)
     return SNERF_ERR_ARG;
-  ZipEnc a{tdist, origins, directions, radii, base_x, base_y, deg_jitter, table, offsets, grid_sizes, nullptr, 0, nullptr, nullptr, R, S, L, n, m, Sl, H, std_scale};
+  const ZipEnc a = zip_enc({tdist, origins, directions, radii, base_x, base_y, deg_jitter}, {table, offsets, grid_sizes}, {R, S, L, n, m, Sl, H, std_scale});
   ZipPropMlp w{w1, b1, w2, b2, hidden, round_bf16, raw_density};
   const dim3 grid((unsigned)((R * S + 255) / 256)), blk(256);
   const size_t lds = (size_t)(hidden * L + 2 * hidden + 1) * sizeof(float);
-  if (table_dtype == SNERF_DT_F32) hipLaunchKernelGGL(zip_encode_prop_kernel<float>, grid, blk, lds, (hipStream_t)stream, a, w);
-  else if (table_dtype == 2) hipLaunchKernelGGL(zip_encode_prop_kernel<__half>, grid, blk, lds, (hipStream_t)stream, a, w);
-  else return SNERF_ERR_ARG;
-  return snerf_check_launch();
+  return zip_launched(zip_table_type(table_dtype, [&](auto tt) {
+    hipLaunchKernelGGL(zip_encode_prop_kernel<zip_t<decltype(tt)>>, grid, blk, lds, (hipStream_t)stream, a, w);
+  }));
 }
 
 template <typename OT, int C>
@@ -891,57 +949,31 @@ __global__ __launch_bounds__(256) void zip_encode_bwd_lds_kernel(ZipEnc a, int l
   }
 }
 
-template <typename TT, typename OT, bool BWD>
-static int zip_enc_launch(ZipEnc a, int C, int lds_levels, size_t lds_bytes, int lds_slabs, hipStream_t s) {
+template <typename TT, typename OT, int C, bool BWD>
+static int zip_enc_launch(ZipEnc a, int lds_levels, size_t lds_bytes, int lds_slabs, hipStream_t s) {
   const dim3 blk(256);
   const int lds_rows = (int)(lds_bytes / (C * 4));
-  if (BWD && lds_levels > 0) {
-    const dim3 grid(256, lds_slabs);
-    switch (C) {
-      case 1: snerf_launch<zip_encode_bwd_lds_kernel<OT, 1>>(grid, blk, lds_bytes, 160 * 1024, s, a, lds_rows); break;
-      case 2: snerf_launch<zip_encode_bwd_lds_kernel<OT, 2>>(grid, blk, lds_bytes, 160 * 1024, s, a, lds_rows); break;
-      case 4: snerf_launch<zip_encode_bwd_lds_kernel<OT, 4>>(grid, blk, lds_bytes, 160 * 1024, s, a, lds_rows); break;
-      case 8: snerf_launch<zip_encode_bwd_lds_kernel<OT, 8>>(grid, blk, lds_bytes, 160 * 1024, s, a, lds_rows); break;
-      default: return SNERF_ERR_ARG;
-    }
-  }
+  if (BWD && lds_levels > 0) snerf_launch<zip_encode_bwd_lds_kernel<OT, C>>(dim3(256, lds_slabs), blk, lds_bytes, 160 * 1024, s, a, lds_rows);
   if (!BWD && a.n <= 8) {
     const int lpt = a.level_begin > 0 ? min(a.level_begin, a.L) : 1;        // levels per thread (the caller's locality hint)
     a.level_begin = lpt;
     const dim3 grid((unsigned)((a.R * a.S + 255) / 256), (a.L + lpt - 1) / lpt);
-    switch (C) {
-      case 1: hipLaunchKernelGGL((zip_encode_fwd_all_kernel<TT, OT, 1>), grid, blk, 0, s, a, ZipBin{}); break;
-      case 2: hipLaunchKernelGGL((zip_encode_fwd_all_kernel<TT, OT, 2>), grid, blk, 0, s, a, ZipBin{}); break;
-      case 4: hipLaunchKernelGGL((zip_encode_fwd_all_kernel<TT, OT, 4>), grid, blk, 0, s, a, ZipBin{}); break;
-      case 8: hipLaunchKernelGGL((zip_encode_fwd_all_kernel<TT, OT, 8>), grid, blk, 0, s, a, ZipBin{}); break;
-      default: return SNERF_ERR_ARG;
-    }
+    hipLaunchKernelGGL((zip_encode_fwd_all_kernel<TT, OT, C>), grid, blk, 0, s, a, ZipBin{});
     return snerf_check_launch();
   }
   a.level_begin = BWD ? lds_levels : 0;
   const int nl = a.L - a.level_begin;
-  if (nl > 0) {
-    const dim3 grid((unsigned)((a.R * a.S + 255) / 256), nl);
-    switch (C) {
-      case 1: hipLaunchKernelGGL((zip_encode_kernel<TT, OT, 1, BWD>), grid, blk, 0, s, a); break;
-      case 2: hipLaunchKernelGGL((zip_encode_kernel<TT, OT, 2, BWD>), grid, blk, 0, s, a); break;
-      case 4: hipLaunchKernelGGL((zip_encode_kernel<TT, OT, 4, BWD>), grid, blk, 0, s, a); break;
-      case 8: hipLaunchKernelGGL((zip_encode_kernel<TT, OT, 8, BWD>), grid, blk, 0, s, a); break;
-      default: return SNERF_ERR_ARG;
-    }
-  }
+  if (nl > 0) hipLaunchKernelGGL((zip_encode_kernel<TT, OT, C, BWD>), dim3((unsigned)((a.R * a.S + 255) / 256), nl), blk, 0, s, a);
   return snerf_check_launch();
 }
 
+// snerf_zip_encode_fwd / _bwd: fp32 / fp16 tables x fp32 / bf16 / fp16 features x C = 1, 2, 4, 8.  (Not `if constexpr (BWD)` in the launch above:
+// both directions keep every kernel of the family in the code object, as they always have.)
 template <bool BWD>
 static int zip_enc_dispatch(const ZipEnc& a, int C, int table_dtype, int feat_dtype, int lds_levels, size_t lds_bytes, int lds_slabs, hipStream_t s) {
-  if (table_dtype == SNERF_DT_F32 && feat_dtype == SNERF_DT_F32) return zip_enc_launch<float, float, BWD>(a, C, lds_levels, lds_bytes, lds_slabs, s);
-  if (table_dtype == SNERF_DT_F32 && feat_dtype == SNERF_DT_BF16) return zip_enc_launch<float, __bf16, BWD>(a, C, lds_levels, lds_bytes, lds_slabs, s);
-  if (table_dtype == 2 && feat_dtype == SNERF_DT_F32) return zip_enc_launch<__half, float, BWD>(a, C, lds_levels, lds_bytes, lds_slabs, s);
-  if (table_dtype == 2 && feat_dtype == SNERF_DT_BF16) return zip_enc_launch<__half, __bf16, BWD>(a, C, lds_levels, lds_bytes, lds_slabs, s);
-  if (table_dtype == SNERF_DT_F32 && feat_dtype == SNERF_DT_F16) return zip_enc_launch<float, _Float16, BWD>(a, C, lds_levels, lds_bytes, lds_slabs, s);
-  if (table_dtype == 2 && feat_dtype == SNERF_DT_F16) return zip_enc_launch<__half, _Float16, BWD>(a, C, lds_levels, lds_bytes, lds_slabs, s);
-  return SNERF_ERR_ARG;
+  return zip_enc_types<1, 2, 4, 8>(table_dtype, feat_dtype, C, [&](auto tt, auto ot, auto c) {
+    return zip_enc_launch<zip_t<decltype(tt)>, zip_t<decltype(ot)>, decltype(c)::value, BWD>(a, lds_levels, lds_bytes, lds_slabs, s);
+  });
 }
 
 extern "C" int snerf_zip_encode_fwd(const float* tdist, const float* origins, const float* directions, const float* radii,
@@ -950,8 +982,8 @@ extern "C" int snerf_zip_encode_fwd(const float* tdist, const float* origins, co
                                     int m, float Sl, int H, float std_scale, int table_dtype, int feat_dtype, int levels_per_thread, void* stream) {
   if (R <= 0) return SNERF_OK;
   if (S <= 0 || L <= 0 || n <= 0 || ld < (long)L * C || table == nullptr || feat == nullptr || grid_sizes == nullptr || levels_per_thread < 0) return SNERF_ERR_ARG;
-  ZipEnc a{tdist, origins, directions, radii, base_x, base_y, deg_jitter, table, offsets, grid_sizes, feat, ld, nullptr, nullptr, R, S, L, n, m, Sl, H, std_scale};
-  a.level_begin = levels_per_thread;
+  ZipEnc a = zip_enc({tdist, origins, directions, radii, base_x, base_y, deg_jitter}, {table, offsets, grid_sizes}, {R, S, L, n, m, Sl, H, std_scale});
+  a.feat = feat; a.ld = ld; a.level_begin = levels_per_thread;
   return zip_enc_dispatch<false>(a, C, table_dtype, feat_dtype, 0, 0, 0, (hipStream_t)stream);
 }
 
@@ -1185,6 +1217,16 @@ __global__ __launch_bounds__(256) void zip_prop_fold_kernel(const float* __restr
   else g_w2[h] += s;
 }
 
+// the instantiations of the proposal-MLP pair: (feature dtype, rounding) in (bf16, 0), (bf16, 1), (f16, 2), (f32, 0), (f32, 1) x LM = 8 / 16
+// feature slots (L <= 8 or not).  f(feature type, rounding, LM)
+template <typename F> static int zpm_dispatch(int feat_dtype, int rnd, int L, F f) {
+  auto slots = [&](auto t, auto r) { return zip_one_of<8, 16>(L <= 8 ? 8 : 16, [&](auto lm) { f(t, r, lm); }); };
+  if (feat_dtype == SNERF_DT_BF16) return zip_one_of<0, 1>(rnd, [&](auto r) { return slots(ZipType<__bf16>{}, r); });
+  if (feat_dtype == SNERF_DT_F16) return zip_one_of<2>(rnd, [&](auto r) { return slots(ZipType<_Float16>{}, r); });
+  if (feat_dtype == SNERF_DT_F32) return zip_one_of<0, 1>(rnd, [&](auto r) { return slots(ZipType<float>{}, r); });
+  return SNERF_ERR_ARG;
+}
+
 extern "C" int snerf_zip_prop_mlp_ws_floats(int L, int hidden, long P) {
   const long tiles = (P + 255) / 256;
   const long wgs = tiles < 1024 ? (tiles < 1 ? 1 : tiles) : 1024;
@@ -1201,14 +1243,9 @@ extern "C" int snerf_zip_prop_mlp_fwd(const void* F, long ldf, long P, int L, co
   const long blocks = (P + 255) / 256;
   const dim3 grid((unsigned)(blocks < 8192 ? blocks : 8192)), blk(256);
   hipStream_t s = (hipStream_t)stream;
-#define ZPM_F(T, RN) do { if (L <= 8) hipLaunchKernelGGL((zip_prop_mlp_fwd_kernel<T, 8, RN>), grid, blk, 0, s, w); \
-                          else hipLaunchKernelGGL((zip_prop_mlp_fwd_kernel<T, 16, RN>), grid, blk, 0, s, w); } while (0)
-  if (feat_dtype == SNERF_DT_BF16) { if (round_bf16 == 1) ZPM_F(__bf16, 1); else if (round_bf16 == 0) ZPM_F(__bf16, 0); else return SNERF_ERR_ARG; }
-  else if (feat_dtype == SNERF_DT_F16) { if (round_bf16 == 2) ZPM_F(_Float16, 2); else return SNERF_ERR_ARG; }
-  else if (feat_dtype == SNERF_DT_F32) { if (round_bf16 == 1) ZPM_F(float, 1); else if (round_bf16 == 0) ZPM_F(float, 0); else return SNERF_ERR_ARG; }
-  else return SNERF_ERR_ARG;
-#undef ZPM_F
-  return snerf_check_launch();
+  return zip_launched(zpm_dispatch(feat_dtype, round_bf16, L, [&](auto t, auto r, auto lm) {
+    hipLaunchKernelGGL((zip_prop_mlp_fwd_kernel<zip_t<decltype(t)>, decltype(lm)::value, decltype(r)::value>), grid, blk, 0, s, w);
+  }));
 }
 
 // backward of snerf_zip_prop_mlp_fwd: dF [P, lddf] (columns L .. lddf - 1 zero) and g_* += the parameter gradients (fp32, the
@@ -1226,13 +1263,10 @@ extern "C" int snerf_zip_prop_mlp_bwd(const void* F, long ldf, const float* d_ra
   const int wgs = (int)(tiles < 1024 ? tiles : 1024);
   hipStream_t s = (hipStream_t)stream;
   const dim3 grid(wgs), blk(256);
-#define ZPM_B(T, RN) do { if (L <= 8) hipLaunchKernelGGL((zip_prop_mlp_bwd_kernel<T, 8, RN>), grid, blk, 0, s, w); \
-                          else hipLaunchKernelGGL((zip_prop_mlp_bwd_kernel<T, 16, RN>), grid, blk, 0, s, w); } while (0)
-  if (feat_dtype == SNERF_DT_BF16) { if (round_bf16 == 1) ZPM_B(__bf16, 1); else if (round_bf16 == 0) ZPM_B(__bf16, 0); else return SNERF_ERR_ARG; }
-  else if (feat_dtype == SNERF_DT_F16) { if (round_bf16 == 2) ZPM_B(_Float16, 2); else return SNERF_ERR_ARG; }
-  else if (feat_dtype == SNERF_DT_F32) { if (round_bf16 == 1) ZPM_B(float, 1); else if (round_bf16 == 0) ZPM_B(float, 0); else return SNERF_ERR_ARG; }
-  else return SNERF_ERR_ARG;
-#undef ZPM_B
+  const int rc = zpm_dispatch(feat_dtype, round_bf16, L, [&](auto t, auto r, auto lm) {
+    hipLaunchKernelGGL((zip_prop_mlp_bwd_kernel<zip_t<decltype(t)>, decltype(lm)::value, decltype(r)::value>), grid, blk, 0, s, w);
+  });
+  if (rc != SNERF_OK) return rc;
   const int n = hidden * (L + 2) + 1;
   hipLaunchKernelGGL(zip_prop_fold_kernel, dim3((n + 3) / 4), dim3(256), 0, s, ws, wgs, hidden, L, g_w1, g_b1, g_w2, g_b2);
   return snerf_check_launch();
@@ -1251,15 +1285,10 @@ extern "C" int snerf_zip_encode_fwd_count(const float* tdist, const float* origi
       grid_sizes == nullptr || ksplit_host == nullptr || level_rows_host == nullptr || counts == nullptr || wg_offsets == nullptr)
     return SNERF_ERR_ARG;
   ZipBin b{};
-  b.bshift = C == 4 ? 12 : 14;
-  for (int l = 0; l < L; ++l) {                         // (the same bound as snerf_zip_encode_bwd_binned)
-    const long rowbins = ((long)level_rows_host[l] + (1L << b.bshift) - 1) >> b.bshift;
-    if (level_rows_host[l] <= 0 || ksplit_host[l] < 1 || rowbins * ksplit_host[l] > ZB_NBMAX) return SNERF_ERR_ARG;
-    b.ksplit[l] = ksplit_host[l];
-  }
+  if (zip_bin_levels(b, C, L, level_rows_host, ksplit_host) != SNERF_OK) return SNERF_ERR_ARG;
   b.counts = counts; b.wg_offsets = (unsigned*)wg_offsets;
-  ZipEnc a{tdist, origins, directions, radii, base_x, base_y, deg_jitter, table, offsets, grid_sizes, feat, ld, nullptr, nullptr, R, S, L, n, m, Sl, H, std_scale};
-  a.level_begin = 1;
+  ZipEnc a = zip_enc({tdist, origins, directions, radii, base_x, base_y, deg_jitter}, {table, offsets, grid_sizes}, {R, S, L, n, m, Sl, H, std_scale});
+  a.feat = feat; a.ld = ld; a.level_begin = 1;
   // (2-D grid, level-major launch order: the workgroups in flight gather from ONE level's table.  Launched level-fastest the same kernel
   // takes 4.3 instead of 3.2 ms per proposal level and 5.5 instead of 4.8 on the NeRF level: profiles/r5_z_pathC_launch_order_ab.txt)
   int ny = L;
@@ -1282,17 +1311,9 @@ extern "C" int snerf_zip_encode_fwd_count(const float* tdist, const float* origi
   }
   const dim3 grid((unsigned)((R * S + 255) / 256), ny), blk(256);
   hipStream_t s = (hipStream_t)stream;
-#define ZFC(TT, OT) do { if (C == 4) hipLaunchKernelGGL((zip_encode_fwd_all_kernel<TT, OT, 4, true>), grid, blk, 0, s, a, b); \
-                         else hipLaunchKernelGGL((zip_encode_fwd_all_kernel<TT, OT, 1, true>), grid, blk, 0, s, a, b); } while (0)
-  if (table_dtype == SNERF_DT_F32 && feat_dtype == SNERF_DT_F32) ZFC(float, float);
-  else if (table_dtype == SNERF_DT_F32 && feat_dtype == SNERF_DT_BF16) ZFC(float, __bf16);
-  else if (table_dtype == 2 && feat_dtype == SNERF_DT_F32) ZFC(__half, float);
-  else if (table_dtype == 2 && feat_dtype == SNERF_DT_BF16) ZFC(__half, __bf16);
-  else if (table_dtype == SNERF_DT_F32 && feat_dtype == SNERF_DT_F16) ZFC(float, _Float16);
-  else if (table_dtype == 2 && feat_dtype == SNERF_DT_F16) ZFC(__half, _Float16);
-  else return SNERF_ERR_ARG;
-#undef ZFC
-  return snerf_check_launch();
+  return zip_launched(zip_enc_types<4, 1>(table_dtype, feat_dtype, C, [&](auto tt, auto ot, auto c) {
+    hipLaunchKernelGGL((zip_encode_fwd_all_kernel<zip_t<decltype(tt)>, zip_t<decltype(ot)>, decltype(c)::value, true>), grid, blk, 0, s, a, b);
+  }));
 }
 
 extern "C" int snerf_zip_encode_bwd(const float* tdist, const float* origins, const float* directions, const float* radii,
@@ -1303,7 +1324,8 @@ extern "C" int snerf_zip_encode_bwd(const float* tdist, const float* origins, co
   if (R <= 0) return SNERF_OK;
   if (S <= 0 || L <= 0 || n <= 0 || ld < (long)L * C || grad_feat == nullptr || grad_table == nullptr || grid_sizes == nullptr) return SNERF_ERR_ARG;
   if (grad_table_bf16 != nullptr && ((C % 2 != 0 && C != 1) || ((uintptr_t)grad_table_bf16) % 4 != 0)) return SNERF_ERR_ARG;
-  ZipEnc a{tdist, origins, directions, radii, base_x, base_y, deg_jitter, nullptr, offsets, grid_sizes, (void*)grad_feat, ld, grad_table, grad_table_bf16, R, S, L, n, m, Sl, H, std_scale};
+  ZipEnc a = zip_enc({tdist, origins, directions, radii, base_x, base_y, deg_jitter}, {nullptr, offsets, grid_sizes}, {R, S, L, n, m, Sl, H, std_scale});
+  a.feat = (void*)grad_feat; a.ld = ld; a.grad_table = grad_table; a.grad_table16 = grad_table_bf16;
   // the first lds_levels levels take the LDS-privatised path in slabs of lds_cells rows (lds_cells * C * 4 bytes <= 160 KB);
   // lds_slabs = sum over those levels of ceil(rows / lds_cells) (the host knows the level sizes)
   if (lds_levels < 0 || lds_levels > L || (lds_levels > 0 && (lds_cells <= 0 || lds_cells * C * 4 > 160 * 1024 || lds_slabs < lds_levels))) return SNERF_ERR_ARG;
@@ -1929,10 +1951,11 @@ extern "C" int snerf_zip_bin_scale(const void* grad_feat, long ld, long rows, in
   if (rows > 0) {
     const long total = rows * cols;
     const int grid = (int)(total / 256 / 8 + 1 < 2048 ? total / 256 / 8 + 1 : 2048);
-    if (feat_dtype == SNERF_DT_BF16) hipLaunchKernelGGL(zip_bin_absmax_kernel<__bf16>, dim3(grid), dim3(256), 0, s, (const __bf16*)grad_feat, ld, rows, cols, (unsigned*)(scale_exp + 1));
-    else if (feat_dtype == SNERF_DT_F16) hipLaunchKernelGGL(zip_bin_absmax_kernel<_Float16>, dim3(grid), dim3(256), 0, s, (const _Float16*)grad_feat, ld, rows, cols, (unsigned*)(scale_exp + 1));
-    else if (feat_dtype == SNERF_DT_F32) hipLaunchKernelGGL(zip_bin_absmax_kernel<float>, dim3(grid), dim3(256), 0, s, (const float*)grad_feat, ld, rows, cols, (unsigned*)(scale_exp + 1));
-    else return SNERF_ERR_ARG;
+    const int rc = zip_feat_type(feat_dtype, [&](auto ot) {
+      using OT = zip_t<decltype(ot)>;
+      hipLaunchKernelGGL(zip_bin_absmax_kernel<OT>, dim3(grid), dim3(256), 0, s, (const OT*)grad_feat, ld, rows, cols, (unsigned*)(scale_exp + 1));
+    });
+    if (rc != SNERF_OK) return rc;
   }
   hipLaunchKernelGGL(zip_bin_scale_kernel, dim3(1), dim3(1), 0, s, scale_exp, 0);
   return snerf_check_launch();
@@ -1942,17 +1965,26 @@ extern "C" int snerf_zip_bin_scale(const void* grad_feat, long ld, long rows, in
 static int zb_accumulate_launch(const ZipEnc& a, const ZipBin& b, int C, int L, bool hrec, hipStream_t s) {
   const size_t lds = (size_t)(1 << b.bshift) * C * 8;
   const dim3 grid(ZB_NBMAX, L);
-#define ZBA(CC, HH) snerf_launch<zip_bin_accumulate_kernel<CC, HH, float>>(grid, dim3(1024), lds, 160 * 1024, s, a, b)
-  if (hrec && C == 4) ZBA(4, true);
-  else if (hrec && C == 1) ZBA(1, true);
-  else if (C == 4) ZBA(4, false);
-  else if (C == 1) ZBA(1, false);
-  else return SNERF_ERR_ARG;
-#undef ZBA
+  const int rc = zip_one_of<4, 1>(C, [&](auto c) { return zip_flag(hrec, [&](auto h) {
+    snerf_launch<zip_bin_accumulate_kernel<decltype(c)::value, decltype(h)::value, float>>(grid, dim3(1024), lds, 160 * 1024, s, a, b);
+  }); });
+  if (rc != SNERF_OK) return rc;
   if (b.g64 != nullptr && b.g64_rows > 0)
     hipLaunchKernelGGL(zip_bin_finish_kernel<float>, dim3(1024), dim3(256), 0, s, (const long long*)b.g64, b.g64_rows * C, a.grad_table, b.scale_exp);
   hipLaunchKernelGGL(zip_bin_overflow_mark_kernel<float>, dim3(1), dim3(1), 0, s, a.grad_table, b.scale_exp);
   return snerf_check_launch();
+}
+
+// The pass numbers of snerf_zip_encode_bwd_binned (ABI) -> the pass proper (0 count, 1 write, 2 accumulate, 3 / 4 the direct / staged writer
+// of the A/B probes; anything else is refused), half records, all levels per thread whatever C:
+//   5 / 6 / 7 = 1 / 3 / 2 with HALF records (see ZB_HALF_SHIFT): the writers then need scale_exp too
+//   8 / 9 (probes) = 1 through the all-levels direct writer whatever C, with fp32 / half records
+struct ZipBinPass { int pass; bool hrec, force_all; };
+static ZipBinPass zip_bin_pass(int pass) {
+  const bool hrec = (pass >= 5 && pass <= 7) || pass == 9, force_all = pass == 8 || pass == 9;
+  if (force_all) pass = 1;
+  else if (hrec) pass = pass == 5 ? 1 : (pass == 6 ? 3 : 2);
+  return {pass, hrec, force_all};
 }
 
 // pass: 0 = count (+ reserve), 1 = write records, 2 = accumulate (+ finish).  The host zeroes counts / g64 and scans counts into starts.
@@ -1965,28 +1997,18 @@ extern "C" int snerf_zip_encode_bwd_binned(int pass, const float* tdist, const f
   if (R <= 0) return SNERF_OK;
   if (S <= 0 || L <= 0 || L > 16 || n <= 0 || (C != 1 && C != 4) || ksplit_host == nullptr || level_rows_host == nullptr || counts == nullptr)
     return SNERF_ERR_ARG;
-  // a level's bins = row ranges x replicas must fit the ZB_NBMAX-entry histograms of the kernels (LDS cnt / base, counts [L, ZB_NBMAX],
-  // the accumulate grid): a table past 2^22 (C = 4) / 2^24 (C = 1) rows per level has more row ranges than that -- refuse it here
-  // instead of corrupting LDS and dropping gradients (the caller falls back to the atomic scatter)
-  for (int l = 0; l < L; ++l) {
-    const long rowbins = ((long)level_rows_host[l] + (1L << (C == 4 ? 12 : 14)) - 1) >> (C == 4 ? 12 : 14);
-    if (level_rows_host[l] <= 0 || ksplit_host[l] < 1 || rowbins * ksplit_host[l] > ZB_NBMAX) return SNERF_ERR_ARG;
-  }
-  ZipEnc a{tdist, origins, directions, radii, base_x, base_y, deg_jitter, nullptr, offsets, grid_sizes, (void*)grad_feat, ld, grad_table, nullptr, R, S, L, n, m, Sl, H, std_scale};
   ZipBin b{};
-  b.bshift = C == 4 ? 12 : 14;
+  if (zip_bin_levels(b, C, L, level_rows_host, ksplit_host) != SNERF_OK) return SNERF_ERR_ARG;
+  ZipEnc a = zip_enc({tdist, origins, directions, radii, base_x, base_y, deg_jitter}, {nullptr, offsets, grid_sizes}, {R, S, L, n, m, Sl, H, std_scale});
+  a.feat = (void*)grad_feat; a.ld = ld; a.grad_table = grad_table;
   b.counts = counts; b.wg_offsets = (unsigned*)wg_offsets; b.starts = starts;
-  for (int l = 0; l < L; ++l) { b.ksplit[l] = ksplit_host[l]; if (b.ksplit[l] < 1) return SNERF_ERR_ARG; }
   b.rec_row = (unsigned short*)rec_row; b.rec_val = rec_val; b.capacity = capacity; b.g64 = (long long*)g64; b.g64_rows = g64_rows;
   b.scale_exp = scale_exp;
   hipStream_t s = (hipStream_t)stream;
   const dim3 blk(256);
-  // passes 5 / 6 / 7 = 1 / 3 / 2 with HALF records (see ZB_HALF_SHIFT): the writers then need scale_exp too
-  // passes 8 / 9 (probes): the all-levels direct writer whatever C, with fp32 / half records
-  const bool hrec = (pass >= 5 && pass <= 7) || pass == 9;
-  const bool force_all = pass == 8 || pass == 9;
-  if (force_all) pass = 1;
-  else if (hrec) pass = pass == 5 ? 1 : (pass == 6 ? 3 : 2);
+  const ZipBinPass decoded = zip_bin_pass(pass);
+  const bool hrec = decoded.hrec, force_all = decoded.force_all;
+  pass = decoded.pass;
   if (pass == 0 || pass == 1 || pass == 3 || pass == 4) {
     if (grad_feat == nullptr || wg_offsets == nullptr || (pass != 0 && (starts == nullptr || rec_row == nullptr || rec_val == nullptr)) || (hrec && scale_exp == nullptr))
       return SNERF_ERR_ARG;
@@ -2006,19 +2028,17 @@ extern "C" int snerf_zip_encode_bwd_binned(int pass, const float* tdist, const f
     static int lf_on = -1;
     if (lf_on < 0) { const char* e = getenv("SNERF_ZIP_WRITER_2D"); lf_on = (e != nullptr && e[0] == '1') ? 0 : 1; }   // (A/B switch)
     if (lf_on) { a_st.lf = L; grid_st = dim3(grid.x * (unsigned)L); }
-#define ZBE(OT, CC) do { if (pass == 0) hipLaunchKernelGGL((zip_bin_emit_kernel<OT, CC, 0>), grid, blk, 0, s, a, b); \
-                         else if (all_levels && hrec) hipLaunchKernelGGL((zip_bin_emit_all_kernel<OT, CC, true>), grid1, blk, 0, s, a, b); \
-                         else if (all_levels) hipLaunchKernelGGL((zip_bin_emit_all_kernel<OT, CC, false>), grid1, blk, 0, s, a, b); \
-                         else if (staged && hrec) hipLaunchKernelGGL((zip_bin_write_staged_kernel<OT, CC, 4, true>), grid_st, blk, 0, s, a_st, b); \
-                         else if (staged) hipLaunchKernelGGL((zip_bin_write_staged_kernel<OT, CC, 4>), grid_st, blk, 0, s, a_st, b); \
-                         else if (hrec) hipLaunchKernelGGL((zip_bin_emit_kernel<OT, CC, 1, true>), grid, blk, 0, s, a, b); \
-                         else hipLaunchKernelGGL((zip_bin_emit_kernel<OT, CC, 1>), grid, blk, 0, s, a, b); } while (0)
-    if (feat_dtype == SNERF_DT_BF16) { if (C == 4) ZBE(__bf16, 4); else ZBE(__bf16, 1); }
-    else if (feat_dtype == SNERF_DT_F16) { if (C == 4) ZBE(_Float16, 4); else ZBE(_Float16, 1); }
-    else if (feat_dtype == SNERF_DT_F32) { if (C == 4) ZBE(float, 4); else ZBE(float, 1); }
-    else return SNERF_ERR_ARG;
-#undef ZBE
-    return snerf_check_launch();
+    return zip_launched(zip_feat_type(feat_dtype, [&](auto ot) { return zip_one_of<4, 1>(C, [&](auto c) {
+      using OT = zip_t<decltype(ot)>;
+      constexpr int CC = decltype(c)::value;
+      if (pass == 0) { hipLaunchKernelGGL((zip_bin_emit_kernel<OT, CC, 0>), grid, blk, 0, s, a, b); return; }
+      zip_flag(hrec, [&](auto h) {
+        constexpr bool HREC = decltype(h)::value;
+        if (all_levels) hipLaunchKernelGGL((zip_bin_emit_all_kernel<OT, CC, HREC>), grid1, blk, 0, s, a, b);
+        else if (staged) hipLaunchKernelGGL((zip_bin_write_staged_kernel<OT, CC, 4, HREC>), grid_st, blk, 0, s, a_st, b);
+        else hipLaunchKernelGGL((zip_bin_emit_kernel<OT, CC, 1, HREC>), grid, blk, 0, s, a, b);
+      });
+    }); }));
   }
   if (pass != 2 || starts == nullptr || rec_row == nullptr || rec_val == nullptr || grad_table == nullptr || scale_exp == nullptr) return SNERF_ERR_ARG;
   return zb_accumulate_launch(a, b, C, L, hrec, s);
@@ -2131,13 +2151,10 @@ int g3_fwd_launch(const float* inputs, const void* table, const int* offsets, vo
   // (2 / 4 / 8 consecutive points per thread with the cell's corners kept in registers: slower, profiles/r5_a_grid_encoder_leg_and_sweep.txt)
   const bool pm = (size_t)C * (dtype == SNERF_DT_F16 ? 2 : 4) >= 8 && s_l == C && s_b == (long)L * C;   // point-major needs the [B, L*C] layout to pay
   const dim3 grid0((unsigned)((B * L + 255) / 256)), grid((unsigned)((B + 255) / 256), L), blk(256);
-#define G3F(TT, CC) do { if (pm) hipLaunchKernelGGL((g3_fwd_kernel<TT, CC, 0>), grid0, blk, 0, s, a); \
-                         else hipLaunchKernelGGL((g3_fwd_kernel<TT, CC, 1>), grid, blk, 0, s, a); } while (0)
-  if (dtype == SNERF_DT_F16) { if (C == 4) G3F(_Float16, 4); else if (C == 1) G3F(_Float16, 1); else if (C == 2) G3F(_Float16, 2); else if (C == 8) G3F(_Float16, 8); else return SNERF_ERR_ARG; }
-  else if (dtype == SNERF_DT_F32) { if (C == 4) G3F(float, 4); else if (C == 1) G3F(float, 1); else if (C == 2) G3F(float, 2); else if (C == 8) G3F(float, 8); else return SNERF_ERR_ARG; }
-  else return SNERF_ERR_ARG;
-#undef G3F
-  return snerf_check_launch();
+  return zip_launched(zip_table_type<_Float16>(dtype, [&](auto tt) { return zip_one_of<4, 1, 2, 8>(C, [&](auto c) {
+    if (pm) hipLaunchKernelGGL((g3_fwd_kernel<zip_t<decltype(tt)>, decltype(c)::value, 0>), grid0, blk, 0, s, a);
+    else hipLaunchKernelGGL((g3_fwd_kernel<zip_t<decltype(tt)>, decltype(c)::value, 1>), grid, blk, 0, s, a);
+  }); }));
 }
 
 // ---- table gradient of the stand-alone encoder (round 6): chunked, LDS-staged, bounded workspace ----------------------------------
@@ -2839,31 +2856,25 @@ extern "C" int snerf_grid_encode_bwd_binned_plan(long B, int C, int L, const int
   return SNERF_OK;
 }
 
-extern "C" int snerf_grid_encode_bwd_binned(const void* grad, const float* inputs, const int* offsets, const int* offsets_host, void* grad_embeddings,
-                                            long B, int C, int L, float S, int H, int grad_dtype, int out_dtype, long grad_stride_l,
-                                            long grad_stride_b, int half_records, void* ws, long ws_bytes, void* stream) {
-  if (B <= 0) return SNERF_OK;
-  if (L <= 0 || L > 16 || (C != 1 && C != 2 && C != 4 && C != 8) || grad == nullptr || inputs == nullptr || offsets == nullptr || offsets_host == nullptr ||
-      grad_embeddings == nullptr || ws == nullptr || ((uintptr_t)ws & 255) || (grad_dtype != SNERF_DT_F32 && grad_dtype != SNERF_DT_F16) ||
-      (out_dtype != SNERF_DT_F32 && out_dtype != SNERF_DT_F16))
-    return SNERF_ERR_ARG;
+// snerf_grid_encode_bwd_binned for a gradient of GT, a table gradient of ET and C channels
+template <typename GT, typename ET, int C>
+static int g3_bwd_binned(const void* grad, const float* inputs, const int* offsets, const int* offsets_host, void* grad_embeddings, long B, int L, float S,
+                         int H, long grad_stride_l, long grad_stride_b, int half_records, void* ws, long ws_bytes, hipStream_t s) {
   const bool hrec = half_records != 0 && (C == 1 || C == 4);              // (C = 2 / 8: fp32 records whatever the gradient's dtype)
   const bool point_major = grad_stride_l == C && grad_stride_b == (long)L * C, level_major = grad_stride_b == C && grad_stride_l == B * C;
   if (!point_major && !level_major) return SNERF_ERR_ARG;
-  const int gsz = grad_dtype == SNERF_DT_F16 ? 2 : 4;
+  const int gsz = sizeof(GT);
   G3Plan pl;
   if (g3_make_plan(B, C, L, offsets_host, hrec, !level_major, gsz, ws_bytes, &pl, nullptr) != SNERF_OK) return SNERF_ERR_ARG;
-  hipStream_t s = (hipStream_t)stream;
   char* base = (char*)ws;
   (void)hipMemsetAsync(base + pl.o_scale, 0, pl.zero_bytes, s);
   int* scale = (int*)(base + pl.o_scale);
   int* counts = (int*)(base + pl.o_counts);
   unsigned* starts = (unsigned*)(base + pl.o_starts);
   long long* g64 = pl.g64_rows > 0 ? (long long*)(base + pl.o_g64) : nullptr;
-  const size_t esz = out_dtype == SNERF_DT_F16 ? 2 : 4;
+  const size_t esz = sizeof(ET);
   if (level_major) {                                                     // the reference's own layout: max |grad| by the stream kernel
-    if (gsz == 2) hipLaunchKernelGGL(zip_bin_absmax_kernel<_Float16>, dim3(2048), dim3(256), 0, s, (const _Float16*)grad, (long)C, B * L, C, (unsigned*)(scale + 1));
-    else hipLaunchKernelGGL(zip_bin_absmax_kernel<float>, dim3(2048), dim3(256), 0, s, (const float*)grad, (long)C, B * L, C, (unsigned*)(scale + 1));
+    hipLaunchKernelGGL(zip_bin_absmax_kernel<GT>, dim3(2048), dim3(256), 0, s, (const GT*)grad, (long)C, B * L, C, (unsigned*)(scale + 1));
     hipLaunchKernelGGL(zip_bin_scale_kernel, dim3(1), dim3(1), 0, s, scale, 3);
   }
   const int RB = L * C * gsz;
@@ -2878,8 +2889,7 @@ extern "C" int snerf_grid_encode_bwd_binned(const void* grad, const float* input
       const int nl = L - l < pl.lt ? L - l : pl.lt;
       const dim3 tgrid((unsigned)((B + TP - 1) / TP));
       const size_t lds = (size_t)TP * RB;
-      if (gsz == 2) hipLaunchKernelGGL(g3_transpose_kernel<_Float16>, tgrid, dim3(256), lds, s, (const _Float16*)grad, B, L * C, C, l, nl, (_Float16*)(base + pl.o_tg), l == 0 ? (unsigned*)(scale + 1) : nullptr, TP);
-      else hipLaunchKernelGGL(g3_transpose_kernel<float>, tgrid, dim3(256), lds, s, (const float*)grad, B, L * C, C, l, nl, (float*)(base + pl.o_tg), l == 0 ? (unsigned*)(scale + 1) : nullptr, TP);
+      hipLaunchKernelGGL(g3_transpose_kernel<GT>, tgrid, dim3(256), lds, s, (const GT*)grad, B, L * C, C, l, nl, (GT*)(base + pl.o_tg), l == 0 ? (unsigned*)(scale + 1) : nullptr, TP);
       if (l == 0) hipLaunchKernelGGL(zip_bin_scale_kernel, dim3(1), dim3(1), 0, s, scale, 3);
     }
     a.level = l; a.K = pl.ks[l];
@@ -2903,38 +2913,32 @@ extern "C" int snerf_grid_encode_bwd_binned(const void* grad, const float* input
       a.starts = starts + (long)c * ZB_NBMAX;
       const long nwg_c = pl.nwg_total - (long)c * pl.wgs_per_chunk < pl.wgs_per_chunk ? pl.nwg_total - (long)c * pl.wgs_per_chunk : pl.wgs_per_chunk;
       const dim3 wgrid((unsigned)nwg_c);
-#define G3WR(GT, CC, HH) snerf_launch<g3_write_staged_kernel<GT, CC, HH>>(wgrid, dim3(G3_WT), (G3Cfg<CC, HH>::LDS), (int)G3Cfg<CC, HH>::LDS, s, a)
-      if (gsz == 2) {
-        if (C == 4) { if (hrec) G3WR(_Float16, 4, true); else G3WR(_Float16, 4, false); }
-        else if (C == 1) { if (hrec) G3WR(_Float16, 1, true); else G3WR(_Float16, 1, false); }
-        else if (C == 2) G3WR(_Float16, 2, false); else G3WR(_Float16, 8, false);
-      } else {
-        if (C == 4) { if (hrec) G3WR(float, 4, true); else G3WR(float, 4, false); }
-        else if (C == 1) { if (hrec) G3WR(float, 1, true); else G3WR(float, 1, false); }
-        else if (C == 2) G3WR(float, 2, false); else G3WR(float, 8, false);
-      }
-#undef G3WR
       ac.counts = counts_l + (long)c * ZB_NBMAX; ac.starts = a.starts; ac.first = c == 0; ac.last = c == pl.nck - 1;
-#define G3AC(CC, HH, GT) snerf_launch<g3_accumulate_kernel<CC, HH, GT>>(dim3(ZB_NBMAX), dim3(1024), lds, 160 * 1024, s, ac)
-      if (out_dtype == SNERF_DT_F16) {
-        if (C == 4) { if (hrec) G3AC(4, true, _Float16); else G3AC(4, false, _Float16); }
-        else if (C == 1) { if (hrec) G3AC(1, true, _Float16); else G3AC(1, false, _Float16); }
-        else if (C == 2) G3AC(2, false, _Float16); else G3AC(8, false, _Float16);
-      } else {
-        if (C == 4) { if (hrec) G3AC(4, true, float); else G3AC(4, false, float); }
-        else if (C == 1) { if (hrec) G3AC(1, true, float); else G3AC(1, false, float); }
-        else if (C == 2) G3AC(2, false, float); else G3AC(8, false, float);
-      }
-#undef G3AC
+      zip_record_type<C>(hrec, [&](auto h) {
+        constexpr bool HREC = decltype(h)::value;
+        snerf_launch<g3_write_staged_kernel<GT, C, HREC>>(wgrid, dim3(G3_WT), G3Cfg<C, HREC>::LDS, (int)G3Cfg<C, HREC>::LDS, s, a);
+        snerf_launch<g3_accumulate_kernel<C, HREC, ET>>(dim3(ZB_NBMAX), dim3(1024), lds, 160 * 1024, s, ac);
+      });
     }
-    if (pl.ks[l] > 1) {
-      if (out_dtype == SNERF_DT_F16) hipLaunchKernelGGL(zip_bin_finish_kernel<_Float16>, dim3(256), dim3(256), 0, s, (const long long*)g64, pl.rows[l] * C, (_Float16*)ac.out, scale);
-      else hipLaunchKernelGGL(zip_bin_finish_kernel<float>, dim3(256), dim3(256), 0, s, (const long long*)g64, pl.rows[l] * C, (float*)ac.out, scale);
-    }
+    if (pl.ks[l] > 1) hipLaunchKernelGGL(zip_bin_finish_kernel<ET>, dim3(256), dim3(256), 0, s, (const long long*)g64, pl.rows[l] * C, (ET*)ac.out, scale);
   }
-  if (out_dtype == SNERF_DT_F16) hipLaunchKernelGGL(zip_bin_overflow_mark_kernel<_Float16>, dim3(1), dim3(1), 0, s, (_Float16*)grad_embeddings, scale);
-  else hipLaunchKernelGGL(zip_bin_overflow_mark_kernel<float>, dim3(1), dim3(1), 0, s, (float*)grad_embeddings, scale);
+  hipLaunchKernelGGL(zip_bin_overflow_mark_kernel<ET>, dim3(1), dim3(1), 0, s, (ET*)grad_embeddings, scale);
   return snerf_check_launch();
+}
+
+extern "C" int snerf_grid_encode_bwd_binned(const void* grad, const float* inputs, const int* offsets, const int* offsets_host, void* grad_embeddings,
+                                            long B, int C, int L, float S, int H, int grad_dtype, int out_dtype, long grad_stride_l,
+                                            long grad_stride_b, int half_records, void* ws, long ws_bytes, void* stream) {
+  if (B <= 0) return SNERF_OK;
+  if (L <= 0 || L > 16 || grad == nullptr || inputs == nullptr || offsets == nullptr || offsets_host == nullptr || grad_embeddings == nullptr ||
+      ws == nullptr || ((uintptr_t)ws & 255))
+    return SNERF_ERR_ARG;
+  return zip_table_type<_Float16>(grad_dtype, [&](auto gt) {           // the gradient and the table gradient: fp32 or fp16 each
+    return zip_table_type<_Float16>(out_dtype, [&](auto et) { return zip_one_of<1, 2, 4, 8>(C, [&](auto c) {
+      return g3_bwd_binned<zip_t<decltype(gt)>, zip_t<decltype(et)>, decltype(c)::value>(
+          grad, inputs, offsets, offsets_host, grad_embeddings, B, L, S, H, grad_stride_l, grad_stride_b, half_records, ws, ws_bytes, (hipStream_t)stream);
+    }); });
+  });
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -3140,23 +3144,14 @@ extern "C" int snerf_zip_encode_ray_bwd(const float* tdist, const float* origins
   if (S <= 0 || L <= 0 || n <= 0 || table == nullptr || grad_feat == nullptr || g_origins == nullptr || g_directions == nullptr ||
       g_base_x == nullptr || g_base_y == nullptr || (C != 1 && C != 4))
     return SNERF_ERR_ARG;
-  ZipEnc a{};
-  a.tdist = tdist; a.origins = origins; a.directions = directions; a.radii = radii; a.base_x = base_x; a.base_y = base_y;
-  a.deg_jitter = deg_jitter; a.table = table; a.offsets = offsets; a.grid_sizes = grid_sizes; a.feat = (void*)grad_feat; a.ld = ld;
-  a.R = R; a.S = S; a.L = L; a.n = n; a.m = m; a.Sl = Sl; a.H = H; a.std_scale = std_scale;
+  ZipEnc a = zip_enc({tdist, origins, directions, radii, base_x, base_y, deg_jitter}, {table, offsets, grid_sizes}, {R, S, L, n, m, Sl, H, std_scale});
+  a.feat = (void*)grad_feat; a.ld = ld;
   const dim3 grid((unsigned)((R * S + 255) / 256)), block(256);
   hipStream_t s = (hipStream_t)stream;
-  // table: fp32 (0) or fp16 (2); gradient features: fp32 (0), bf16 (1) or fp16 (2)
-#define ZRB(TT, OT, CC) hipLaunchKernelGGL((zip_encode_ray_bwd_kernel<TT, OT, CC>), grid, block, 0, s, a, g_origins, g_directions, g_base_x, g_base_y)
-  if (table_dtype == 2 && feat_dtype == SNERF_DT_BF16) { if (C == 4) ZRB(__half, __bf16, 4); else ZRB(__half, __bf16, 1); }
-  else if (table_dtype == 2 && feat_dtype == SNERF_DT_F32) { if (C == 4) ZRB(__half, float, 4); else ZRB(__half, float, 1); }
-  else if (table_dtype == 0 && feat_dtype == SNERF_DT_BF16) { if (C == 4) ZRB(float, __bf16, 4); else ZRB(float, __bf16, 1); }
-  else if (table_dtype == 0 && feat_dtype == SNERF_DT_F32) { if (C == 4) ZRB(float, float, 4); else ZRB(float, float, 1); }
-  else if (table_dtype == 2 && feat_dtype == SNERF_DT_F16) { if (C == 4) ZRB(__half, _Float16, 4); else ZRB(__half, _Float16, 1); }
-  else if (table_dtype == 0 && feat_dtype == SNERF_DT_F16) { if (C == 4) ZRB(float, _Float16, 4); else ZRB(float, _Float16, 1); }
-  else return SNERF_ERR_ARG;
-#undef ZRB
-  return snerf_check_launch();
+  return zip_launched(zip_enc_types<4, 1>(table_dtype, feat_dtype, C, [&](auto tt, auto ot, auto c) {
+    hipLaunchKernelGGL((zip_encode_ray_bwd_kernel<zip_t<decltype(tt)>, zip_t<decltype(ot)>, decltype(c)::value>), grid, block, 0, s, a, g_origins, g_directions,
+                       g_base_x, g_base_y);
+  }));
 }
 
 // ------------------------------------------------------------------------------------------------------------------

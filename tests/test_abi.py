@@ -406,3 +406,174 @@ def test_linear_wgrad_workspace_query_pins_the_plan():
         assert (q(M, N, K, 0), q(M, N, K, 3)) == expect, (M, N, K)
     assert q(0, 256, 256, 0) == 0 and q(256, 0, 256, 0) == 0 and q(256, 256, -1, 3) == 0
     assert _lib.query("snerf_linear_wgrad_ws_floats", 70001, 1024, 1152, 1024, 1152, _F16, 3) == 15728640      # fp16 runs the bf16 plan
+
+
+# ---- the host statuses of the hash-grid entries (csrc/zip.hip) --------------------------------------------------------------------------------
+_ZC = (1, 2, 3, 4, 8)
+_ZIP_SELF_CONTAINED = ("snerf_zip_encode_fwd", "snerf_zip_encode_prop_fwd", "snerf_zip_prop_mlp_fwd", "snerf_zip_prop_mlp_bwd", "snerf_zip_encode_fwd_count",
+                       "snerf_zip_encode_bwd", "snerf_zip_encode_ray_bwd", "snerf_zip_bin_scale")
+# Per entry: the axes of its dtype / channel / flavour arguments and, over their full cross product (last axis fastest), `x` = refused
+# ("bad argument"), `.` = reaches a launch.  Read off the library before the entries' type ladders were folded into one dispatch.
+_ZIP_CROSS = {
+    "snerf_zip_encode_fwd": (dict(table_dtype=range(4), feat_dtype=range(4), C=_ZC),
+                             "..x.. ..x.. ..x.. xxxxx  xxxxx xxxxx xxxxx xxxxx  ..x.. ..x.. ..x.. xxxxx  xxxxx xxxxx xxxxx xxxxx"),
+    "snerf_zip_encode_prop_fwd": (dict(table_dtype=range(4)), ".x.x"),
+    "snerf_zip_prop_mlp_fwd": (dict(feat_dtype=range(4), round_bf16=range(4), L=(2, 12)), "....xxxx ....xxxx xxxx..xx xxxxxxxx"),
+    "snerf_zip_prop_mlp_bwd": (dict(feat_dtype=range(4), round_bf16=range(4), L=(2, 12)), "....xxxx ....xxxx xxxx..xx xxxxxxxx"),
+    "snerf_zip_encode_fwd_count": (dict(table_dtype=range(4), feat_dtype=range(4), C=_ZC),
+                                   ".xx.x .xx.x .xx.x xxxxx  xxxxx xxxxx xxxxx xxxxx  .xx.x .xx.x .xx.x xxxxx  xxxxx xxxxx xxxxx xxxxx"),
+    "snerf_zip_encode_bwd": (dict(feat_dtype=range(4), C=_ZC, lds_levels=(0, 1)), "....xx.... ....xx.... ....xx.... xxxxxxxxxx"),
+    "snerf_zip_encode_ray_bwd": (dict(table_dtype=range(4), feat_dtype=range(4), C=_ZC),
+                                 ".xx.x .xx.x .xx.x xxxxx  xxxxx xxxxx xxxxx xxxxx  .xx.x .xx.x .xx.x xxxxx  xxxxx xxxxx xxxxx xxxxx"),
+    "snerf_zip_bin_scale": (dict(feat_dtype=range(4)), "...x"),
+    # (passes -1 .. 10 per channel count; the accumulate passes 2 and 7 never look at the gradient's dtype)
+    "snerf_zip_encode_bwd_binned": (dict(feat_dtype=range(4), C=_ZC, **{"pass": range(-1, 11)}),
+                                    "x..........x xxxxxxxxxxxx xxxxxxxxxxxx x..........x xxxxxxxxxxxx " * 3
+                                    + "xxx.xxxx.xxx xxxxxxxxxxxx xxxxxxxxxxxx xxx.xxxx.xxx xxxxxxxxxxxx"),
+    # (gradient fp32 / fp16 x table gradient fp32 / fp16; half records asked for at C = 2 / 8 are fp32 records, not a refusal)
+    "snerf_grid_encode_bwd_binned": (dict(grad_dtype=range(4), out_dtype=range(4), C=_ZC, half_records=(0, 1)),
+                                     ("....xx.... xxxxxxxxxx ....xx.... xxxxxxxxxx " + "x" * 40) * 2),
+}
+# snerf_zip_encode_bwd_binned, pass -1 .. 10 (columns) with one pointer absent (rows; the first row: none absent), C = 4, bf16 gradients
+_ZIP_PASS_PTRS = ("grad_feat", "grad_table", "ksplit_host", "level_rows_host", "counts", "wg_offsets", "starts", "rec_row", "rec_val", "scale_exp")
+_ZIP_PASSES = """x..........x xxx.xxxx.xxx x..x....x..x xxxxxxxxxxxx xxxxxxxxxxxx xxxxxxxxxxxx xxx.xxxx.xxx x.xxxxxxxxxx x.xxxxxxxxxx x.xxxxxxxxxx
+                 x..x..xxx.xx"""
+
+
+def _zip_problem():
+    """Real operands of one tiny problem for every hash-grid entry: R = 4 rays x S = 2 intervals, L = 2 levels (one dense, one hashed; the
+    layout of ops.grid_level_layout), n = 7 multisamples, every buffer sized for the widest case of the lists (C = 8, 4-byte elements), on the
+    device where there is one -- an accepted case then runs on valid memory -- and on the host otherwise (no launch happens there).  The
+    `*_host` arrays are numpy: the library reads them on the host.  -> ({argument name: value}, what must stay alive)"""
+    import numpy as np
+    import torch
+    from snerf_amd import ops
+    dev = "cuda" if torch.cuda.is_available() else "cpu"
+    R, S, L, n, B = 4, 2, 2, 7, 8
+    g = torch.Generator().manual_seed(12)
+    rnd = lambda *shape: torch.randn(*shape, generator=g)
+    unit = lambda t: torch.nn.functional.normalize(t, dim=-1)
+    off, sizes = ops.grid_level_layout(3, L, 2.0, 16, 12)               # 17^3 -> 4920 rows (dense), 33^3 -> 4096 rows (hashed)
+    rows = int(off[-1])
+    d = unit(rnd(R, 3))
+    bx = unit(torch.cross(d, rnd(R, 3), dim=-1))
+    t = dict(tdist=torch.sort(torch.rand(R, S + 1, generator=g) * 5 + 0.2, -1)[0], origins=rnd(R, 3) * 0.1, directions=d,
+             radii=2e-3 + 2e-3 * torch.rand(R, generator=g), base_x=bx, base_y=unit(torch.cross(d, bx, dim=-1)),
+             deg_jitter=torch.rand(R, S, n, generator=g), table=rnd(rows, 8) * 0.1, offsets=torch.from_numpy(off), grid_sizes=torch.from_numpy(sizes),
+             feat=torch.zeros(R * S, 16), grad_feat=rnd(R * S, 16) * 1e-3, grad_table=torch.zeros(rows, 8), grad_table_bf16=torch.zeros(rows, 8),
+             w1=rnd(8, 16) * 0.3, b1=rnd(8) * 0.1, w2=rnd(8) * 0.3, b2=rnd(1), raw_density=torch.zeros(R * S), raw=torch.zeros(R * S),
+             F=rnd(R * S, 16) * 0.5, d_raw=rnd(R * S) * 1e-3, dF=torch.zeros(R * S, 16), g_w1=torch.zeros(8, 16), g_b1=torch.zeros(8), g_w2=torch.zeros(8),
+             g_b2=torch.zeros(1), counts=torch.zeros(L, 1024, dtype=torch.int32), wg_offsets=torch.zeros(L, 1024, dtype=torch.int32),
+             starts=torch.zeros(L, 1024, dtype=torch.int64), rec_row=torch.zeros(4096, dtype=torch.int16), rec_val=torch.zeros(4096, 8),
+             g64=torch.zeros(rows, 8, dtype=torch.int64), scale_exp=torch.zeros(2, dtype=torch.int32), g_origins=torch.zeros(R, 3),
+             g_directions=torch.zeros(R, 3), g_base_x=torch.zeros(R, 3), g_base_y=torch.zeros(R, 3), grad=rnd(B, L * 8) * 1e-3,
+             inputs=torch.rand(B, 3, generator=g), grad_embeddings=torch.zeros(rows, 8))
+    t = {k: v.to(dev).contiguous() for k, v in t.items()}
+    host = dict(ksplit_host=np.ones(L, dtype=np.int32), level_rows_host=np.diff(off).astype(np.int32), offsets_host=np.ascontiguousarray(off))
+    ws_bytes = max(_lib.query("snerf_grid_encode_bwd_binned_ws_bytes", B, C, L, host["offsets_host"].ctypes.data, 0) for C in (1, 2, 4, 8))
+    t["ws"] = torch.zeros(ws_bytes + 256, dtype=torch.uint8, device=dev)
+    a = {k: v.data_ptr() for k, v in t.items()}
+    a.update({k: v.ctypes.data for k, v in host.items()})
+    a["ws"] = (a["ws"] + 255) & ~255                                    # (the stand-alone encoder's workspace must be 256-byte aligned)
+    a.update(R=R, S=S, L=L, n=n, m=3, Sl=1.0, H=16, std_scale=0.35, C=4, ld=16, table_dtype=_F32, feat_dtype=_BF16, levels_per_thread=0, hidden=8,
+             round_bf16=1, P=R * S, ldf=16, lddf=16, ws_floats=_lib.query("snerf_zip_prop_mlp_ws_floats", 12, 8, R * S), lds_levels=0, lds_cells=0,
+             lds_slabs=0, rows=R * S, cols=4, capacity=4096, g64_rows=0, B=B, grad_dtype=_F32, out_dtype=_F32, half_records=0, ws_bytes=ws_bytes,
+             stream=None)
+    a["pass"] = 0
+    a["grad_table_bf16"], a["bf16_image"] = None, a["grad_table_bf16"]  # (optional: absent unless a case asks for it)
+    return a, (t, host)
+
+
+def _zip_status(name, a, **over):
+    v = dict(a, **over)
+    if name == "snerf_grid_encode_bwd_binned":                         # (its S is the levels' log2 growth; the gradient is point-major [B, L C])
+        v["S"] = 1.0
+        v.setdefault("grad_stride_l", v["C"])
+        v.setdefault("grad_stride_b", v["L"] * v["C"])
+    if v["lds_levels"] == 1 and "lds_cells" not in over:               # level 0 (4920 rows) as one LDS slab: 4920 C floats <= 160 KiB up to C = 8
+        v.update(lds_cells=4920, lds_slabs=1)
+    return getattr(_lib.load(), name)(*[v[arg] for _, arg in _lib.parse_header()[name]])
+
+
+def _zip_rows_host(*rows):
+    import numpy as np
+    return np.array(rows, dtype=np.int32)
+
+
+def _zip_refusals(a):
+    """every single-argument refusal of each entry: {entry: [change, ...]} against the accepted base case (C = 4, fp32 table, bf16 features)"""
+    big, zero, k0 = _zip_rows_host(4913, 1 << 23), _zip_rows_host(4920, 0), _zip_rows_host(1, 0)     # 2^23 rows at C = 4: 2048 row ranges
+    per_level = [dict(level_rows_host=big.ctypes.data), dict(level_rows_host=zero.ctypes.data), dict(ksplit_host=k0.ctypes.data)]
+    mlp = [dict(L=0), dict(L=17), dict(ldf=1), dict(hidden=0), dict(hidden=65)] + _nulls("F", "w1", "b1", "w2", "b2")
+    off_empty, off_big = _zip_rows_host(0, 4920, 4920), _zip_rows_host(0, 8, 8 + (1 << 23))
+    return (big, zero, k0, off_empty, off_big), {
+        "snerf_zip_encode_fwd": [dict(S=0), dict(L=0), dict(n=0), dict(ld=7), dict(levels_per_thread=-1)] + _nulls("table", "feat", "grid_sizes"),
+        "snerf_zip_encode_prop_fwd": [dict(S=0), dict(L=0), dict(L=17), dict(n=0), dict(n=9), dict(hidden=0), dict(hidden=1025)]
+                                     + _nulls("table", "grid_sizes", "w1", "b1", "w2", "b2", "raw_density"),
+        "snerf_zip_prop_mlp_fwd": mlp + _nulls("raw"),
+        "snerf_zip_prop_mlp_bwd": mlp + [dict(lddf=1), dict(lddf=65), dict(ws_floats=a["ws_floats"] - 1, L=12)]
+                                  + _nulls("d_raw", "dF", "g_w1", "g_b1", "g_w2", "g_b2", "ws"),
+        "snerf_zip_encode_fwd_count": [dict(S=0), dict(L=0), dict(L=17), dict(n=0), dict(n=9), dict(ld=7)] + per_level
+                                      + _nulls("table", "feat", "grid_sizes", "ksplit_host", "level_rows_host", "counts", "wg_offsets"),
+        "snerf_zip_encode_bwd": [dict(S=0), dict(L=0), dict(n=0), dict(ld=7), dict(grad_table_bf16=a["bf16_image"] + 2), dict(grad_table_bf16=a["bf16_image"], C=3),
+                                 dict(lds_levels=-1), dict(lds_levels=3), dict(lds_levels=1, lds_cells=0, lds_slabs=1),
+                                 dict(lds_levels=1, lds_cells=10241, lds_slabs=1), dict(lds_levels=1, lds_cells=4920, lds_slabs=0)]
+                                + _nulls("grad_feat", "grad_table", "grid_sizes"),
+        "snerf_zip_encode_bwd_binned": [dict(S=0), dict(L=0), dict(L=17), dict(n=0)] + per_level + _nulls("ksplit_host", "level_rows_host", "counts"),
+        "snerf_zip_encode_ray_bwd": [dict(S=0), dict(L=0), dict(n=0)] + _nulls("table", "grad_feat", "g_origins", "g_directions", "g_base_x", "g_base_y"),
+        "snerf_zip_bin_scale": [dict(cols=0), dict(ld=3)] + _nulls("scale_exp", "grad_feat"),
+        "snerf_grid_encode_bwd_binned": [dict(L=0), dict(L=17), dict(ws=a["ws"] + 128), dict(ws_bytes=0), dict(ws_bytes=256), dict(grad_stride_l=5),
+                                         dict(grad_stride_b=9), dict(offsets_host=off_empty.ctypes.data), dict(offsets_host=off_big.ctypes.data)]
+                                        + _nulls("grad", "inputs", "offsets", "offsets_host", "grad_embeddings", "ws"),
+    }
+
+
+@pytest.mark.parametrize("entry", sorted(_ZIP_CROSS))
+def test_hash_grid_entries_keep_their_statuses(entry):
+    """Every hash-grid entry whose host code dispatches on a dtype or a channel count: the full cross product of those arguments is refused
+    exactly where recorded, each single-argument refusal it has is "bad argument", and an empty batch is OK before anything is looked at.
+    What is not refused reaches a launch: "launch failed" without a device.  With one, the self-contained entries launch every accepted case
+    on the real operands of _zip_problem and must return OK (a wrongly routed instantiation shows as a status, not as a fault); the two
+    multi-pass entries (their later passes read what earlier ones wrote) run only their refusals and empty batches there -- the value tests
+    of test_zip_paths.py and test_gpu_grid.py reach their accepted cases in order."""
+    if not os.path.exists(_lib.LIB_PATH):
+        pytest.skip("library not built")
+    import itertools
+    import torch
+    a, keep = _zip_problem()
+    gpu = torch.cuda.is_available()
+    launch = gpu and entry in _ZIP_SELF_CONTAINED
+    accepted = lambda rc: rc == (0 if launch else 2)
+    axes, marks = _ZIP_CROSS[entry]
+    marks = marks.replace(" ", "")
+    combos = list(itertools.product(*axes.values()))
+    assert len(marks) == len(combos)
+    for combo, mark in zip(combos, marks):
+        case = dict(zip(axes, combo))
+        if mark == "x":
+            assert _zip_status(entry, a, **case) == 1, (entry, case)
+        elif launch or not gpu:
+            rc = _zip_status(entry, a, **case)
+            assert accepted(rc), (entry, case, rc)
+    keep2, refusals = _zip_refusals(a)
+    for change in refusals[entry]:
+        assert _zip_status(entry, a, **change) == 1, (entry, change)
+    if entry == "snerf_zip_encode_bwd_binned":
+        rows = _ZIP_PASSES.split()
+        assert len(rows) == 1 + len(_ZIP_PASS_PTRS)
+        for absent, row in zip((None,) + _ZIP_PASS_PTRS, rows):
+            for p, mark in zip(range(-1, 11), row):
+                if mark == "x" or not gpu:
+                    rc = _zip_status(entry, a, **{"pass": p}, **({absent: None} if absent else {}))
+                    assert rc == (1 if mark == "x" else 2), (absent, p, rc)
+    batch = {"snerf_zip_prop_mlp_fwd": "P", "snerf_zip_prop_mlp_bwd": "P", "snerf_grid_encode_bwd_binned": "B", "snerf_zip_bin_scale": None}.get(entry, "R")
+    if batch is None:                                                   # snerf_zip_bin_scale: no rows is a launch of its own (the default scale)
+        assert accepted(_zip_status(entry, a, rows=0, grad_feat=None, cols=0, feat_dtype=3))
+    else:
+        nothing = dict(a, **{arg: None for ty, arg in _lib.parse_header()[entry] if ty is ctypes.c_void_p})          # (no pointer at all)
+        for empty in (0, -1):
+            assert _zip_status(entry, a, **{batch: empty}) == 0
+            assert _zip_status(entry, dict(nothing, C=3, L=99, n=-1, table_dtype=3, feat_dtype=3, grad_dtype=3, **{"pass": 11}), **{batch: empty}) == 0
+    if gpu:
+        torch.cuda.synchronize()
+    del keep, keep2

@@ -860,6 +860,45 @@ def test_zip_encode_ray_bwd_kernel_vs_oracle(lvl, half):
         assert rel < 2e-2, (name, rel)        # finest levels: 1e-7 position differences (sincosf / cbrtf vs torch) -> 1e-3 of the derivative
 
 
+@pytest.mark.gpu
+@pytest.mark.parametrize("lvl", [1, 2])
+def test_zip_encode_fwd_feature_dtype_leaves_round_the_fp32_result(lvl):
+    """snerf_zip_encode_fwd / snerf_zip_encode_fwd_count at C = 1 (proposal grid) and C = 4 (NeRF grid), fp32 and fp16 tables: the kernels
+    accumulate in fp32 and cast once at the store, so the bf16- and the fp16-feature instantiation must write the fp32-feature
+    instantiation's output rounded to that dtype, bit for bit -- a feature dtype routed to another instantiation cannot."""
+    from snerf_amd import ops
+    specs, p = zip_setup()
+    spec = specs[lvl]
+    emb = p[("prop_mlp_1." if lvl == 1 else "nerf_mlp.") + "encoder.embeddings"] * 30      # trained-like magnitudes
+    R, S, n = 64, 16, 7
+    g = torch.Generator().manual_seed(3)
+    d = torch.nn.functional.normalize(torch.randn(R, 3, generator=g), dim=-1)
+    bx = torch.nn.functional.normalize(torch.cross(d, torch.randn(R, 3, generator=g), dim=-1), dim=-1)
+    by = torch.nn.functional.normalize(torch.cross(d, bx, dim=-1), dim=-1)
+    o = torch.randn(R, 3, generator=g) * 0.1
+    radii = 2e-3 + 2e-3 * torch.rand(R, generator=g)
+    tdist = torch.sort(torch.rand(R, S + 1, generator=g) * 5 + 0.2, -1)[0]
+    degj = torch.rand(R, S, n, generator=g)
+    L, C = spec.L, spec.C
+    assert C == (1 if lvl == 1 else 4)
+    c = lambda t: t.cuda().contiguous()
+    rays = [c(t) for t in (tdist, o, d, radii, bx, by, degj)]
+    offs, gs = c(torch.from_numpy(spec.offsets.astype(np.int32))), c(torch.from_numpy(spec.res.astype(np.int32)))
+    ks, _, level_rows = ops.zip_bin_plan(spec.offsets, C, R * S * n * 8)
+    for table in (c(emb), c(emb.half())):
+        out = {}
+        for fdt in (torch.float32, torch.bfloat16, torch.float16):
+            plain, count = (torch.full((R * S, L * C), float("nan"), dtype=fdt, device="cuda") for _ in range(2))
+            ops.zip_encode_fwd(*rays, table, offs, gs, plain, L, C, n, 3, spec.S, spec.H, 0.35)
+            ops.zip_encode_fwd_count(*rays, table, offs, gs, count, L, C, n, 3, spec.S, spec.H, 0.35, ks, level_rows)
+            out[fdt] = (plain, count)
+        for k, entry in enumerate(("snerf_zip_encode_fwd", "snerf_zip_encode_fwd_count")):
+            ref = out[torch.float32][k]
+            assert bool(torch.isfinite(ref).all()) and float(ref.abs().max()) > 0, entry
+            for fdt in (torch.bfloat16, torch.float16):
+                assert torch.equal(out[fdt][k], ref.to(fdt)), (entry, table.dtype, fdt)
+
+
 def test_loss_scaler_policy_is_gradscalers():
     """LossScaler = torch.cuda.amp.GradScaler's update rule (what accelerate wraps around the reference's fp16 training, zipnerf/train.py:44):
     backoff on an overflow (and the step is skipped), growth after `growth_interval` CONSECUTIVE clean steps; checked against torch's own
