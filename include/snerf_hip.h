@@ -400,6 +400,30 @@ int snerf_mip_loss_tail(const float* rgb, const float* tgt, const float* dist1, 
                         const float* conf, const float* s_f, const float* w_f, const float* s_c, const float* w_c, long N, int Pf,
                         int Sc, int disparity, float depth_lambda, float coarse_mult, float prop_lambda, float* out, float* g_rgb,
                         float* g_dist1, float* g_dist0, float* g_wc, void* stream);
+/* The same tail with the per-image rules of s-nerf/train.py:131-209; the arguments of snerf_mip_loss_tail keep their meaning and,
+ * with every new pointer NULL, their results (gradients bit for bit).  New, each nullable = term or mask absent:
+ *   sem [N,C] fp32 composited logits, labels [N] (int32, or fp32 holding exact integers when labels_f32 = 1), g_sem [N,C]: all three
+ *   or none; C in 1..32.  SemanticLoss (model/loss_factory.py:13-24): semantic_lambda * nn.CrossEntropyLoss()(sem, labels), labels
+ *   of -100 (ignore_index) left out.  A label outside [0, C) other than -100 is left out too (the reference raises on one).
+ *   rows int64 [N,2] (the batcher's sel_coords: element 2 r = pixel row of ray r), img_i int64 [1] DEVICE word = the image of the
+ *   batch (read by the kernels, never on the host), rgb_row_limit / depth_row_limit / sem_valid int32 [n_images] per-image tables:
+ *   all five or none.  With i = *img_i: Wr = rows[2 r] < rgb_row_limit[i] (train.py:137-144, the Waymo side cameras),
+ *   Br = rows[2 r] < depth_row_limit[i] (train.py:165-170, the back camera), semantic term only where sem_valid[i] != 0
+ *   (train.py:131,185).  An i outside [0, n_images) counts no ray for the rgb, depth and semantic terms.
+ *   depth_keep [N] fp32 (needs tdepth): Br also needs depth_keep[r] == 0 (train.py:168-170, seg_mask == 0).
+ * rgb = sum_{Wr} |rgb - tgt|^2 / (3 #W), g_rgb = 0 where !Wr; depth = the plain expression over the rays with tdepth != 0 and Br,
+ * divided by their number; semantic = mean over the rays with Wr and a counted label of -log softmax(sem_r)[label_r] (row maximum
+ * subtracted, float64 log-sum-exp) times semantic_lambda, g_sem = semantic_lambda (softmax - onehot) / #sem on those rays and 0
+ * elsewhere (always written in full); proposal = every ray.  A term whose count is 0 is 0 with zero gradients (the reference's mean
+ * over an empty selection is NaN).
+ * out[8] = {#depth rays, rgb, depth, proposal, total, semantic, #rgb rays, #semantic rays} (out[0..4] as snerf_mip_loss_tail). */
+int snerf_mip_loss_tail_masked(const float* rgb, const float* tgt, const float* dist1, const float* dist0, const float* tdepth,
+                               const float* conf, const float* s_f, const float* w_f, const float* s_c, const float* w_c,
+                               const float* sem, const void* labels, int labels_f32, int C, const long* rows, const long* img_i,
+                               const int* rgb_row_limit, const int* depth_row_limit, const int* sem_valid, int n_images,
+                               const float* depth_keep, long N, int Pf, int Sc, int disparity, float depth_lambda, float coarse_mult,
+                               float prop_lambda, float semantic_lambda, float* out, float* g_rgb, float* g_dist1, float* g_dist0,
+                               float* g_wc, float* g_sem, void* stream);
 
 /* zipnerf (path C) ray generation: s-nerfpp/zipnerf/internal/camera_utils.py:453-563 pixels_to_rays, perspective camera, no
  * distortion, no NDC.  pix_x / pix_y int32 [N] integer pixel coordinates, cam_idx int32 [N] (NULL = camera 0) into pixtocams

@@ -233,6 +233,8 @@ __global__ __launch_bounds__(1024) void loss_prepare_kernel(const float* __restr
   }
 }
 
+// (loss_tail_proposal / loss_tail_depth below restate the depth and proposal blocks of this kernel for the masked tail: an edit to
+// either side must be mirrored on the other; tests/test_mip_semantic_step.py compares the two entries' gradients bit for bit.)
 __global__ __launch_bounds__(64) void loss_tail_kernel(LossTail a) {
   const long r = (long)blockIdx.x * 64 + threadIdx.x;
   float l_rgb = 0.f, l_dep = 0.f, l_prop = 0.f;
@@ -332,6 +334,248 @@ extern "C" int snerf_mip_loss_tail(const float* rgb, const float* tgt, const flo
   LossTail a{rgb, tgt, dist1, dist0, tdepth, conf, s_f, w_f, s_c, w_c, N, Pf, Sc, disparity, depth_lambda, coarse_mult, prop_lambda, out,
              g_rgb, g_dist1, g_dist0, g_wc};
   hipLaunchKernelGGL(loss_tail_kernel, dim3((unsigned)((N + 63) / 64)), dim3(64), 0, (hipStream_t)stream, a);
+  return snerf_check_launch();
+}
+
+// ---------------------------------------------------------------------------
+// The same tail with the per-image rules of s-nerf/train.py:131-209: the semantic cross-entropy (SemanticLoss,
+// loss_factory.py:13-24 = nn.CrossEntropyLoss, ignore_index -100, times semantic_lambda; only for images with labels), the Waymo
+// side-camera mask (:137-144: rays of pixel rows >= a limit leave the RGB and the semantic mean) and the back-camera mask
+// (:165-170, loss.py:344-346: rays of rows >= a limit, or with seg_mask != 0, leave the depth mean -- and only that).  The image
+// is the device word *img_i, never read on the host; its rules come from three tables with one entry per image.  Per ray r:
+//   Wr = rows[2 r] < rgb_row_limit[i];  Br = rows[2 r] < depth_row_limit[i] and depth_keep[r] == 0  (absent = true)
+//   rgb       sum_{Wr} |rgb - tgt|^2 / (3 #W), gradient 0 where !Wr
+//   depth     the plain tail's expression over the rays with tdepth != 0 and Br, divided by their number
+//   semantic  sem_valid[i] != 0: semantic_lambda * mean over the rays with Wr and a label in [0, C) of -log softmax(sem_r)[label_r]
+//             (float64 log-sum-exp after subtracting the row maximum, one rounding per emitted value); g_sem is written in full
+//   proposal  every ray, as in the plain tail
+// A term whose count is 0 is 0 and so are its gradients (the reference's empty mean is NaN); an image index outside the tables
+// counts no ray for the rgb, depth and semantic terms.  The prepare launch forms the three counts and zeroes the sums.
+// out[0..7] = {#depth rays, rgb, depth, proposal, total, semantic, #rgb rays, #semantic rays}: out[0..4] as in the plain tail.
+// With every new pointer null the lanes do the plain tail's arithmetic in the plain tail's order.
+// ---------------------------------------------------------------------------
+// The proposal and depth terms of loss_tail_kernel as functions, statement for statement.  (The plain kernel keeps its inline text:
+// routed through these functions it computed the same bits on another instruction schedule, 2 % slower -- 294 -> 300 us at 4096 rays
+// on the MI355X.)
+// ProposalLoss of ray r: the coarse histogram must bound the (detached) fine weights from above.  -> the ray's term (times
+// prop_lambda / N); writes g_wc[r] = d term / d w_c[r].
+__device__ __forceinline__ float loss_tail_proposal(const LossTail& a, long r) {
+  float l_prop = 0.f;
+  const float* sf = a.s_f + r * a.Pf;
+  const float* wf = a.w_f + r * (a.Pf - 1);
+  const float* sc = a.s_c + r * (a.Sc + 1);
+  const float* wc = a.w_c + r * a.Sc;
+  float* g = a.g_wc + r * a.Sc;
+  for (int j = 0; j < a.Sc; ++j) g[j] = 0.f;
+  const int cap = min(a.Pf - 2, a.Sc - 1);          // the reference clamps `right` with the FINE interval count
+  const float scale = a.prop_lambda / (float)a.N;
+  // walk both sorted fence-post lists once; p = #(s_c <= s_f[k]) (searchsorted right=True); C = cumsum(w_c)
+  int p = 0;
+  double cum = 0.0;
+  float Wlast = 0.f;                                 // C[min(p-1, Sc-1)]
+  float Wcap = 0.f;                                  // C[cap], known once p-1 >= cap
+  const float W0 = wc[0];                            // C[0]: the reference clamps the left index at 0 (not "empty prefix")
+  float left = 0.f;
+  int li = 0;
+  for (int k = 0; k < a.Pf; ++k) {
+    const float s = sf[k];
+    while (p <= a.Sc && sc[p] <= s) {
+      if (p < a.Sc) { cum += (double)wc[p]; Wlast = (float)cum; if (p == cap) Wcap = Wlast; }
+      ++p;
+    }
+    const int idx = p - 1;                           // inds - 1 of this fence post
+    if (k > 0) {
+      const int ri = idx > cap ? cap : max(idx, 0);
+      const float right = idx > cap ? Wcap : (idx <= 0 ? W0 : Wlast);
+      const float w = wf[k - 1];
+      const float over = w - (right - left);
+      if (over > 0.f) {
+        l_prop += over * over / (w + 1e-8f);
+        const float gb = -2.f * over / (w + 1e-8f) * scale;
+        g[ri] += gb;
+        g[li] -= gb;
+      }
+    }
+    li = idx <= 0 ? 0 : min(idx, a.Sc - 1);          // (an index past the last interval raises in the reference)
+    left = idx <= 0 ? W0 : Wlast;
+  }
+  l_prop *= scale;
+  // d/dw_c[j] = sum_{k >= j} dW[k]
+  double acc = 0.0;
+  for (int j = a.Sc - 1; j >= 0; --j) { acc += (double)g[j]; g[j] = (float)acc; }
+  return l_prop;
+}
+
+// the depth term of ray r, which has a LiDAR target t != 0 and is one of the out[0] counted rays.  -> the term; *g1 / *g0 = d term /
+// d (dist1[r], dist0[r]).
+__device__ __forceinline__ float loss_tail_depth(const LossTail& a, long r, float t, float* g1, float* g0) {
+  const float nv = a.out[0];
+  const float cw = (a.conf != nullptr ? a.conf[r] : 1.f);
+  const float d1 = a.dist1[r], d0 = a.dist0[r];
+  float e1, e0, s1, s0;
+  if (a.disparity) { e1 = 1.f / d1 - 1.f / t; e0 = 1.f / d0 - 1.f / t; s1 = -1.f / (d1 * d1); s0 = -1.f / (d0 * d0); }
+  else { e1 = d1 - t; e0 = d0 - t; s1 = 1.f; s0 = 1.f; }
+  const float k = cw * a.depth_lambda / nv;
+  *g1 = (e1 > 0.f ? 1.f : (e1 < 0.f ? -1.f : 0.f)) * s1 * k;
+  *g0 = (e0 > 0.f ? 1.f : (e0 < 0.f ? -1.f : 0.f)) * s0 * k * a.coarse_mult;
+  return (fabsf(e1) + a.coarse_mult * fabsf(e0)) * k;
+}
+
+struct LossTailMasked {
+  LossTail t;
+  const float* sem; const void* labels; int labels_f32, C;
+  const long *rows, *img_i;
+  const int *rgb_row_limit, *depth_row_limit, *sem_valid;
+  int n_images;
+  const float* depth_keep;
+  float sem_lambda;
+  float* g_sem;
+};
+
+// label of ray r, or -1 for a ray the semantic mean leaves out (ignore_index -100, and any other value outside [0, C))
+__device__ __forceinline__ int loss_tail_label(const LossTailMasked& a, long r) {
+  int l;
+  if (a.labels_f32) {
+    const float f = ((const float*)a.labels)[r];
+    l = (f >= 0.f && f < 32.f) ? (int)f : -1;          // (NaN fails both comparisons)
+    if ((float)l != f) l = -1;
+  } else {
+    l = ((const int*)a.labels)[r];
+  }
+  return (l >= 0 && l < a.C) ? l : -1;
+}
+
+// which means ray r enters: bit 0 = rgb (and semantic) mask Wr, bit 1 = depth mask Br
+__device__ __forceinline__ int loss_tail_masks(const LossTailMasked& a, long r) {
+  int W = 1, B = 1;
+  if (a.rows != nullptr) {
+    const long i = a.img_i[0];
+    if (i < 0 || i >= a.n_images) return 0;
+    const long row = a.rows[2 * r];
+    W = row < a.rgb_row_limit[i];
+    B = row < a.depth_row_limit[i];
+  }
+  if (a.depth_keep != nullptr) B = B && a.depth_keep[r] == 0.f;
+  return W | B << 1;
+}
+
+__device__ __forceinline__ bool loss_tail_sem_active(const LossTailMasked& a) {
+  if (a.sem == nullptr) return false;
+  if (a.rows == nullptr) return true;
+  const long i = a.img_i[0];
+  return i >= 0 && i < a.n_images && a.sem_valid[i] != 0;
+}
+
+__global__ __launch_bounds__(1024) void loss_prepare_masked_kernel(LossTailMasked a) {
+  __shared__ int part[3][16];
+  int cnt[3] = {0, 0, 0};                              // depth, rgb, semantic
+  const bool sem_on = loss_tail_sem_active(a);
+  for (long r = threadIdx.x; r < a.t.N; r += 1024) {
+    const int m = loss_tail_masks(a, r);
+    if (a.t.tdepth != nullptr) cnt[0] += a.t.tdepth[r] != 0.f && (m & 2);
+    cnt[1] += m & 1;
+    if (sem_on) cnt[2] += (m & 1) && loss_tail_label(a, r) >= 0;
+  }
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) cnt[k] += __shfl_xor(cnt[k], o, 64);
+    if ((threadIdx.x & 63) == 0) part[k][threadIdx.x >> 6] = cnt[k];
+  }
+  __syncthreads();
+  if (threadIdx.x < 3) {
+    int t = 0;
+    for (int w = 0; w < 16; ++w) t += part[threadIdx.x][w];
+    a.t.out[threadIdx.x == 0 ? 0 : 5 + threadIdx.x] = (float)t;
+  }
+  if (threadIdx.x >= 3 && threadIdx.x < 8) a.t.out[threadIdx.x - 2] = 0.f;      // out[1..5]
+}
+
+__global__ __launch_bounds__(64) void loss_tail_masked_kernel(LossTailMasked a) {
+  const LossTail& t = a.t;
+  const long r = (long)blockIdx.x * 64 + threadIdx.x;
+  float l_rgb = 0.f, l_dep = 0.f, l_prop = 0.f;
+  double l_sem = 0.0;
+  if (r < t.N) {
+    const int m = loss_tail_masks(a, r);
+    // ---- RGB: mean over the #W * 3 values of the rays inside the mask
+    const float nW = t.out[6];
+    const float inv = nW > 0.f ? 1.f / (3.f * nW) : 0.f;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const float d = t.rgb[3 * r + c] - t.tgt[3 * r + c];
+      if (m & 1) l_rgb += d * d;
+      t.g_rgb[3 * r + c] = (m & 1) ? d * (2.f * inv) : 0.f;
+    }
+    l_rgb *= inv;
+    // ---- depth: mean over the rays with a LiDAR target inside the depth mask
+    if (t.tdepth != nullptr) {
+      const float td = t.tdepth[r];
+      float g1 = 0.f, g0 = 0.f;
+      if (td != 0.f && (m & 2)) l_dep = loss_tail_depth(t, r, td, &g1, &g0);
+      t.g_dist1[r] = g1;
+      t.g_dist0[r] = g0;
+    }
+    // ---- proposal: every ray
+    if (t.s_c != nullptr) l_prop = loss_tail_proposal(t, r);
+    // ---- semantic: cross-entropy of the composited logits
+    if (a.sem != nullptr) {
+      const float* x = a.sem + r * a.C;
+      float* g = a.g_sem + r * a.C;
+      const int lab = (loss_tail_sem_active(a) && (m & 1)) ? loss_tail_label(a, r) : -1;
+      if (lab < 0) {
+        for (int c = 0; c < a.C; ++c) g[c] = 0.f;
+      } else {
+        float mx = x[0];
+        for (int c = 1; c < a.C; ++c) mx = fmaxf(mx, x[c]);
+        double se = 0.0;
+        for (int c = 0; c < a.C; ++c) se += exp((double)x[c] - (double)mx);
+        const double lse = log(se);
+        const double k = (double)a.sem_lambda / (double)t.out[7];      // (this ray is counted: out[7] >= 1)
+        l_sem = (lse - ((double)x[lab] - (double)mx)) * k;
+        for (int c = 0; c < a.C; ++c) {
+          const double p = exp(((double)x[c] - (double)mx) - lse);
+          g[c] = (float)((p - (c == lab ? 1.0 : 0.0)) * k);
+        }
+      }
+    }
+  }
+  l_rgb = wave_sum(l_rgb); l_dep = wave_sum(l_dep); l_prop = wave_sum(l_prop);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) l_sem += __shfl_xor(l_sem, o, 64);
+  if (threadIdx.x == 0) {
+    const float ls = (float)l_sem;
+    atomicAdd(t.out + 1, l_rgb);
+    if (t.tdepth != nullptr) atomicAdd(t.out + 2, l_dep);
+    if (t.s_c != nullptr) atomicAdd(t.out + 3, l_prop);
+    if (a.sem != nullptr) atomicAdd(t.out + 5, ls);
+    atomicAdd(t.out + 4, ((l_rgb + l_dep) + l_prop) + ls);
+  }
+}
+
+extern "C" int snerf_mip_loss_tail_masked(const float* rgb, const float* tgt, const float* dist1, const float* dist0, const float* tdepth,
+                                          const float* conf, const float* s_f, const float* w_f, const float* s_c, const float* w_c,
+                                          const float* sem, const void* labels, int labels_f32, int C, const long* rows, const long* img_i,
+                                          const int* rgb_row_limit, const int* depth_row_limit, const int* sem_valid, int n_images,
+                                          const float* depth_keep, long N, int Pf, int Sc, int disparity, float depth_lambda, float coarse_mult,
+                                          float prop_lambda, float semantic_lambda, float* out, float* g_rgb, float* g_dist1, float* g_dist0,
+                                          float* g_wc, float* g_sem, void* stream) {
+  if (N <= 0) return SNERF_OK;
+  if (rgb == nullptr || tgt == nullptr || out == nullptr || g_rgb == nullptr) return SNERF_ERR_ARG;
+  if (tdepth != nullptr && (dist1 == nullptr || dist0 == nullptr || g_dist1 == nullptr || g_dist0 == nullptr)) return SNERF_ERR_ARG;
+  if (s_c != nullptr && (s_f == nullptr || w_f == nullptr || w_c == nullptr || g_wc == nullptr || Pf < 2 || Sc < 1)) return SNERF_ERR_ARG;
+  const int n_sem = (sem != nullptr) + (labels != nullptr) + (g_sem != nullptr);
+  if (n_sem != 0 && n_sem != 3) return SNERF_ERR_ARG;
+  if (sem != nullptr && (C < 1 || C > 32 || (labels_f32 != 0 && labels_f32 != 1))) return SNERF_ERR_ARG;
+  const int n_rule = (rows != nullptr) + (img_i != nullptr) + (rgb_row_limit != nullptr) + (depth_row_limit != nullptr) + (sem_valid != nullptr);
+  if (n_rule != 0 && n_rule != 5) return SNERF_ERR_ARG;
+  if (rows != nullptr && n_images < 1) return SNERF_ERR_ARG;
+  if (depth_keep != nullptr && tdepth == nullptr) return SNERF_ERR_ARG;
+  LossTailMasked a{{rgb, tgt, dist1, dist0, tdepth, conf, s_f, w_f, s_c, w_c, N, Pf, Sc, disparity, depth_lambda, coarse_mult, prop_lambda, out,
+                    g_rgb, g_dist1, g_dist0, g_wc},
+                   sem, labels, labels_f32, C, rows, img_i, rgb_row_limit, depth_row_limit, sem_valid, n_images, depth_keep, semantic_lambda, g_sem};
+  hipLaunchKernelGGL(loss_prepare_masked_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(loss_tail_masked_kernel, dim3((unsigned)((N + 63) / 64)), dim3(64), 0, (hipStream_t)stream, a);
   return snerf_check_launch();
 }
 

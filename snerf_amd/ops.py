@@ -1410,6 +1410,48 @@ def mip_loss_tail(rgb, tgt, dist1, dist0, tdepth, conf, s_f, w_f, s_c, w_c, disp
     return out, g_rgb, g1, g0, gw
 
 
+def mip_loss_tail_masked(rgb, tgt, dist1, dist0, tdepth, conf, s_f, w_f, s_c, w_c, disparity, depth_lambda, coarse_mult, prop_lambda,
+                         sem=None, labels=None, semantic_lambda=0.1, rows=None, img_i=None, rgb_row_limit=None, depth_row_limit=None,
+                         sem_valid=None, depth_keep=None):
+    """snerf_mip_loss_tail_masked: mip_loss_tail with the per-image rules of s-nerf/train.py:131-209 (each new argument None = absent).
+    sem [n,C] fp32 composited logits + labels [n] (int32, or fp32 holding exact integers -- a batcher's extras row; -100 = ignored, and
+    so is any other label outside [0, C): the reference raises on one); rows = the batcher's sel_coords (int64 [n,2]), img_i int64 [1]
+    device tensor (read by the kernel, never on the host) and the three int32 per-image tables (trainer.MipLossRules): all or none;
+    depth_keep [n] fp32: a ray counts for the depth term only where it is 0.  A term whose count is 0 is 0 with zero gradients.
+    -> (out[8] = {#depth rays, rgb, depth, proposal, total, semantic, #rgb rays, #semantic rays}, g_rgb, g_dist1, g_dist0, g_wc, g_sem);
+    absent terms return None gradients."""
+    n = rgb.shape[0]
+    dev = rgb.device
+    out = torch.empty(8, dtype=torch.float32, device=dev)
+    g_rgb = torch.empty(n, 3, dtype=torch.float32, device=dev)
+    g1 = g0 = gw = gs = None
+    if tdepth is not None:
+        g1, g0 = torch.empty(n, dtype=torch.float32, device=dev), torch.empty(n, dtype=torch.float32, device=dev)
+    Pf = Sc = C = lab_f32 = 0
+    if s_c is not None:
+        Pf, Sc = s_f.shape[1], w_c.shape[1]
+        assert w_f.shape[1] == Pf - 1 and s_c.shape[1] == Sc + 1
+        gw = torch.empty(n, Sc, dtype=torch.float32, device=dev)
+    c = lambda t: None if t is None else _f32c(t)
+    if sem is not None:
+        C = sem.shape[1]
+        assert labels is not None and labels.dtype in (torch.int32, torch.float32) and labels.is_cuda and labels.is_contiguous() and labels.numel() == n
+        lab_f32 = 1 if labels.dtype == torch.float32 else 0
+        gs = torch.empty(n, C, dtype=torch.float32, device=dev)
+    n_img = 0
+    if rows is not None:
+        assert rows.dtype == torch.int64 and rows.is_cuda and rows.is_contiguous() and tuple(rows.shape) == (n, 2), "rows: the batcher's sel_coords, int64 [n, 2]"
+        assert torch.is_tensor(img_i) and img_i.is_cuda and img_i.dtype == torch.int64 and img_i.numel() == 1, "img_i: an int64 [1] CUDA tensor"
+        n_img = rgb_row_limit.numel()
+        for t in (rgb_row_limit, depth_row_limit, sem_valid):
+            assert t.dtype == torch.int32 and t.is_cuda and t.is_contiguous() and t.numel() == n_img
+    _lib.call("snerf_mip_loss_tail_masked", _p(c(rgb)), _p(c(tgt)), _p(c(dist1)), _p(c(dist0)), _p(c(tdepth)), _p(c(conf)), _p(c(s_f)), _p(c(w_f)),
+              _p(c(s_c)), _p(c(w_c)), _p(c(sem)), _p(labels), lab_f32, C, _p(rows), _p(img_i), _p(rgb_row_limit), _p(depth_row_limit), _p(sem_valid),
+              n_img, _p(c(depth_keep)), n, Pf, Sc, int(bool(disparity)), float(depth_lambda), float(coarse_mult), float(prop_lambda),
+              float(semantic_lambda), _p(out), _p(g_rgb), _p(g1), _p(g0), _p(gw), _p(gs), _stream())
+    return out, g_rgb, g1, g0, gw, gs
+
+
 def zip_pixels_to_rays(pix_x, pix_y, cam_idx, pixtocams, camtoworlds, want_imageplane=False):
     """camera_utils.pixels_to_rays on device: int32 pixel coordinates [n] (+ int32 camera index [n] or None) and the stacked
     [ncam,3,3] inverse intrinsics / [ncam,3,4] extrinsics -> dict(origins, directions, viewdirs, radii [n,1], base_x, base_y

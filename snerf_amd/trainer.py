@@ -251,17 +251,65 @@ class _PoseAdam:
             self.step_dev.fill_(self.t)
 
 
+class MipLossRules:
+    """The per-image rules of the reference's loss block (s-nerf/train.py:131-209) as three int32 tables with one entry per image, built
+    once; the loss tail looks up the entry of the batch's image on the device (ops.mip_loss_tail_masked), so the step never reads the
+    image index on the host.
+      rgb_row_limit[i]    rays of pixel rows >= it leave the RGB and the semantic mean: `waymo_row_limit` where `waymo` is set and
+                          camera_index[i] is one of `waymo_cams` (train.py:137-144: --waymo, cameras 3 and 4, row 886), else H (no rule)
+      depth_row_limit[i]  rays of rows >= it leave the depth mean: `backcam_row_limit` where `backcam` is set and camera_index[i] ==
+                          `backcam_cam` (train.py:165-170, loss.py:344-346: --backcam, camera 0, row 750), else H
+      sem_valid[i]        1 for the images of `semantic_index` (train.py:131,185: the images with labels), else 0: no semantic term
+    `camera_index`: the camera of every image ([num_images], as the reference's cam_index).  The tables are host tensors;
+    `on(device)` returns (and keeps) their device copies."""
+
+    def __init__(self, num_images, H, camera_index, semantic_index=None, waymo=False, backcam=False, waymo_cams=(3, 4), waymo_row_limit=886,
+                 backcam_cam=0, backcam_row_limit=750):
+        import numpy as np
+        n = int(num_images)
+        cam = np.asarray(camera_index.cpu() if torch.is_tensor(camera_index) else camera_index).reshape(-1)
+        if n < 1 or cam.shape[0] != n:
+            raise ValueError(f"MipLossRules: camera_index needs one entry per image ({n}), got {cam.shape[0]}")
+        rgb = np.full(n, int(H), np.int32)
+        dep = np.full(n, int(H), np.int32)
+        sem = np.zeros(n, np.int32)
+        if waymo:
+            rgb[np.isin(cam, list(waymo_cams))] = int(waymo_row_limit)
+        if backcam:
+            dep[cam == backcam_cam] = int(backcam_row_limit)
+        if semantic_index is not None:
+            idx = np.asarray(semantic_index.cpu() if torch.is_tensor(semantic_index) else list(semantic_index), dtype=np.int64).reshape(-1)
+            if idx.size and (idx.min() < 0 or idx.max() >= n):
+                raise ValueError("MipLossRules: semantic_index points past the images")
+            sem[idx] = 1
+        self.num_images, self.H = n, int(H)
+        self.rgb_row_limit, self.depth_row_limit, self.sem_valid = torch.from_numpy(rgb), torch.from_numpy(dep), torch.from_numpy(sem)
+        self._dev = {}
+
+    def on(self, device):
+        """-> (rgb_row_limit, depth_row_limit, sem_valid) on `device`"""
+        key = str(device)
+        if key not in self._dev:
+            self._dev[key] = tuple(t.to(device) for t in (self.rgb_row_limit, self.depth_row_limit, self.sem_valid))
+        return self._dev[key]
+
+
 class MipTrainer(_AdamState):
+    rules = None                                     # (class default: loss_and_grads also serves trainers assembled without __init__)
+
     def __init__(self, model, lr=5e-4, betas=(0.9, 0.999), eps=1e-8, depth_lambda=0.2, coarse_depth_mult=0.2,
                  proposal_loss=False, proposal_lambda=0.05, disparity_depth=True, process_group=None,
                  nonfinite="zero", grad_max_val=0.0, grad_max_norm=0.0, exchange_when_single=False,
-                 pose_net=None, pose_lr=1e-4, pose_betas=(0.9, 0.999), pose_eps=1e-8):
+                 pose_net=None, pose_lr=1e-4, pose_betas=(0.9, 0.999), pose_eps=1e-8, semantic_lambda=0.1, loss_rules=None):
         """`nonfinite` / `grad_max_val` / `grad_max_norm`: gradient hygiene folded into the Adam launch (ops.adam_step).  The s-nerf
         reference has none (train.py:212-215 drops into pdb on a failing backward); the default "zero" keeps one NaN / Inf gradient
         (1/(depth + eps), a bf16 overflow) from poisoning m, v and the parameters of the whole arena on every rank.  "keep" = plain Adam.
         `pose_net` (poses.LearnPose; configs: pose_refine = True): the learned camera poses are trained inside the step -- see `step`'s
         `img_i`.  The module is moved to the model's device and its trained parameters into one flat buffer (`self.pose`, _PoseAdam);
-        `pose_lr` / `pose_betas` / `pose_eps`: their own Adam (utils/model_utils.py:36-42: lr 1e-4, no schedule)."""
+        `pose_lr` / `pose_betas` / `pose_eps`: their own Adam (utils/model_utils.py:36-42: lr 1e-4, no schedule).
+        `semantic_lambda` (arg_parser.py:166): weight of the semantic cross-entropy of `step`'s `target_semantic`.  `loss_rules`
+        (MipLossRules): the Waymo side-camera / back-camera masks and the images with labels, applied inside the loss tail to the image
+        `step`'s `img_i` names."""
         self.model = model
         self.lr, self.betas, self.eps = lr, betas, eps
         self.nonfinite, self.grad_max_val, self.grad_max_norm = nonfinite, float(grad_max_val), float(grad_max_norm)
@@ -277,6 +325,10 @@ class MipTrainer(_AdamState):
         self._step_dev = self._lr_dev = self._graph = None
         a.grad.zero_()
         self.pose = None if pose_net is None else _PoseAdam(pose_net, a.flat.device, pose_lr, pose_betas, pose_eps)
+        self.semantic_lambda, self.rules = float(semantic_lambda), loss_rules
+        self._rule_tables = None if loss_rules is None else loss_rules.on(a.flat.device)
+        self.last_semantic_loss = self.last_counts = None
+        self._img_dev = None                         # (python int img_i, its int64 [1] device tensor)
 
     def broadcast_parameters(self, src=0):
         if self.world > 1:
@@ -310,12 +362,29 @@ class MipTrainer(_AdamState):
                       step_dev=self._step_dev, lr_dev=self._lr_dev)
         a.bump()
 
-    def loss_and_grads(self, outs, target_rgb, target_depth, conf):
+    def loss_and_grads(self, outs, target_rgb, target_depth, conf, target_semantic=None, sel_coords=None, img_i=None, depth_keep=None):
         """The reference's per-ray loss tail (train.py:150-208) in ONE kernel, `snerf_mip_loss_tail`: RGB MSE, the
         confidence-weighted (disparity) depth loss on both levels masked to rays with a LiDAR target, and -- with
-        `proposal_loss` -- ProposalLoss on the two histograms.  Returns (loss [device scalar], output gradients)."""
+        `proposal_loss` -- ProposalLoss on the two histograms.  Returns (loss [device scalar], output gradients).
+        With `target_semantic`, `depth_keep` or loss rules (see `step`): `snerf_mip_loss_tail_masked`, which adds the semantic
+        cross-entropy and the per-image masks of train.py:131-209; the output gradients then end with g_semantic.  `last_losses` keeps
+        its four entries; `last_semantic_loss` and `last_counts` = (#depth rays, #rgb rays, #semantic rays) are device scalars too."""
         dist0, acc0, s0, w0, rgb1, dist1, acc1, s1, w1 = outs[:9]
         prop = self.proposal_loss
+        rules = self.rules
+        if target_semantic is not None or depth_keep is not None or rules is not None:
+            tables = self._rule_tables if rules is not None else (None, None, None)
+            with_sem = target_semantic is not None
+            out, g_rgb1, g_dist1, g_dist0, g_w0, g_sem = ops.mip_loss_tail_masked(
+                rgb1, target_rgb, dist1 if target_depth is not None else None, dist0 if target_depth is not None else None,
+                target_depth, conf, s1 if prop else None, w1 if prop else None, s0 if prop else None, w0 if prop else None,
+                self.disparity_depth, self.depth_lambda, self.coarse_depth_mult, self.proposal_lambda,
+                sem=outs[9] if with_sem else None, labels=target_semantic, semantic_lambda=self.semantic_lambda,
+                rows=sel_coords if rules is not None else None, img_i=img_i if rules is not None else None,
+                rgb_row_limit=tables[0], depth_row_limit=tables[1], sem_valid=tables[2], depth_keep=depth_keep)
+            self.last_losses = out[:4]
+            self.last_semantic_loss, self.last_counts = out[5], (out[0], out[6], out[7])
+            return out[4], (g_dist0, None, g_w0, g_rgb1, g_dist1, None, None, g_sem)
         out, g_rgb1, g_dist1, g_dist0, g_w0 = ops.mip_loss_tail(
             rgb1, target_rgb, dist1 if target_depth is not None else None, dist0 if target_depth is not None else None,
             target_depth, conf, s1 if prop else None, w1 if prop else None, s0 if prop else None, w0 if prop else None,
@@ -323,7 +392,8 @@ class MipTrainer(_AdamState):
         self.last_losses = out[:4]                               # {#valid depth rays, rgb, depth, proposal}: stays on the device
         return out[4], (g_dist0, None, g_w0, g_rgb1, g_dist1, None, None)      # out[4]: their sum, formed by the same launch
 
-    def step(self, rays, target_rgb, target_depth=None, conf=None, randomized=True, s_rand=None, u=None, ray_grads=False, viewc=None, img_i=None):
+    def step(self, rays, target_rgb, target_depth=None, conf=None, randomized=True, s_rand=None, u=None, ray_grads=False, viewc=None, img_i=None,
+             target_semantic=None, sel_coords=None, depth_keep=None):
         """`ray_grads=True` (pose refinement, configs: pose_refine = True): `last_ray_grads` = d loss / d (origins, directions, viewdirs)
         of this rank's rays, for the caller's pose optimiser (`rays.origins.backward(g_o)` etc. chains them into the pose parameters).
         `viewc` (fn = 0 models, the view-centred warp): the warp centre the reference passes to every forward (train.py:36,112); a model
@@ -331,16 +401,27 @@ class MipTrainer(_AdamState):
         With a `pose_net`: `rays` are the UNtransformed rays of image `img_i` (a python int, or the batcher's int64 [1] device tensor,
         which is never read on the host); the step applies row img_i of the pose table to them (ops.pose_apply: sample_rays' pose
         branch), runs forward, loss tail and backward with ray gradients (`last_ray_grads` as above), reduces those to the row's gradient
-        (ops.pose_grad) and follows the model's Adam with the pose table's -- no torch op, autograd graph or host sync in between."""
+        (ops.pose_grad) and follows the model's Adam with the pose table's -- no torch op, autograd graph or host sync in between.
+        `target_semantic` (a model with semantic=True): per-ray labels, int32 or fp32 holding exact integers (a batcher's extras row;
+        other integer types are converted), -100 = ignored; the semantic cross-entropy times `semantic_lambda` joins the loss and
+        trains the semantic head (train.py:185-191).  A label outside [0, C) other than -100 is ignored as well -- the reference
+        raises on one.  `depth_keep` [n] fp32 (with target_depth): a ray counts for the depth term only where it is 0 (train.py:168-170,
+        seg_mask == 0).  With `loss_rules`: `sel_coords` (the batcher's int64 [n,2] pixel coordinates) and `img_i` (as above; a
+        python int is wrapped into a device tensor once per value) are needed, and the tail applies the rules of that image: rays of pixel rows at or past
+        the RGB row limit leave the RGB and semantic means, rays at or past the depth row limit (or with depth_keep != 0) the depth mean
+        -- and, as in the reference, only that one -- and images outside the rules' semantic_index have no semantic term.  A term that counts
+        no ray is 0 with zero gradients, where the reference's empty mean is NaN.  world > 1: every rank forms its means over its
+        own shard of the batch, like the reference under DDP and like the depth term's count before."""
         self._set_viewc(viewc)
         if self.pose is not None and img_i is None:
             raise ValueError("MipTrainer with a pose_net: step() needs img_i= (the image the rays belong to)")
-        if self.pose is None and img_i is not None:
-            raise ValueError("MipTrainer: img_i= given without a pose_net")
+        if self.pose is None and self.rules is None and img_i is not None:
+            raise ValueError("MipTrainer: img_i= given without a pose_net or loss_rules")
         ex = _GradExchange(self.model.arena, self.world, self.pg, self.single_rank_exchange)
         # every block of the gradient arena goes on the wire as soon as the backward pass has finished it (heads, then trunk layer by
         # trunk layer, then the proposal network): the collectives run under the remaining backward kernels
-        loss, outs = self._forward_backward(rays, target_rgb, target_depth, conf, randomized, s_rand, u, ray_grads, ex, img_i)
+        loss, outs = self._forward_backward(rays, target_rgb, target_depth, conf, randomized, s_rand, u, ray_grads, ex, img_i,
+                                            target_semantic, sel_coords, depth_keep)
         ex.finish()
         self.t += 1
         self._adam()                                      # graph mode: step count and lr live on the device (capture / replay below)
@@ -355,13 +436,46 @@ class MipTrainer(_AdamState):
         elif m.fn == 0 and not getattr(m, "_viewc_given", False):
             raise ValueError("MipTrainer: the model warps around a view centre (fn = 0): pass viewc= (train.py:36,112) or call model.set_viewc first")
 
-    def _forward_backward(self, rays, target_rgb, target_depth, conf, randomized, s_rand, u, ray_grads, on_done, img_i=None):
+    def _tail_extras(self, n, dev, target_depth, img_i, target_semantic, sel_coords, depth_keep):
+        """checks and device forms of the masked tail's inputs -> (target_semantic, sel_coords, img_i, depth_keep)"""
+        if target_semantic is not None:
+            if not getattr(self.model, "semantic", False):
+                raise ValueError("MipTrainer: target_semantic= given, but the model has no semantic head (semantic=True)")
+            if self.rules is not None and not bool(self.rules.sem_valid.any()):
+                raise ValueError("MipTrainer: target_semantic= given, but the loss rules name no image with labels (semantic_index)")
+            if target_semantic.dtype not in (torch.int32, torch.float32):
+                target_semantic = target_semantic.to(torch.int32)
+            target_semantic = target_semantic.to(dev).reshape(-1).contiguous()
+            if target_semantic.shape[0] != n:
+                raise ValueError("MipTrainer: target_semantic needs one label per ray")
+        if depth_keep is not None:
+            if target_depth is None:
+                raise ValueError("MipTrainer: depth_keep= masks the depth term: it needs target_depth=")
+            depth_keep = depth_keep.to(dev, torch.float32).reshape(-1).contiguous()
+        if self.rules is None:
+            return target_semantic, None, None, depth_keep
+        if sel_coords is None or img_i is None:
+            raise ValueError("MipTrainer with loss_rules: step() needs sel_coords= and img_i= (the pixels and the image of the batch)")
+        sel_coords = sel_coords.to(dev, torch.int64).contiguous()
+        if tuple(sel_coords.shape) != (n, 2):
+            raise ValueError("MipTrainer: sel_coords is the batcher's [n, 2] (row, col) per ray")
+        if not torch.is_tensor(img_i):                   # wrapped once per value: steps on the same image upload nothing
+            if self._img_dev is None or self._img_dev[0] != int(img_i):
+                self._img_dev = (int(img_i), torch.tensor([int(img_i)], dtype=torch.int64, device=dev))
+            img_i = self._img_dev[1]
+        return target_semantic, sel_coords, img_i.to(dev), depth_keep
+
+    def _forward_backward(self, rays, target_rgb, target_depth, conf, randomized, s_rand, u, ray_grads, on_done, img_i=None,
+                          target_semantic=None, sel_coords=None, depth_keep=None):
         """draws, both levels forward, the fused loss tail, the backward pass into the gradient arena (no exchange, no optimiser); with a
         pose table: its row applied to the rays in front, the ray gradients reduced into its gradient buffer behind"""
         m = self.model
         dev = m.arena.flat.device
         n = rays.origins.shape[0]
         ps = self.pose
+        masked = target_semantic is not None or depth_keep is not None or self.rules is not None
+        if masked:
+            target_semantic, sel_coords, rule_img, depth_keep = self._tail_extras(n, dev, target_depth, img_i, target_semantic, sel_coords, depth_keep)
         if ps is not None:
             ps.check_views()
             f32 = lambda x: x.detach().to(dev, torch.float32).contiguous()
@@ -373,7 +487,10 @@ class MipTrainer(_AdamState):
         s_rand = ds_rand if s_rand is None else s_rand
         u = du if u is None else u
         outs, ctx = m._run(rays, True, False, s_rand, u.contiguous(), noise0, noise1)
-        loss, g = self.loss_and_grads(outs, target_rgb, target_depth, conf)
+        if masked:
+            loss, g = self.loss_and_grads(outs, target_rgb, target_depth, conf, target_semantic, sel_coords, rule_img, depth_keep)
+        else:
+            loss, g = self.loss_and_grads(outs, target_rgb, target_depth, conf)
         self.last_ray_grads = m._backward(ctx, *g, on_done=on_done, ray_grads=ray_grads)
         if ps is not None:
             g_o, g_d, g_v = self.last_ray_grads
@@ -382,7 +499,7 @@ class MipTrainer(_AdamState):
 
     # ---- hipGraph capture of the whole step --------------------------------------------------------------------------------------
     def capture(self, rays, target_rgb, target_depth=None, conf=None, randomized=True, warmup=3, viewc=None, batcher=None, conf_extra=None,
-                img_i=None):
+                img_i=None, sem_extra=None, depth_keep_extra=None):
         """Capture one full training step (draws, forward, loss tail, backward, Adam: ~130 launches) in a hipGraph over the GIVEN tensors;
         afterwards `replay()` runs a step with one graph launch -- the caller refreshes the batch by copying into those tensors
         (`rays.origins.copy_(...)` etc.).  Worth it when the step is launch-bound: at 512 rays per GPU (the 8-GPU split of the
@@ -408,7 +525,12 @@ class MipTrainer(_AdamState):
         With a `pose_net` the captured step is the draw, ops.pose_apply fed by the batch's `img` tensor (without a batcher: `img_i`, an
         int64 [1] device tensor the caller refreshes like the rays), forward, backward with ray gradients, ops.pose_grad and both Adams
         (world > 1: both Adams and the two all-reduces follow the graph); the pose table, its moments and step count are snapshotted and
-        restored around the warm-up like the model's."""
+        restored around the warm-up like the model's.
+
+        `sem_extra` / `depth_keep_extra`: indices of the batcher's extra maps that serve as `step`'s `target_semantic` (a label map
+        stored as fp32) and `depth_keep` (a seg map); with loss rules the captured tail takes `sel_coords` and the image from the batch
+        buffers, so every replay applies the rules of the image it drew, without a host read.  (Labels, `depth_keep` and loss rules
+        are captured with a batcher only.)"""
         self._set_viewc(viewc)                           # (fn = 0: the centre is a kernel argument, i.e. a constant of the captured graph)
         a = self.model.arena
         dev = a.flat.device
@@ -422,16 +544,23 @@ class MipTrainer(_AdamState):
                 ps.step_dev = torch.tensor([ps.t], dtype=torch.int32, device=dev)
                 ps.lr_dev = torch.tensor([ps.lr], dtype=torch.float32, device=dev)
         self._batcher = batcher
+        target_semantic = sel_coords = depth_keep = None
         if batcher is not None:
             buf = batcher.buffers()
             self.batch = batcher.view(buf)
             rays, target_rgb, target_depth, _, _, extras = self.batch
             conf = None if conf_extra is None else extras[conf_extra]
+            target_semantic = None if sem_extra is None else extras[sem_extra]
+            depth_keep = None if depth_keep_extra is None else extras[depth_keep_extra]
             b_snap = (batcher.counter.clone(), batcher.step)
-            img_i = self.batch[4] if ps is not None else None
-        if ps is not None and not (torch.is_tensor(img_i) and img_i.is_cuda):
-            raise ValueError("capture() with a pose_net: img_i= must be an int64 [1] device tensor (a python int would be frozen into the graph)")
+            img_i = self.batch[4] if (ps is not None or self.rules is not None) else None
+            sel_coords = self.batch[3] if self.rules is not None else None
+        if self.rules is not None and batcher is None:
+            raise ValueError("capture() with loss_rules needs batcher=: the captured tail takes sel_coords and the image from its buffers")
+        if (ps is not None or self.rules is not None) and not (torch.is_tensor(img_i) and img_i.is_cuda):
+            raise ValueError("capture() with a pose_net or loss_rules: img_i= must be an int64 [1] device tensor (a python int would be frozen into the graph)")
         args = (rays, target_rgb, target_depth, conf)
+        tail = dict(target_semantic=target_semantic, sel_coords=sel_coords, depth_keep=depth_keep)
 
         def draw():
             if batcher is not None:
@@ -441,7 +570,7 @@ class MipTrainer(_AdamState):
         with torch.cuda.stream(side):                    # warm-up on a side stream
             for _ in range(warmup):
                 draw()
-                self.step(*args, randomized=randomized, img_i=img_i)
+                self.step(*args, randomized=randomized, img_i=img_i, **tail)
         torch.cuda.current_stream(dev).wait_stream(side)
         with torch.no_grad():
             a.flat.copy_(snap[0]); self.m.copy_(snap[1]); self.v.copy_(snap[2])
@@ -458,9 +587,9 @@ class MipTrainer(_AdamState):
         with torch.cuda.graph(self._graph):
             draw()
             if self.world == 1:
-                self._graph_loss, self._graph_outs = self.step(*args, randomized=randomized, img_i=img_i)
+                self._graph_loss, self._graph_outs = self.step(*args, randomized=randomized, img_i=img_i, **tail)
             else:
-                self._graph_loss, self._graph_outs = self._forward_backward(*args, randomized, None, None, False, None, img_i)
+                self._graph_loss, self._graph_outs = self._forward_backward(*args, randomized, None, None, False, None, img_i, **tail)
         if batcher is not None:
             batcher._step = b_snap[1]
         if self.world == 1:
