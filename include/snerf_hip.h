@@ -424,6 +424,17 @@ int snerf_mip_loss_tail_masked(const float* rgb, const float* tgt, const float* 
                                const float* depth_keep, long N, int Pf, int Sc, int disparity, float depth_lambda, float coarse_mult,
                                float prop_lambda, float semantic_lambda, float* out, float* g_rgb, float* g_dist1, float* g_dist0,
                                float* g_wc, float* g_sem, void* stream);
+/* snerf_mip_loss_tail_masked plus g_conf [N] (needs tdepth) = d total / d conf[r] = (|e1| + coarse_mult |e0|) depth_lambda / #depth on
+ * the rays the depth mean counts (e = the depth errors of DepthLoss above) and 0 elsewhere, always written in full: what the learned
+ * confidence (snerf_conf_grad) reduces to the gradient of its table.  Every other output keeps the bits snerf_mip_loss_tail_masked
+ * gives; with g_conf NULL the entry IS snerf_mip_loss_tail_masked. */
+int snerf_mip_loss_tail_gconf(const float* rgb, const float* tgt, const float* dist1, const float* dist0, const float* tdepth,
+                              const float* conf, const float* s_f, const float* w_f, const float* s_c, const float* w_c,
+                              const float* sem, const void* labels, int labels_f32, int C, const long* rows, const long* img_i,
+                              const int* rgb_row_limit, const int* depth_row_limit, const int* sem_valid, int n_images,
+                              const float* depth_keep, long N, int Pf, int Sc, int disparity, float depth_lambda, float coarse_mult,
+                              float prop_lambda, float semantic_lambda, float* out, float* g_rgb, float* g_dist1, float* g_dist0,
+                              float* g_wc, float* g_sem, float* g_conf, void* stream);
 
 /* zipnerf (path C) ray generation: s-nerfpp/zipnerf/internal/camera_utils.py:453-563 pixels_to_rays, perspective camera, no
  * distortion, no NDC.  pix_x / pix_y int32 [N] integer pixel coordinates, cam_idx int32 [N] (NULL = camera 0) into pixtocams
@@ -824,6 +835,31 @@ int snerf_pose_grad(const float* r, int n_cams, const long* cam_dev, int cam_hos
                     void* stream);
 /* doubles of scratch snerf_pose_grad needs for n rays */
 long snerf_pose_grad_ws(long n);
+
+/* Learned depth confidence (depth_conf = True, precompute_conf = True; s-nerf/model/confidence.py:65-73,193-206) on the rays of one
+ * batch: conf[r] = sum_k w_k maps[k, slot, row_r, col_r] / sum_k w_k with w_k = sigmoid(lambdas[k, i]), i the image of the batch and
+ * slot = slot_of_image[i] its position among the images with maps (the reference indexes the maps by position in i_train and lambdas
+ * by image: confidence.py:193,196), and conf[r] = 1 where sky[i, row_r, col_r] != 0 (confidence.py:202-203).
+ * maps fp32 [M,P,H,W] (M modes, 1..8; P images with maps), slot_of_image int32 [n_images] (in [0,P) or -1), lambdas fp32 [M,n_images],
+ * sky uint8 [n_images,H,W] (nullable), coords int64 [n,2] = (row, col) (a batcher's sel_coords).  w_k is formed in double and rounded
+ * once; the sums run in the reference's mode order as separate fp32 ops, then one fp32 division.  img_dev: int64 [1] in device memory
+ * (a batcher's img_out as it is: no host read), NULL = use img_host.  A device index outside the table, a slot of -1 (or past P) and a
+ * ray whose (row, col) lies outside the image give conf = 1 (the reference raises).  n = 0 is a no-op; bad arguments (a null required
+ * pointer, M outside 1..8, P / H / W / n_images < 1, n < 0, img_host outside the table) return 1 before any launch. */
+int snerf_conf_apply(const float* maps, int M, int P, int H, int W, const int* slot_of_image, const float* lambdas, int n_images,
+                     const unsigned char* sky, const long* img_dev, int img_host, const long* coords, long n, float* conf, void* stream);
+/* g_conf [n] = d loss / d conf (snerf_mip_loss_tail_gconf) reduced to the gradient of column i of lambdas: the M sums
+ * A_k = sum_r g_conf[r] maps[k, slot, row_r, col_r] over the rays that are not sky (and inside the image), in double in an order that
+ * depends on n only (a partial and a finish launch, no floating-point atomics: bit-reproducible), then
+ * d lambda_k = s_k (1 - s_k) / S (A_k - sum_j s_j A_j / S), s = sigmoid(lambdas[:, i]) and S = sum s in double, rounded once and ADDED
+ * into grad_lambdas[k, i] (fp32 [M,n_images]); the other columns are not touched.  An index outside the table or a slot of -1 adds
+ * nothing.  ws: >= snerf_conf_grad_ws(n) doubles of device scratch, ws_doubles = its length (short = bad argument).  Image index,
+ * n = 0 and bad arguments as for snerf_conf_apply.  Linear in the rays: per-slice results add up. */
+int snerf_conf_grad(const float* maps, int M, int P, int H, int W, const int* slot_of_image, const float* lambdas, int n_images,
+                    const unsigned char* sky, const long* img_dev, int img_host, const long* coords, const float* g_conf, long n,
+                    double* ws, long ws_doubles, float* grad_lambdas, void* stream);
+/* doubles of scratch snerf_conf_grad needs for n rays */
+long snerf_conf_grad_ws(long n);
 
 #ifdef __cplusplus
 }

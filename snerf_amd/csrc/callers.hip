@@ -408,7 +408,7 @@ __device__ __forceinline__ float loss_tail_proposal(const LossTail& a, long r) {
 
 // the depth term of ray r, which has a LiDAR target t != 0 and is one of the out[0] counted rays.  -> the term; *g1 / *g0 = d term /
 // d (dist1[r], dist0[r]).
-__device__ __forceinline__ float loss_tail_depth(const LossTail& a, long r, float t, float* g1, float* g0) {
+__device__ __forceinline__ float loss_tail_depth(const LossTail& a, long r, float t, float* g1, float* g0, float* gc = nullptr) {
   const float nv = a.out[0];
   const float cw = (a.conf != nullptr ? a.conf[r] : 1.f);
   const float d1 = a.dist1[r], d0 = a.dist0[r];
@@ -418,6 +418,7 @@ __device__ __forceinline__ float loss_tail_depth(const LossTail& a, long r, floa
   const float k = cw * a.depth_lambda / nv;
   *g1 = (e1 > 0.f ? 1.f : (e1 < 0.f ? -1.f : 0.f)) * s1 * k;
   *g0 = (e0 > 0.f ? 1.f : (e0 < 0.f ? -1.f : 0.f)) * s0 * k * a.coarse_mult;
+  if (gc != nullptr) *gc = (fabsf(e1) + a.coarse_mult * fabsf(e0)) * (a.depth_lambda / nv);      // d term / d conf[r]
   return (fabsf(e1) + a.coarse_mult * fabsf(e0)) * k;
 }
 
@@ -491,7 +492,10 @@ __global__ __launch_bounds__(1024) void loss_prepare_masked_kernel(LossTailMaske
   if (threadIdx.x >= 3 && threadIdx.x < 8) a.t.out[threadIdx.x - 2] = 0.f;      // out[1..5]
 }
 
-__global__ __launch_bounds__(64) void loss_tail_masked_kernel(LossTailMasked a) {
+// GCONF: also write g_conf[r] = d total / d conf[r] (the learned confidence, confidence.hip); the other outputs keep their bits (this
+// unit is built without fp contraction, so the extra statement cannot fuse into theirs)
+template <bool GCONF>
+__global__ __launch_bounds__(64) void loss_tail_masked_kernel(LossTailMasked a, float* __restrict__ g_conf) {
   const LossTail& t = a.t;
   const long r = (long)blockIdx.x * 64 + threadIdx.x;
   float l_rgb = 0.f, l_dep = 0.f, l_prop = 0.f;
@@ -511,10 +515,11 @@ __global__ __launch_bounds__(64) void loss_tail_masked_kernel(LossTailMasked a) 
     // ---- depth: mean over the rays with a LiDAR target inside the depth mask
     if (t.tdepth != nullptr) {
       const float td = t.tdepth[r];
-      float g1 = 0.f, g0 = 0.f;
-      if (td != 0.f && (m & 2)) l_dep = loss_tail_depth(t, r, td, &g1, &g0);
+      float g1 = 0.f, g0 = 0.f, gc = 0.f;
+      if (td != 0.f && (m & 2)) l_dep = loss_tail_depth(t, r, td, &g1, &g0, GCONF ? &gc : nullptr);
       t.g_dist1[r] = g1;
       t.g_dist0[r] = g0;
+      if (GCONF) g_conf[r] = gc;
     }
     // ---- proposal: every ray
     if (t.s_c != nullptr) l_prop = loss_tail_proposal(t, r);
@@ -553,13 +558,15 @@ __global__ __launch_bounds__(64) void loss_tail_masked_kernel(LossTailMasked a) 
   }
 }
 
-extern "C" int snerf_mip_loss_tail_masked(const float* rgb, const float* tgt, const float* dist1, const float* dist0, const float* tdepth,
-                                          const float* conf, const float* s_f, const float* w_f, const float* s_c, const float* w_c,
-                                          const float* sem, const void* labels, int labels_f32, int C, const long* rows, const long* img_i,
-                                          const int* rgb_row_limit, const int* depth_row_limit, const int* sem_valid, int n_images,
-                                          const float* depth_keep, long N, int Pf, int Sc, int disparity, float depth_lambda, float coarse_mult,
-                                          float prop_lambda, float semantic_lambda, float* out, float* g_rgb, float* g_dist1, float* g_dist0,
-                                          float* g_wc, float* g_sem, void* stream) {
+// snerf_mip_loss_tail_masked that also returns g_conf [N] (nullable) = d total / d conf[r] = (|e1| + coarse_mult |e0|) depth_lambda / #depth
+// on the rays the depth mean counts and 0 elsewhere, for the learned confidence (confidence.hip)
+extern "C" int snerf_mip_loss_tail_gconf(const float* rgb, const float* tgt, const float* dist1, const float* dist0, const float* tdepth,
+                                         const float* conf, const float* s_f, const float* w_f, const float* s_c, const float* w_c,
+                                         const float* sem, const void* labels, int labels_f32, int C, const long* rows, const long* img_i,
+                                         const int* rgb_row_limit, const int* depth_row_limit, const int* sem_valid, int n_images,
+                                         const float* depth_keep, long N, int Pf, int Sc, int disparity, float depth_lambda, float coarse_mult,
+                                         float prop_lambda, float semantic_lambda, float* out, float* g_rgb, float* g_dist1, float* g_dist0,
+                                         float* g_wc, float* g_sem, float* g_conf, void* stream) {
   if (N <= 0) return SNERF_OK;
   if (rgb == nullptr || tgt == nullptr || out == nullptr || g_rgb == nullptr) return SNERF_ERR_ARG;
   if (tdepth != nullptr && (dist1 == nullptr || dist0 == nullptr || g_dist1 == nullptr || g_dist0 == nullptr)) return SNERF_ERR_ARG;
@@ -571,12 +578,27 @@ extern "C" int snerf_mip_loss_tail_masked(const float* rgb, const float* tgt, co
   if (n_rule != 0 && n_rule != 5) return SNERF_ERR_ARG;
   if (rows != nullptr && n_images < 1) return SNERF_ERR_ARG;
   if (depth_keep != nullptr && tdepth == nullptr) return SNERF_ERR_ARG;
+  if (g_conf != nullptr && tdepth == nullptr) return SNERF_ERR_ARG;      // (g_conf is a by-product of the depth term)
   LossTailMasked a{{rgb, tgt, dist1, dist0, tdepth, conf, s_f, w_f, s_c, w_c, N, Pf, Sc, disparity, depth_lambda, coarse_mult, prop_lambda, out,
                     g_rgb, g_dist1, g_dist0, g_wc},
                    sem, labels, labels_f32, C, rows, img_i, rgb_row_limit, depth_row_limit, sem_valid, n_images, depth_keep, semantic_lambda, g_sem};
   hipLaunchKernelGGL(loss_prepare_masked_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, a);
-  hipLaunchKernelGGL(loss_tail_masked_kernel, dim3((unsigned)((N + 63) / 64)), dim3(64), 0, (hipStream_t)stream, a);
+  const dim3 grid((unsigned)((N + 63) / 64));
+  if (g_conf != nullptr) hipLaunchKernelGGL(loss_tail_masked_kernel<true>, grid, dim3(64), 0, (hipStream_t)stream, a, g_conf);
+  else hipLaunchKernelGGL(loss_tail_masked_kernel<false>, grid, dim3(64), 0, (hipStream_t)stream, a, g_conf);
   return snerf_check_launch();
+}
+
+extern "C" int snerf_mip_loss_tail_masked(const float* rgb, const float* tgt, const float* dist1, const float* dist0, const float* tdepth,
+                                          const float* conf, const float* s_f, const float* w_f, const float* s_c, const float* w_c,
+                                          const float* sem, const void* labels, int labels_f32, int C, const long* rows, const long* img_i,
+                                          const int* rgb_row_limit, const int* depth_row_limit, const int* sem_valid, int n_images,
+                                          const float* depth_keep, long N, int Pf, int Sc, int disparity, float depth_lambda, float coarse_mult,
+                                          float prop_lambda, float semantic_lambda, float* out, float* g_rgb, float* g_dist1, float* g_dist0,
+                                          float* g_wc, float* g_sem, void* stream) {
+  return snerf_mip_loss_tail_gconf(rgb, tgt, dist1, dist0, tdepth, conf, s_f, w_f, s_c, w_c, sem, labels, labels_f32, C, rows, img_i, rgb_row_limit,
+                                   depth_row_limit, sem_valid, n_images, depth_keep, N, Pf, Sc, disparity, depth_lambda, coarse_mult, prop_lambda,
+                                   semantic_lambda, out, g_rgb, g_dist1, g_dist0, g_wc, g_sem, nullptr, stream);
 }
 
 // ---------------------------------------------------------------------------

@@ -1412,8 +1412,10 @@ def mip_loss_tail(rgb, tgt, dist1, dist0, tdepth, conf, s_f, w_f, s_c, w_c, disp
 
 def mip_loss_tail_masked(rgb, tgt, dist1, dist0, tdepth, conf, s_f, w_f, s_c, w_c, disparity, depth_lambda, coarse_mult, prop_lambda,
                          sem=None, labels=None, semantic_lambda=0.1, rows=None, img_i=None, rgb_row_limit=None, depth_row_limit=None,
-                         sem_valid=None, depth_keep=None):
+                         sem_valid=None, depth_keep=None, want_g_conf=False):
     """snerf_mip_loss_tail_masked: mip_loss_tail with the per-image rules of s-nerf/train.py:131-209 (each new argument None = absent).
+    want_g_conf (needs tdepth): snerf_mip_loss_tail_gconf -- the same outputs, bit for bit, followed by g_conf [n] = d total / d conf,
+    the input of conf_grad.
     sem [n,C] fp32 composited logits + labels [n] (int32, or fp32 holding exact integers -- a batcher's extras row; -100 = ignored, and
     so is any other label outside [0, C): the reference raises on one); rows = the batcher's sel_coords (int64 [n,2]), img_i int64 [1]
     device tensor (read by the kernel, never on the host) and the three int32 per-image tables (trainer.MipLossRules): all or none;
@@ -1445,10 +1447,16 @@ def mip_loss_tail_masked(rgb, tgt, dist1, dist0, tdepth, conf, s_f, w_f, s_c, w_
         n_img = rgb_row_limit.numel()
         for t in (rgb_row_limit, depth_row_limit, sem_valid):
             assert t.dtype == torch.int32 and t.is_cuda and t.is_contiguous() and t.numel() == n_img
-    _lib.call("snerf_mip_loss_tail_masked", _p(c(rgb)), _p(c(tgt)), _p(c(dist1)), _p(c(dist0)), _p(c(tdepth)), _p(c(conf)), _p(c(s_f)), _p(c(w_f)),
-              _p(c(s_c)), _p(c(w_c)), _p(c(sem)), _p(labels), lab_f32, C, _p(rows), _p(img_i), _p(rgb_row_limit), _p(depth_row_limit), _p(sem_valid),
-              n_img, _p(c(depth_keep)), n, Pf, Sc, int(bool(disparity)), float(depth_lambda), float(coarse_mult), float(prop_lambda),
-              float(semantic_lambda), _p(out), _p(g_rgb), _p(g1), _p(g0), _p(gw), _p(gs), _stream())
+    args = (_p(c(rgb)), _p(c(tgt)), _p(c(dist1)), _p(c(dist0)), _p(c(tdepth)), _p(c(conf)), _p(c(s_f)), _p(c(w_f)),
+            _p(c(s_c)), _p(c(w_c)), _p(c(sem)), _p(labels), lab_f32, C, _p(rows), _p(img_i), _p(rgb_row_limit), _p(depth_row_limit), _p(sem_valid),
+            n_img, _p(c(depth_keep)), n, Pf, Sc, int(bool(disparity)), float(depth_lambda), float(coarse_mult), float(prop_lambda),
+            float(semantic_lambda), _p(out), _p(g_rgb), _p(g1), _p(g0), _p(gw), _p(gs))
+    if want_g_conf:
+        assert tdepth is not None, "g_conf is a by-product of the depth term: tdepth is needed"
+        gc = torch.empty(n, dtype=torch.float32, device=dev)
+        _lib.call("snerf_mip_loss_tail_gconf", *args, _p(gc), _stream())
+        return out, g_rgb, g1, g0, gw, gs, gc
+    _lib.call("snerf_mip_loss_tail_masked", *args, _stream())
     return out, g_rgb, g1, g0, gw, gs
 
 
@@ -1544,6 +1552,50 @@ def pose_grad(r, cam, g_o, g_d, g_v, directions, viewdirs, grad_r, grad_t=None, 
     cam_dev, cam_host = _cam_args(cam)
     _lib.call("snerf_pose_grad", _p(r), r.shape[0], cam_dev, cam_host, _p(g_o), _p(g_d), _p(g_v), _p(directions), _p(viewdirs), n, _p(ws),
               ws.numel(), _p(grad_r), _p(grad_t), _stream())
+
+
+def _conf_args(maps, slot_of_image, lambdas, sky, img, coords):
+    """checks and the leading arguments shared by snerf_conf_apply / snerf_conf_grad"""
+    _f32c(maps); _f32c(lambdas)
+    assert maps.dim() == 4 and lambdas.dim() == 2 and lambdas.shape[0] == maps.shape[0], "maps [M,P,H,W] and lambdas [M,n_images]"
+    M, P, H, W = maps.shape
+    n_img = lambdas.shape[1]
+    assert slot_of_image.is_cuda and slot_of_image.dtype == torch.int32 and slot_of_image.is_contiguous() and slot_of_image.numel() == n_img
+    assert sky is None or (sky.is_cuda and sky.dtype == torch.uint8 and sky.is_contiguous() and tuple(sky.shape) == (n_img, H, W)), \
+        "sky: uint8 [n_images,H,W]"
+    assert coords.is_cuda and coords.dtype == torch.int64 and coords.is_contiguous() and coords.dim() == 2 and coords.shape[1] == 2, \
+        "coords: the batcher's sel_coords, int64 [n, 2]"
+    img_dev, img_host = _cam_args(img)
+    return (_p(maps), M, P, H, W, _p(slot_of_image), _p(lambdas), n_img, _p(sky), img_dev, img_host, _p(coords)), coords.shape[0]
+
+
+def conf_apply(maps, slot_of_image, lambdas, sky, img, coords):
+    """snerf_conf_apply: the learned confidence of the rays at pixels coords (int64 [n,2] = (row, col)) of image `img` (a python int, or
+    an int64 [1] device tensor that the kernel reads: no host sync) -> conf [n] = sum_k sigmoid(lambdas[k,img]) maps[k,slot,row,col] /
+    sum_k sigmoid(lambdas[k,img]), 1 on sky pixels (sky uint8 [n_images,H,W] or None) and for an image without maps.
+    maps fp32 [M,P,H,W], slot_of_image int32 [n_images], lambdas fp32 [M,n_images] (confidence.ConfidenceMaps / Confidence)."""
+    head, n = _conf_args(maps, slot_of_image, lambdas, sky, img, coords)
+    conf = torch.empty(n, dtype=torch.float32, device=maps.device)
+    _lib.call("snerf_conf_apply", *head, n, _p(conf), _stream())
+    return conf
+
+
+def conf_grad_ws(n):
+    """doubles of scratch conf_grad needs for n rays (snerf_conf_grad_ws)"""
+    return int(_lib.query("snerf_conf_grad_ws", int(n)))
+
+
+def conf_grad(maps, slot_of_image, lambdas, sky, img, coords, g_conf, grad_lambdas, ws=None):
+    """snerf_conf_grad: g_conf [n] = d loss / d conf reduced to the gradient of column `img` of lambdas, ADDED into grad_lambdas
+    [M,n_images].  Deterministic (double sums in a fixed order, no atomics).  ws: fp64 scratch of >= conf_grad_ws(n) elements
+    (allocated when None)."""
+    head, n = _conf_args(maps, slot_of_image, lambdas, sky, img, coords)
+    _f32c(g_conf); _f32c(grad_lambdas)
+    assert g_conf.numel() == n and grad_lambdas.shape == lambdas.shape
+    if ws is None:
+        ws = torch.empty(conf_grad_ws(n), dtype=torch.float64, device=maps.device)
+    assert ws.is_cuda and ws.dtype == torch.float64 and ws.is_contiguous()
+    _lib.call("snerf_conf_grad", *head, _p(g_conf), n, _p(ws), ws.numel(), _p(grad_lambdas), _stream())
 
 
 def zip_ray_batch(images, depths, semantics, masks, pixtocams, camtoworlds, local2global, near, far, border, patch_size, single_image, seed,

@@ -157,10 +157,12 @@ class _PoseAdam:
     torch.optim.Adam([{'params': [...], 'lr': 1e-4}]).state_dict(): the `optimizer` entry of the reference's pose/NNNNNN.tar.
     The module must stay where the trainer put it: a later `pose_net.to(...)` / `.float()` that reallocates its parameters would cut
     them off from the flat buffer (`check_views` raises then, before a step trains a table the module no longer sees)."""
+    what = "pose"                                   # (names the table in the messages of load_state_dict; _ConfAdam shares them)
 
     def __init__(self, pose_net, device, lr, betas, eps):
         self.net = pose_net
         pose_net.to(device)
+        self.shape = (pose_net.num_cams, 3)         # of every trained parameter
         self.names = [n for n in ("r", "t") if getattr(pose_net, n).requires_grad]
         if not self.names:
             raise ValueError("pose_net: neither r nor t is trained (learn_R / learn_t)")
@@ -212,19 +214,19 @@ class _PoseAdam:
                       zero_grad=True, nonfinite=nonfinite, step_dev=self.step_dev, lr_dev=self.lr_dev)
 
     def state_dict(self):
-        k = 3 * self.net.num_cams
-        state = {i: {"step": torch.tensor(float(self.t)), "exp_avg": self.m[i * k:(i + 1) * k].view(-1, 3).clone(),
-                     "exp_avg_sq": self.v[i * k:(i + 1) * k].view(-1, 3).clone()} for i in range(len(self.names))}
+        k = self.shape[0] * self.shape[1]
+        state = {i: {"step": torch.tensor(float(self.t)), "exp_avg": self.m[i * k:(i + 1) * k].view(self.shape).clone(),
+                     "exp_avg_sq": self.v[i * k:(i + 1) * k].view(self.shape).clone()} for i in range(len(self.names))}
         group = {"lr": self.lr, "betas": tuple(self.betas), "eps": self.eps, "weight_decay": 0, "amsgrad": False, "maximize": False,
                  "foreach": None, "capturable": False, "differentiable": False, "fused": None, "params": list(range(len(self.names)))}
         return {"state": state, "param_groups": [group]}
 
     def load_state_dict(self, sd):
-        k = 3 * self.net.num_cams
+        k = self.shape[0] * self.shape[1]
         groups = sd["param_groups"]
         order = [i for g in groups for i in g["params"]]
         if len(groups) != 1 or len(order) != len(self.names):
-            raise ValueError(f"pose optimizer state: one param group over {len(self.names)} parameters ({', '.join(self.names)}) expected")
+            raise ValueError(f"{self.what} optimizer state: one param group over {len(self.names)} parameters ({', '.join(self.names)}) expected")
         g0 = groups[0]
         if float(g0.get("weight_decay", 0) or 0) != 0 or g0.get("amsgrad", False):
             raise ValueError("the fused Adam launch has no weight decay / amsgrad")
@@ -238,17 +240,64 @@ class _PoseAdam:
                 if st is None:                              # (the saved optimizer never stepped)
                     self.m[i * k:(i + 1) * k].zero_(); self.v[i * k:(i + 1) * k].zero_()
                     continue
-                if tuple(st["exp_avg"].shape) != (self.net.num_cams, 3):
-                    raise ValueError(f"pose optimizer state of {self.names[i]}: shape {tuple(st['exp_avg'].shape)}, the table has {(self.net.num_cams, 3)}")
+                if tuple(st["exp_avg"].shape) != self.shape:
+                    raise ValueError(f"{self.what} optimizer state of {self.names[i]}: shape {tuple(st['exp_avg'].shape)}, the table has {self.shape}")
                 self.m[i * k:(i + 1) * k].copy_(st["exp_avg"].reshape(-1).to(self.m.device, torch.float32))
                 self.v[i * k:(i + 1) * k].copy_(st["exp_avg_sq"].reshape(-1).to(self.v.device, torch.float32))
                 steps.add(int(float(st["step"])))
         if len(steps) > 1:
-            raise ValueError(f"one Adam launch covers the pose parameters: the saved parameters disagree on the step count ({sorted(steps)})")
+            raise ValueError(f"one Adam launch covers the {self.what} parameters: the saved parameters disagree on the step count ({sorted(steps)})")
         self.t = steps.pop() if steps else 0
         self.lr, self.betas, self.eps = float(g0["lr"]), new_betas, new_eps
         if self.step_dev is not None:
             self.step_dev.fill_(self.t)
+
+
+class _ConfAdam(_PoseAdam):
+    """The learned depth confidence of a trainer (confidence.Confidence + confidence.ConfidenceMaps) and its Adam (model/confidence.py:182-184:
+    its own optimiser, lr 1e-3) on the device: the flat buffer is `lambdas` itself (moved to the device once), with a gradient buffer and
+    two moment buffers of its shape; one ops.adam_step covers the table.  Dense over the whole table like torch.optim.Adam: a column
+    visited earlier keeps moving on its momentum, a column never visited has m = v = 0 and stays put exactly.  State in the layout of
+    torch.optim.Adam([{'params': [lambdas], 'lr': 1e-3}]).state_dict(): the `optimizer_conf` entry of the reference's checkpoint
+    (_PoseAdam's code, over the one parameter).  The module must stay where the trainer put it (`check_views`, as for the pose table)."""
+    what = "confidence"
+
+    def __init__(self, conf_net, maps, device, lr, betas, eps):
+        self.net = conf_net
+        conf_net.to(device)
+        p = conf_net.lambdas
+        if p.dtype != torch.float32 or p.dim() != 2 or not p.requires_grad:
+            raise ValueError("conf_net.lambdas: a trained fp32 [n_modes, n_images] table expected")
+        p.data = p.data.contiguous()
+        self.maps = maps.for_model(conf_net).to(device)
+        self.names, self.shape = ["lambdas"], tuple(p.shape)
+        self.flat = p.data.view(-1)
+        self.grad, self.m, self.v = torch.zeros_like(self.flat), torch.zeros_like(self.flat), torch.zeros_like(self.flat)
+        self.g = self.grad.view(p.shape)
+        self.lr, self.betas, self.eps, self.t = float(lr), tuple(betas), float(eps), 0
+        self.step_dev = self.lr_dev = None
+        self._ws = None
+
+    def check_views(self):
+        if self.net.lambdas.data_ptr() != self.flat.data_ptr():
+            raise RuntimeError("conf_net.lambdas no longer lives where the trainer trains it (was the module moved or cast after MipTrainer took it?)")
+
+    def workspace(self, n):
+        """fp64 scratch of ops.conf_grad for n rays, kept between steps"""
+        need = ops.conf_grad_ws(n)
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = torch.empty(need, dtype=torch.float64, device=self.flat.device)
+        return self._ws
+
+    def apply(self, img, coords):
+        """-> the confidence of the rays at pixels coords of image img, [n]"""
+        m = self.maps
+        return ops.conf_apply(m.maps, m.slot_of_image, self.net.lambdas.data, m.sky, img, coords)
+
+    def reduce(self, img, coords, g_conf):
+        """d loss / d conf [n] into the gradient buffer's column of image img"""
+        m = self.maps
+        ops.conf_grad(m.maps, m.slot_of_image, self.net.lambdas.data, m.sky, img, coords, g_conf, self.g, ws=self.workspace(coords.shape[0]))
 
 
 class MipLossRules:
@@ -300,7 +349,8 @@ class MipTrainer(_AdamState):
     def __init__(self, model, lr=5e-4, betas=(0.9, 0.999), eps=1e-8, depth_lambda=0.2, coarse_depth_mult=0.2,
                  proposal_loss=False, proposal_lambda=0.05, disparity_depth=True, process_group=None,
                  nonfinite="zero", grad_max_val=0.0, grad_max_norm=0.0, exchange_when_single=False,
-                 pose_net=None, pose_lr=1e-4, pose_betas=(0.9, 0.999), pose_eps=1e-8, semantic_lambda=0.1, loss_rules=None):
+                 pose_net=None, pose_lr=1e-4, pose_betas=(0.9, 0.999), pose_eps=1e-8, semantic_lambda=0.1, loss_rules=None,
+                 conf_net=None, conf_maps=None, conf_lr=1e-3, conf_betas=(0.9, 0.999), conf_eps=1e-8):
         """`nonfinite` / `grad_max_val` / `grad_max_norm`: gradient hygiene folded into the Adam launch (ops.adam_step).  The s-nerf
         reference has none (train.py:212-215 drops into pdb on a failing backward); the default "zero" keeps one NaN / Inf gradient
         (1/(depth + eps), a bf16 overflow) from poisoning m, v and the parameters of the whole arena on every rank.  "keep" = plain Adam.
@@ -309,7 +359,11 @@ class MipTrainer(_AdamState):
         `pose_lr` / `pose_betas` / `pose_eps`: their own Adam (utils/model_utils.py:36-42: lr 1e-4, no schedule).
         `semantic_lambda` (arg_parser.py:166): weight of the semantic cross-entropy of `step`'s `target_semantic`.  `loss_rules`
         (MipLossRules): the Waymo side-camera / back-camera masks and the images with labels, applied inside the loss tail to the image
-        `step`'s `img_i` names."""
+        `step`'s `img_i` names.
+        `conf_net` + `conf_maps` (confidence.Confidence / ConfidenceMaps; configs: depth_conf = True, precompute_conf = True): the
+        per-ray depth confidence is mixed from the precomputed maps with the learned per-image weights and those are trained inside
+        the step (`self.conf`, _ConfAdam) -- see `step`.  `conf_lr` / `conf_betas` / `conf_eps`: their own Adam (confidence.py:182-184:
+        lr 1e-3, no schedule)."""
         self.model = model
         self.lr, self.betas, self.eps = lr, betas, eps
         self.nonfinite, self.grad_max_val, self.grad_max_norm = nonfinite, float(grad_max_val), float(grad_max_norm)
@@ -329,6 +383,9 @@ class MipTrainer(_AdamState):
         self._rule_tables = None if loss_rules is None else loss_rules.on(a.flat.device)
         self.last_semantic_loss = self.last_counts = None
         self._img_dev = None                         # (python int img_i, its int64 [1] device tensor)
+        if (conf_net is None) != (conf_maps is None):
+            raise ValueError("MipTrainer: conf_net= and conf_maps= go together (the learned weights and the maps they mix)")
+        self.conf = None if conf_net is None else _ConfAdam(conf_net, conf_maps, a.flat.device, conf_lr, conf_betas, conf_eps)
 
     def broadcast_parameters(self, src=0):
         if self.world > 1:
@@ -337,6 +394,8 @@ class MipTrainer(_AdamState):
             if self.pose is not None:                    # the whole table: an untrained t (learn_t=False) is applied to the rays all the same
                 for p in (self.pose.net.r, self.pose.net.t):
                     dist.broadcast(p.data, src=src, group=self.pg)
+            if self.conf is not None:
+                dist.broadcast(self.conf.flat, src=src, group=self.pg)
 
     def pose_state_dict(self):
         """the pose optimiser's state in torch.optim.Adam's layout (the `optimizer` entry of the reference's pose/NNNNNN.tar; the table
@@ -353,6 +412,21 @@ class MipTrainer(_AdamState):
         self.pose.t += 1
         self.pose.step(self.world, self.nonfinite)
 
+    def conf_state_dict(self):
+        """the confidence optimiser's state in torch.optim.Adam's layout (the `optimizer_conf` entry of the reference's checkpoint; the
+        table itself is `conf_net.state_dict()`, its `confidence` entry)"""
+        return self.conf.state_dict()
+
+    def load_conf_state_dict(self, sd):
+        self.conf.load_state_dict(sd)
+
+    def _conf_adam(self):
+        """the confidence table's Adam step (after the model's): the ranks' table gradients are summed like the model's, 1 / world folded in"""
+        if self.world > 1:
+            dist.all_reduce(self.conf.grad, op=dist.ReduceOp.SUM, group=self.pg)
+        self.conf.t += 1
+        self.conf.step(self.world, self.nonfinite)
+
     def _adam(self):
         """One fused Adam launch over the flat arena; folds the data-parallel mean, the gradient hygiene and zero_grad."""
         a = self.model.arena
@@ -362,26 +436,30 @@ class MipTrainer(_AdamState):
                       step_dev=self._step_dev, lr_dev=self._lr_dev)
         a.bump()
 
-    def loss_and_grads(self, outs, target_rgb, target_depth, conf, target_semantic=None, sel_coords=None, img_i=None, depth_keep=None):
+    def loss_and_grads(self, outs, target_rgb, target_depth, conf, target_semantic=None, sel_coords=None, img_i=None, depth_keep=None,
+                       want_g_conf=False):
         """The reference's per-ray loss tail (train.py:150-208) in ONE kernel, `snerf_mip_loss_tail`: RGB MSE, the
         confidence-weighted (disparity) depth loss on both levels masked to rays with a LiDAR target, and -- with
         `proposal_loss` -- ProposalLoss on the two histograms.  Returns (loss [device scalar], output gradients).
         With `target_semantic`, `depth_keep` or loss rules (see `step`): `snerf_mip_loss_tail_masked`, which adds the semantic
         cross-entropy and the per-image masks of train.py:131-209; the output gradients then end with g_semantic.  `last_losses` keeps
-        its four entries; `last_semantic_loss` and `last_counts` = (#depth rays, #rgb rays, #semantic rays) are device scalars too."""
+        its four entries; `last_semantic_loss` and `last_counts` = (#depth rays, #rgb rays, #semantic rays) are device scalars too.
+        `want_g_conf` (the learned confidence): the masked tail's g_conf route; `last_g_conf` [n] = d loss / d conf."""
         dist0, acc0, s0, w0, rgb1, dist1, acc1, s1, w1 = outs[:9]
         prop = self.proposal_loss
         rules = self.rules
-        if target_semantic is not None or depth_keep is not None or rules is not None:
+        if target_semantic is not None or depth_keep is not None or rules is not None or want_g_conf:
             tables = self._rule_tables if rules is not None else (None, None, None)
             with_sem = target_semantic is not None
-            out, g_rgb1, g_dist1, g_dist0, g_w0, g_sem = ops.mip_loss_tail_masked(
+            out, g_rgb1, g_dist1, g_dist0, g_w0, g_sem, *g_conf = ops.mip_loss_tail_masked(
                 rgb1, target_rgb, dist1 if target_depth is not None else None, dist0 if target_depth is not None else None,
                 target_depth, conf, s1 if prop else None, w1 if prop else None, s0 if prop else None, w0 if prop else None,
                 self.disparity_depth, self.depth_lambda, self.coarse_depth_mult, self.proposal_lambda,
                 sem=outs[9] if with_sem else None, labels=target_semantic, semantic_lambda=self.semantic_lambda,
                 rows=sel_coords if rules is not None else None, img_i=img_i if rules is not None else None,
-                rgb_row_limit=tables[0], depth_row_limit=tables[1], sem_valid=tables[2], depth_keep=depth_keep)
+                rgb_row_limit=tables[0], depth_row_limit=tables[1], sem_valid=tables[2], depth_keep=depth_keep,
+                **(dict(want_g_conf=True) if want_g_conf else {}))
+            self.last_g_conf = g_conf[0] if want_g_conf else None
             self.last_losses = out[:4]
             self.last_semantic_loss, self.last_counts = out[5], (out[0], out[6], out[7])
             return out[4], (g_dist0, None, g_w0, g_rgb1, g_dist1, None, None, g_sem)
@@ -411,12 +489,23 @@ class MipTrainer(_AdamState):
         the RGB row limit leave the RGB and semantic means, rays at or past the depth row limit (or with depth_keep != 0) the depth mean
         -- and, as in the reference, only that one -- and images outside the rules' semantic_index have no semantic term.  A term that counts
         no ray is 0 with zero gradients, where the reference's empty mean is NaN.  world > 1: every rank forms its means over its
-        own shard of the batch, like the reference under DDP and like the depth term's count before."""
+        own shard of the batch, like the reference under DDP and like the depth term's count before.
+        With a `conf_net`: `target_depth`, `sel_coords` and `img_i` are needed and `conf=` is refused; the step mixes the confidence of
+        the batch's rays from the maps with the learned weights of image img_i (ops.conf_apply, never a host read of the index), runs
+        the loss tail's g_conf route (loss rules, `depth_keep` and the semantic term keep working), reduces d loss / d conf to the
+        gradient of the image's column of the table right behind the tail (ops.conf_grad) and follows the model's Adam (and the pose
+        table's) with the confidence table's.  `last_conf` [n] is the confidence the step used."""
         self._set_viewc(viewc)
         if self.pose is not None and img_i is None:
             raise ValueError("MipTrainer with a pose_net: step() needs img_i= (the image the rays belong to)")
-        if self.pose is None and self.rules is None and img_i is not None:
+        if self.pose is None and self.rules is None and self.conf is None and img_i is not None:
             raise ValueError("MipTrainer: img_i= given without a pose_net or loss_rules")
+        if self.conf is not None:
+            if conf is not None:
+                raise ValueError("MipTrainer with a conf_net: the step forms the confidence itself, conf= cannot be given")
+            if target_depth is None or sel_coords is None or img_i is None:
+                raise ValueError("MipTrainer with a conf_net: step() needs target_depth=, sel_coords= and img_i= (the confidence weighs the depth term "
+                                 "of the batch's pixels with the weights of its image)")
         ex = _GradExchange(self.model.arena, self.world, self.pg, self.single_rank_exchange)
         # every block of the gradient arena goes on the wire as soon as the backward pass has finished it (heads, then trunk layer by
         # trunk layer, then the proposal network): the collectives run under the remaining backward kernels
@@ -427,6 +516,8 @@ class MipTrainer(_AdamState):
         self._adam()                                      # graph mode: step count and lr live on the device (capture / replay below)
         if self.pose is not None:
             self._pose_adam()
+        if self.conf is not None:
+            self._conf_adam()
         return loss, outs
 
     def _set_viewc(self, viewc):
@@ -473,7 +564,16 @@ class MipTrainer(_AdamState):
         dev = m.arena.flat.device
         n = rays.origins.shape[0]
         ps = self.pose
+        cf = self.conf
+        if cf is not None:
+            cf.check_views()
+            c_coords = sel_coords.to(dev, torch.int64).contiguous()
+            if tuple(c_coords.shape) != (n, 2):
+                raise ValueError("MipTrainer: sel_coords is the batcher's [n, 2] (row, col) per ray")
+            c_img = img_i.to(dev) if torch.is_tensor(img_i) else int(img_i)
+            conf = self.last_conf = cf.apply(c_img, c_coords)
         masked = target_semantic is not None or depth_keep is not None or self.rules is not None
+        rule_img = None
         if masked:
             target_semantic, sel_coords, rule_img, depth_keep = self._tail_extras(n, dev, target_depth, img_i, target_semantic, sel_coords, depth_keep)
         if ps is not None:
@@ -487,8 +587,11 @@ class MipTrainer(_AdamState):
         s_rand = ds_rand if s_rand is None else s_rand
         u = du if u is None else u
         outs, ctx = m._run(rays, True, False, s_rand, u.contiguous(), noise0, noise1)
-        if masked:
-            loss, g = self.loss_and_grads(outs, target_rgb, target_depth, conf, target_semantic, sel_coords, rule_img, depth_keep)
+        if masked or cf is not None:
+            loss, g = self.loss_and_grads(outs, target_rgb, target_depth, conf, target_semantic, sel_coords if masked else None, rule_img,
+                                          depth_keep, want_g_conf=cf is not None)
+            if cf is not None:
+                cf.reduce(c_img, c_coords, self.last_g_conf)
         else:
             loss, g = self.loss_and_grads(outs, target_rgb, target_depth, conf)
         self.last_ray_grads = m._backward(ctx, *g, on_done=on_done, ray_grads=ray_grads)
@@ -527,6 +630,10 @@ class MipTrainer(_AdamState):
         (world > 1: both Adams and the two all-reduces follow the graph); the pose table, its moments and step count are snapshotted and
         restored around the warm-up like the model's.
 
+        With a `conf_net` (batcher only; `conf_extra` stays None) the captured step also holds ops.conf_apply and ops.conf_grad, fed by the
+        batch's `sel_coords` and `img` buffers, and the confidence table's Adam (world > 1: that Adam and its all-reduce follow the
+        graph); the table, its moments and step count are snapshotted and restored around the warm-up like the pose table's.
+
         `sem_extra` / `depth_keep_extra`: indices of the batcher's extra maps that serve as `step`'s `target_semantic` (a label map
         stored as fp32) and `depth_keep` (a seg map); with loss rules the captured tail takes `sel_coords` and the image from the batch
         buffers, so every replay applies the rules of the image it drew, without a host read.  (Labels, `depth_keep` and loss rules
@@ -537,12 +644,17 @@ class MipTrainer(_AdamState):
         snap = (a.flat.clone(), self.m.clone(), self.v.clone(), self.t)
         ps = self.pose
         p_snap = None if ps is None else ps.snapshot()
+        cf = self.conf
+        c_snap = None if cf is None else cf.snapshot()
         if self.world == 1:
             self._step_dev = torch.tensor([self.t], dtype=torch.int32, device=dev)
             self._lr_dev = torch.tensor([self.lr], dtype=torch.float32, device=dev)
             if ps is not None:
                 ps.step_dev = torch.tensor([ps.t], dtype=torch.int32, device=dev)
                 ps.lr_dev = torch.tensor([ps.lr], dtype=torch.float32, device=dev)
+            if cf is not None:
+                cf.step_dev = torch.tensor([cf.t], dtype=torch.int32, device=dev)
+                cf.lr_dev = torch.tensor([cf.lr], dtype=torch.float32, device=dev)
         self._batcher = batcher
         target_semantic = sel_coords = depth_keep = None
         if batcher is not None:
@@ -553,11 +665,13 @@ class MipTrainer(_AdamState):
             target_semantic = None if sem_extra is None else extras[sem_extra]
             depth_keep = None if depth_keep_extra is None else extras[depth_keep_extra]
             b_snap = (batcher.counter.clone(), batcher.step)
-            img_i = self.batch[4] if (ps is not None or self.rules is not None) else None
-            sel_coords = self.batch[3] if self.rules is not None else None
+            img_i = self.batch[4] if (ps is not None or self.rules is not None or cf is not None) else None
+            sel_coords = self.batch[3] if (self.rules is not None or cf is not None) else None
         if self.rules is not None and batcher is None:
             raise ValueError("capture() with loss_rules needs batcher=: the captured tail takes sel_coords and the image from its buffers")
-        if (ps is not None or self.rules is not None) and not (torch.is_tensor(img_i) and img_i.is_cuda):
+        if cf is not None and batcher is None:
+            raise ValueError("capture() with a conf_net needs batcher=: the captured step takes sel_coords and the image from its buffers")
+        if (ps is not None or self.rules is not None or cf is not None) and not (torch.is_tensor(img_i) and img_i.is_cuda):
             raise ValueError("capture() with a pose_net or loss_rules: img_i= must be an int64 [1] device tensor (a python int would be frozen into the graph)")
         args = (rays, target_rgb, target_depth, conf)
         tail = dict(target_semantic=target_semantic, sel_coords=sel_coords, depth_keep=depth_keep)
@@ -582,6 +696,8 @@ class MipTrainer(_AdamState):
                 batcher.counter.copy_(b_snap[0])
         if ps is not None:
             ps.restore(p_snap)
+        if cf is not None:
+            cf.restore(c_snap)
         a.bump()
         self._graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self._graph):
@@ -596,6 +712,8 @@ class MipTrainer(_AdamState):
             self.t -= 1                                  # capturing records the step, it does not run it
             if ps is not None:
                 ps.t -= 1
+            if cf is not None:
+                cf.t -= 1
         return self._graph_loss
 
     def replay(self):
@@ -607,6 +725,9 @@ class MipTrainer(_AdamState):
             if self.pose is not None:
                 self.pose.lr_dev.fill_(self.pose.lr)
                 self.pose.t += 1
+            if self.conf is not None:
+                self.conf.lr_dev.fill_(self.conf.lr)
+                self.conf.t += 1
             self._graph.replay()
             self.t += 1
             return self._graph_loss, self._graph_outs
@@ -617,6 +738,8 @@ class MipTrainer(_AdamState):
         self._adam()
         if self.pose is not None:
             self._pose_adam()
+        if self.conf is not None:
+            self._conf_adam()
         return self._graph_loss, self._graph_outs
 
 
