@@ -861,6 +861,33 @@ int snerf_conf_grad(const float* maps, int M, int P, int H, int W, const int* sl
 /* doubles of scratch snerf_conf_grad needs for n rays */
 long snerf_conf_grad_ws(long n);
 
+/* The reprojection confidence maps of one base image on the device: the rgb, ssim and depth modes of Confidence.precompute_conf_map
+ * (s-nerf/model/confidence.py:78-112 = get_reproj_conf, model/loss.py:271-327, over reproj_err :218-268, warping :138-179,
+ * sample_points :122-135 and utils/pytorch_msssim ssim).  One pass per neighbour, in the order given (select_conf_depends' sel_ids:
+ * the LAST neighbour is special): every base pixel is projected into the neighbour with the base depth, base_pose and the general
+ * affine inverse of the neighbour's pose (double from the fp32 entries, rounded once); it is in view iff its rounded (rintf, half to
+ * even) coordinates lie inside the image, compared as floats (non-finite = out of view; points behind the camera are not rejected).
+ * In view: fake = grid_sample of the neighbour image (align_corners = False, zero padding, at u / ((W-1)//2) - 1, v / ((H-1)//2) - 1:
+ * the reference's integer division), tgt_depth = the neighbour's depth at the rounded pixel; errors rgb = mean_c |base - fake|, ssim =
+ * 1 - mean_c SSIM of the two full masked images (11 x 11 Gaussian, sigma 1.5, zero padding 5, C1 = 0.01^2, C2 = 0.03^2: L = 1, images
+ * in [0,1]), depth = |dep - tgt_depth| / max(tgt_depth, 1e-10), flagged where > tau, then clamped to tau.  Per pass and mode
+ * (emax - err) / (emax - emin), emax / emin over the pass's in-view pixels (emax == emin: 0 / 0 = NaN, as the reference), is added on
+ * the in-view pixels; the result is sum / max(count, 1), and with the depth bit every mode's map is 0 on the pixels in view and over
+ * tau in the last pass only.  A pass with no pixel in view is skipped entirely (the reference raises) and is not the last pass.
+ * Images smaller than the 11 x 11 window (where the reference shrinks the window) are not the reference's: the window stays 11 x 11,
+ * and for H or W < 3, where (W-1)//2 = 0 leaves the sample point undefined, fake is 0.
+ * images [N,H,W,3] uint8 (images_u8 = 1: decoded as float32(k / 255.0)) or fp32 in [0,1], depths [N,H,W], poses [N,3,4], intrinsics
+ * [N,4] = (cx, cy, fx, fy), all in device memory; neighbours is a HOST array.  modes: bit 0 rgb, 1 ssim, 2 depth; out_* [H,W] fp32,
+ * required iff its bit is set.  ws: >= snerf_reproj_conf_ws(H, W) bytes of device scratch, 4-byte aligned.  No host read, no sync, no
+ * floating-point atomics: bit-reproducible and capturable in a graph.  n_neighbours = 0 writes zeros.  Bad arguments (a null required
+ * pointer, N / H / W < 1, base or a neighbour outside [0,N), n_neighbours < 0 or > 0 with neighbours NULL, modes outside 1..7, an
+ * output missing for a set bit, a short or null workspace, tau not finite) return 1 before any launch. */
+int snerf_reproj_conf(const void* images, int images_u8, const float* depths, const float* poses, const float* intrinsics, int N, int H,
+                      int W, int base, const int* neighbours, int n_neighbours, int modes, float tau, void* ws, long ws_bytes,
+                      float* out_rgb, float* out_ssim, float* out_depth, void* stream);
+/* bytes of scratch snerf_reproj_conf needs for H x W images (0 for H or W < 1) */
+long snerf_reproj_conf_ws(int H, int W);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1598,6 +1598,43 @@ def conf_grad(maps, slot_of_image, lambdas, sky, img, coords, g_conf, grad_lambd
     _lib.call("snerf_conf_grad", *head, _p(g_conf), n, _p(ws), ws.numel(), _p(grad_lambdas), _stream())
 
 
+REPROJ_MODES = ("rgb", "ssim", "depth")                # bit k of snerf_reproj_conf's `modes`
+
+
+def reproj_conf_ws(H, W):
+    """bytes of scratch reproj_conf needs for H x W images (snerf_reproj_conf_ws)"""
+    return int(_lib.query("snerf_reproj_conf_ws", int(H), int(W)))
+
+
+def reproj_conf(images, depths, poses, intrinsics, base, neighbours, modes, tau, out=None, ws=None):
+    """snerf_reproj_conf: the reprojection confidence maps of image `base` against `neighbours` (python ints, in the reference's sel_ids
+    order: the last one decides the depth-mask zeroing) -> fp32 [len(modes), H, W] in the order of `modes` (names out of rgb / ssim /
+    depth).  images [N,H,W,3] uint8 / fp32 in [0,1], depths [N,H,W], poses [N,3,4], intrinsics [N,4] = (cx, cy, fx, fy), all resident
+    (an ImageRayBatcher's tensors as they are).  No host read or sync; graph-capturable when `out` and `ws` (uint8, >= reproj_conf_ws(H, W)
+    elements) are preallocated."""
+    u8 = _u8_or_f32(images)
+    N, H, W = images.shape[:3]
+    for t in (depths, poses, intrinsics):
+        _f32c(t)
+    assert images.dim() == 4 and images.shape[3] == 3 and tuple(depths.shape) == (N, H, W) and tuple(poses.shape) == (N, 3, 4) and \
+        tuple(intrinsics.shape) == (N, 4), "images [N,H,W,3], depths [N,H,W], poses [N,3,4], intrinsics [N,4]"
+    modes = list(modes)
+    assert modes and len(set(modes)) == len(modes) and all(m in REPROJ_MODES for m in modes), f"modes: distinct names out of {REPROJ_MODES}"
+    if out is None:
+        out = torch.empty(len(modes), H, W, dtype=torch.float32, device=images.device)
+    _f32c(out)
+    assert tuple(out.shape) == (len(modes), H, W)
+    need = reproj_conf_ws(H, W)
+    if ws is None:
+        ws = torch.empty(need, dtype=torch.uint8, device=images.device)
+    assert ws.is_cuda and ws.dtype == torch.uint8 and ws.is_contiguous() and ws.numel() >= need
+    planes = [_p(out[modes.index(m)]) if m in modes else None for m in REPROJ_MODES]
+    nb = (ctypes.c_int * max(len(neighbours), 1))(*[int(i) for i in neighbours])
+    _lib.call("snerf_reproj_conf", _p(images), u8, _p(depths), _p(poses), _p(intrinsics), N, H, W, int(base), nb, len(neighbours),
+              sum(1 << REPROJ_MODES.index(m) for m in modes), float(tau), _p(ws), ws.numel(), *planes, _stream())
+    return out
+
+
 def zip_ray_batch(images, depths, semantics, masks, pixtocams, camtoworlds, local2global, near, far, border, patch_size, single_image, seed,
                   counter, n, i0, i1, out):
     """snerf_zip_ray_batch: rows [i0, i1) of step counter[0]'s global batch of n rays into the preallocated `out` (dict: origins,
