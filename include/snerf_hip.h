@@ -435,6 +435,22 @@ int snerf_mip_loss_tail_gconf(const float* rgb, const float* tgt, const float* d
                               const float* depth_keep, long N, int Pf, int Sc, int disparity, float depth_lambda, float coarse_mult,
                               float prop_lambda, float semantic_lambda, float* out, float* g_rgb, float* g_dist1, float* g_dist0,
                               float* g_wc, float* g_sem, float* g_conf, void* stream);
+/* Edge-aware smoothness of P depth patches of p x p pixels (--smooth_loss, s-nerf/train.py:154-177): SmoothLoss
+ * (model/loss_factory.py:39-57) over edge_aware_loss_v2 (model/loss.py:14-34), value and gradient w.r.t. dist in one pass.
+ * rgb [P,p,p,3] (the target colours), dist [P,p,p] (the renderer's distances), sky [P,p,p] (nullable = no sky weighting), fp32:
+ *   disp = 1 / max(dist, 1e-5); u = disp / (patch mean of disp + 1e-7); every pair of horizontal neighbours (a left, b right) gives
+ *   |u_a - u_b| exp(-mean_c |rgb_a - rgb_b|) (1 + sky_a), every vertical pair alike with a on top;
+ *   loss = weight (mean over the P p (p - 1) x-edges + mean over the P p (p - 1) y-edges).
+ * out[3] = {loss, x mean, y mean}; total (nullable device float) += loss; g_dist [P,p,p] = d loss / d dist, ADDED when
+ * accumulate = 1 and stored when 0.  The gradient follows torch's rules: sign(0) = 0 for equal neighbours, no gradient where
+ * dist < 1e-5 (such a pixel still enters its patch mean).  One workgroup per patch, float64 throughout, each result rounded to fp32
+ * once; the patches' sums pass through ws (>= snerf_smooth_loss_ws(P) doubles of device scratch, ws_doubles = its length) and are added
+ * in a fixed order by a second launch: no floating-point atomics, bit-reproducible, graph-safe.  P = 0 is a no-op; bad arguments (a null
+ * rgb / dist / out / g_dist / ws, a short ws, P < 0, p outside 2..32, accumulate outside {0, 1}) return 1 before any launch. */
+int snerf_smooth_loss(const float* rgb, const float* dist, const float* sky, long P, int p, float weight, double* ws, long ws_doubles,
+                      float* out, float* total, float* g_dist, int accumulate, void* stream);
+/* doubles of scratch snerf_smooth_loss needs for P patches */
+long snerf_smooth_loss_ws(long P);
 
 /* zipnerf (path C) ray generation: s-nerfpp/zipnerf/internal/camera_utils.py:453-563 pixels_to_rays, perspective camera, no
  * distortion, no NDC.  pix_x / pix_y int32 [N] integer pixel coordinates, cam_idx int32 [N] (NULL = camera 0) into pixtocams
@@ -463,7 +479,25 @@ int snerf_mip_image_batch(const void* images, int images_u8, const float* depths
                           int n_train, int N, int H, int W, long seed, long* counter, long n, long i0, long i1, float* origins,
                           float* directions, float* viewdirs, float* radii, float* lossmult, float* near_out, float* far_out,
                           float* app_out, float* rgb, float* depth, float* extras_out, long* sel_coords, long* img_out, void* stream);
-/* Path C (s-nerfpp/zipnerf/internal/datasets.py:442-566 Dataset._next_train + _make_ray_batch, patch_size 1; anything else is a
+/* snerf_mip_image_batch followed by the depth patches of --smooth_loss (s-nerf/utils/sample_utils.py:68-89 sample_patches_pt, :102-103,
+ * 136-138: the patches lie BEHIND the random pixels).  With n_patch = 0 (then k0 = k1 = 0) it IS snerf_mip_image_batch: every output
+ * has the same bits.  Otherwise ONE launch writes (i1 - i0) pixel rows followed by (k1 - k0) patch_sz^2 patch rows, patches [k0, k1) of
+ * the step's n_patch (a rank's whole patches); every output has (i1 - i0) + (k1 - k0) patch_sz^2 rows, extras_out that row stride.  The
+ * image of the step and the pixel rows are those of snerf_mip_image_batch for the same seed and step: patches do not move the random
+ * pixels.  Centre k of step s is drawn WITH replacement (np.random.randint there) over the (H - 2p - 1)(W - 2p - 1) pixels strictly
+ * more than p = patch_sz from every border: the bounded draw of snerf_zip_ray_batch with (i, v) = (k, 3), idx -> row p + 1 + idx / wc,
+ * column p + 1 + idx % wc, wc = W - 2p - 1 (csrc/callers.hip).  The patch's pixels are [c - p/2, c + p/2) in both axes, rows outer,
+ * patches in order k; every field of a patch row is computed as for a pixel row.  One counter advance per launch; graph-safe.
+ * n_patch = 0 with n = 0 is a no-op.  Bad arguments (those of snerf_mip_image_batch; n_patch < 0; 0 <= k0 <= k1 <= n_patch not
+ * holding; with n_patch > 0: patch_sz odd, below 2 or above 32, fewer than 1 or 2^32 and more interior pixels) return 1 before any
+ * launch. */
+int snerf_mip_image_patch_batch(const void* images, int images_u8, const float* depths, const float* poses, const float* intrinsics,
+                                const float* near, const float* far, const float* app, const float* extras, int n_extra,
+                                const int* i_train, int n_train, int N, int H, int W, long seed, long* counter, long n, long i0, long i1,
+                                float* origins, float* directions, float* viewdirs, float* radii, float* lossmult, float* near_out,
+                                float* far_out, float* app_out, float* rgb, float* depth, float* extras_out, long* sel_coords,
+                                long* img_out, int n_patch, int patch_sz, int k0, int k1, void* stream);
+/* Path C(s-nerfpp/zipnerf/internal/datasets.py:442-566 Dataset._next_train + _make_ray_batch, patch_size 1; anything else is a
  * bad argument): per ray a camera in [0, N) and x in [border, W - border), y in [border, H - border), uniform WITH replacement like
  * np.random.randint (single_image = 1: one camera per step, batching 'single_image').  images [N,H,W,3] fp32 or uint8, depths
  * [N,H,W] fp32, semantics int32 [N,H,W], masks fp32 [N,H,W] (each nullable with its output), pixtocams [N,3,3], camtoworlds

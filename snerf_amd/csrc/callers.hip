@@ -602,6 +602,122 @@ extern "C" int snerf_mip_loss_tail_masked(const float* rgb, const float* tgt, co
 }
 
 // ---------------------------------------------------------------------------
+// Edge-aware smoothness of depth patches (--smooth_loss; s-nerf/train.py:154-177): SmoothLoss (model/loss_factory.py:39-57) over
+// edge_aware_loss_v2 (model/loss.py:14-34), value and gradient w.r.t. the distances in one pass.  Per patch of p x p pixels:
+//   disp = 1 / max(dist, 1e-5), u = disp / (mean(disp) + 1e-7),
+//   x-edge (a = left, b = right neighbour): |u_a - u_b| exp(-mean_c |rgb_a - rgb_b|) (1 + sky_a); y-edges alike with a = top;
+//   loss = weight (sum over x-edges / (P p (p - 1)) + the same for the y-edges).
+// One workgroup per patch, one lane per pixel (p^2 lanes rounded up to whole waves; p = 8 is one wave).  Everything is float64: the
+// fp32 inputs convert exactly and every output is rounded to fp32 once.  u goes through LDS to the neighbours; each lane owns the edge
+// to its right and the edge below it and leaves their signed weights in LDS, from which every lane collects q = d (edge sums) / d u
+// of its pixel.  With M = mean + 1e-7 and S = sum_i q_i disp_i:  d / d disp_j = q_j / M - S / (M^2 p^2), times -1 / dist^2 where
+// dist >= 1e-5 (torch's clamp passes no gradient below its bound; such a pixel still enters the mean), sign(0) = 0.  The gradient of a
+// patch needs only that patch, so it leaves in this launch; the patch's two edge sums go to ws and a one-wave finish launch adds them
+// in a fixed order: no floating-point atomics, two calls give the same bits.
+// ---------------------------------------------------------------------------
+struct SmoothArgs {
+  const float *rgb, *dist, *sky;    // [P,p,p,3], [P,p,p], [P,p,p] nullable
+  long P; int p;
+  double weight;
+  double* ws;                       // [P,2] = each patch's {x-edge sum, y-edge sum}
+  float *out, *total, *g_dist;
+  int accumulate;
+};
+
+// sum over the workgroup, the same bits in every lane: xor butterfly inside the waves, then the waves' values in wave order
+__device__ __forceinline__ double smooth_block_sum(double v, double* s_part) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  __syncthreads();                                   // (the previous sum's readers are done with s_part)
+  if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = v;
+  __syncthreads();
+  double s = 0.0;
+  for (int w = 0; w < (int)(blockDim.x >> 6); ++w) s += s_part[w];
+  return s;
+}
+
+__global__ __launch_bounds__(1024) void smooth_loss_kernel(SmoothArgs a) {
+  __shared__ double s_u[1024], s_gx[1024], s_gy[1024], s_part[16];
+  const int p = a.p, pp = p * p, t = (int)threadIdx.x;
+  const bool live = t < pp;
+  const long base = (long)blockIdx.x * pp;
+  const int y = t / p, x = t - y * p;
+  const float df = live ? a.dist[base + t] : 1.f;
+  const bool clamped = df < 1e-5f;                   // (a NaN distance is not clamped, as in torch)
+  const double d = clamped ? (double)1e-5f : (double)df;
+  const double disp = live ? 1.0 / d : 0.0;
+  const double M = smooth_block_sum(disp, s_part) / (double)pp + 1e-7;
+  const double u = disp / M;
+  s_u[t] = u;
+  __syncthreads();
+  double ex = 0.0, ey = 0.0, gx = 0.0, gy = 0.0;     // this lane's two edges: value, and signed weight = d value / d u of this pixel
+  if (live) {
+    const float* c0 = a.rgb + 3 * (base + t);
+    const double k = a.sky != nullptr ? 1.0 + (double)a.sky[base + t] : 1.0;
+    if (x + 1 < p) {
+      const float* c1 = c0 + 3;
+      const double w = exp(-((fabs((double)c0[0] - (double)c1[0]) + fabs((double)c0[1] - (double)c1[1])) + fabs((double)c0[2] - (double)c1[2])) / 3.0) * k;
+      const double du = u - s_u[t + 1];
+      ex = fabs(du) * w;
+      gx = du > 0.0 ? w : (du < 0.0 ? -w : 0.0);
+    }
+    if (y + 1 < p) {
+      const float* c1 = c0 + 3 * p;
+      const double w = exp(-((fabs((double)c0[0] - (double)c1[0]) + fabs((double)c0[1] - (double)c1[1])) + fabs((double)c0[2] - (double)c1[2])) / 3.0) * k;
+      const double du = u - s_u[t + p];
+      ey = fabs(du) * w;
+      gy = du > 0.0 ? w : (du < 0.0 ? -w : 0.0);
+    }
+  }
+  s_gx[t] = gx;
+  s_gy[t] = gy;
+  __syncthreads();
+  double q = 0.0;
+  if (live) {
+    q = gx + gy;
+    if (x > 0) q -= s_gx[t - 1];
+    if (y > 0) q -= s_gy[t - p];
+  }
+  const double S = smooth_block_sum(q * disp, s_part);
+  const double sx = smooth_block_sum(ex, s_part), sy = smooth_block_sum(ey, s_part);
+  if (t == 0) { a.ws[2 * blockIdx.x] = sx; a.ws[2 * blockIdx.x + 1] = sy; }
+  if (live) {
+    const double scale = a.weight / ((double)a.P * p * (p - 1));
+    const double g_disp = (q / M - S / (M * M * (double)pp)) * scale;
+    const float g = clamped ? 0.f : (float)(g_disp * (-1.0 / (d * d)));
+    a.g_dist[base + t] = a.accumulate ? a.g_dist[base + t] + g : g;
+  }
+}
+
+__global__ __launch_bounds__(64) void smooth_loss_finish_kernel(SmoothArgs a) {
+  double sx = 0.0, sy = 0.0;
+  for (long k = threadIdx.x; k < a.P; k += 64) { sx += a.ws[2 * k]; sy += a.ws[2 * k + 1]; }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) { sx += __shfl_xor(sx, o, 64); sy += __shfl_xor(sy, o, 64); }
+  if (threadIdx.x == 0) {
+    const double edges = (double)a.P * a.p * (a.p - 1);
+    const float loss = (float)(a.weight * (sx / edges + sy / edges));
+    a.out[0] = loss;
+    a.out[1] = (float)(sx / edges);
+    a.out[2] = (float)(sy / edges);
+    if (a.total != nullptr) *a.total = *a.total + loss;
+  }
+}
+
+extern "C" long snerf_smooth_loss_ws(long P) { return P <= 0 ? 0 : 2 * P; }
+
+extern "C" int snerf_smooth_loss(const float* rgb, const float* dist, const float* sky, long P, int p, float weight, double* ws, long ws_doubles,
+                                 float* out, float* total, float* g_dist, int accumulate, void* stream) {
+  if (P == 0) return SNERF_OK;
+  if (P < 0 || P > 0x7FFFFFFFL || p < 2 || p > 32 || (accumulate != 0 && accumulate != 1)) return SNERF_ERR_ARG;
+  if (rgb == nullptr || dist == nullptr || out == nullptr || g_dist == nullptr || ws == nullptr || ws_doubles < 2 * P) return SNERF_ERR_ARG;
+  SmoothArgs a{rgb, dist, sky, P, p, (double)weight, ws, out, total, g_dist, accumulate};
+  hipLaunchKernelGGL(smooth_loss_kernel, dim3((unsigned)P), dim3((unsigned)((p * p + 63) / 64 * 64)), 0, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(smooth_loss_finish_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, a);
+  return snerf_check_launch();
+}
+
+// ---------------------------------------------------------------------------
 // zipnerf (path C) ray generation: s-nerfpp/zipnerf/internal/camera_utils.py:453-563 (pixels_to_rays), perspective camera, no
 // distortion, no NDC.  numpy promotes to float64 there (integer pixels + .5); the dataset casts the result to fp32.  One lane
 // per ray, float64 arithmetic, one rounding per emitted value.
@@ -693,6 +809,7 @@ extern "C" int snerf_zip_pixels_to_rays(const int* pix_x, const int* pix_y, cons
 //   a = 0, 1, ...: u = philox(i, 3 << 16 | v << 8 | a, lo32(s), hi32(s)), m = u * range (64 bits); accepted when lo32(m) >=
 //   2^32 mod range (Lemire's unbiased bounded integers); value = lo + hi32(m).  Attempt 255 is accepted as it is (a rejection has
 //   probability range / 2^32).  batching 'single_image': every ray takes the camera of ray 0.
+//   snerf_mip_image_patch_batch, step s, patch k: the same bounded draw with (i, v) = (k, 3) over the patch-centre window (below).
 // A ray's draws depend on (seed, step, i) only: not on the rank slice [i0, i1) a launch writes, nor on the launch geometry.
 // Step counter ctr[2] (int64, device): ctr[0] = step.  Every workgroup reads it and takes a ticket (ctr[1]); the last one stores
 // step + 1 and resets the ticket: a replayed graph launch draws a new batch every time.
@@ -769,18 +886,33 @@ struct MipBatch {
   long n, i0, i1;
   float *origins, *directions, *viewdirs, *radii, *lossmult, *near_out, *far_out, *app_out, *rgb, *depth, *extras_out;
   long *sel_coords, *img_out;
+  int patch_sz, pk0, pk1;                         // snerf_mip_image_patch_batch: patches [pk0, pk1) of patch_sz^2 pixels behind the pixel rows
 };
 
+// Patch rows (snerf_mip_image_patch_batch; sample_utils.py:68-89 sample_patches_pt): centre k of step s = bounded_draw(k, 3, s, hr wc)
+// over the hr x wc = (H - 2p - 1)(W - 2p - 1) pixels strictly more than p = patch_sz from every border, row-major: WITH replacement,
+// like np.random.randint; its p^2 pixels are [c - p/2, c + p/2) in both axes, rows outer.
 __global__ __launch_bounds__(256) void mip_image_batch_kernel(MipBatch a) {
   const long s = batch_step(a.ctr);
   const long e = s / a.n_train, pos = s - e * a.n_train;
   const int img = a.i_train[keyed_perm((unsigned long long)pos, (unsigned long long)a.n_train, 1u, e, a.k0, a.k1)];
   if (blockIdx.x == 0 && threadIdx.x == 0) a.img_out[0] = img;
-  const long i = a.i0 + (long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= a.i1) return;
-  const long r = i - a.i0, HW = (long)a.H * a.W;
-  const long q = (long)keyed_perm((unsigned long long)i, (unsigned long long)HW, 2u, s, a.k0, a.k1);
-  const int row = (int)(q / a.W), col = (int)(q - (long)row * a.W);
+  const long r = (long)blockIdx.x * 256 + threadIdx.x;
+  const long npix = a.i1 - a.i0, pp = (long)a.patch_sz * a.patch_sz, nl = npix + (long)(a.pk1 - a.pk0) * pp;
+  if (r >= nl) return;
+  const long HW = (long)a.H * a.W;
+  int row, col;
+  if (r < npix) {
+    const long q = (long)keyed_perm((unsigned long long)(a.i0 + r), (unsigned long long)HW, 2u, s, a.k0, a.k1);
+    row = (int)(q / a.W); col = (int)(q - (long)row * a.W);
+  } else {
+    const long j = r - npix, k = a.pk0 + j / pp;
+    const int t = (int)(j - (k - a.pk0) * pp), p = a.patch_sz, wc = a.W - 2 * p - 1;
+    const unsigned idx = (unsigned)bounded_draw((unsigned)k, 3u, s, (unsigned)(a.H - 2 * p - 1) * (unsigned)wc, a.k0, a.k1);
+    row = p + 1 + (int)(idx / (unsigned)wc) - p / 2 + t / p;
+    col = p + 1 + (int)(idx % (unsigned)wc) - p / 2 + t % p;
+  }
+  const long q = (long)row * a.W + col;
   const float* p = a.poses + 12 * (long)img;
   const float* k = a.intr + 4 * (long)img;
   float d[3], v[3], rad;
@@ -799,10 +931,53 @@ __global__ __launch_bounds__(256) void mip_image_batch_kernel(MipBatch a) {
   a.far_out[r] = a.far[img];
   a.app_out[r] = a.app[img];
   if (a.depth != nullptr) a.depth[r] = a.depths[pix];
-  const long nl = a.i1 - a.i0;
   for (int x = 0; x < a.n_extra; ++x) a.extras_out[x * nl + r] = a.extras[(long)x * a.N * HW + pix];
   a.sel_coords[2 * r] = row;
   a.sel_coords[2 * r + 1] = col;
+}
+
+// checks shared by the two path A entries; n == 0 is handled by the callers
+static int mip_batch_bad(const void* images, int images_u8, const float* depths, const float* poses, const float* intrinsics, const float* near,
+                         const float* far, const float* app, const float* extras, int n_extra, const int* i_train, int n_train, int N, int H,
+                         int W, const long* counter, long n, long i0, long i1, const float* origins, const float* directions,
+                         const float* viewdirs, const float* radii, const float* lossmult, const float* near_out, const float* far_out,
+                         const float* app_out, const float* rgb, const float* depth, const float* extras_out, const long* sel_coords,
+                         const long* img_out) {
+  if (n < 0 || N < 1 || n_train < 1 || H < 3 || W < 1 || n > (long)H * W || i0 < 0 || i1 < i0 || i1 > n || n_extra < 0) return 1;
+  if (images == nullptr || poses == nullptr || intrinsics == nullptr || near == nullptr || far == nullptr || app == nullptr ||
+      i_train == nullptr || counter == nullptr || img_out == nullptr || (images_u8 != 0 && images_u8 != 1))
+    return 1;
+  if (origins == nullptr || directions == nullptr || viewdirs == nullptr || radii == nullptr || lossmult == nullptr || near_out == nullptr ||
+      far_out == nullptr || app_out == nullptr || rgb == nullptr || sel_coords == nullptr)
+    return 1;
+  if ((depth != nullptr && depths == nullptr) || (n_extra > 0 && (extras == nullptr || extras_out == nullptr))) return 1;
+  return 0;
+}
+
+extern "C" int snerf_mip_image_patch_batch(const void* images, int images_u8, const float* depths, const float* poses, const float* intrinsics,
+                                           const float* near, const float* far, const float* app, const float* extras, int n_extra,
+                                           const int* i_train, int n_train, int N, int H, int W, long seed, long* counter, long n, long i0,
+                                           long i1, float* origins, float* directions, float* viewdirs, float* radii, float* lossmult,
+                                           float* near_out, float* far_out, float* app_out, float* rgb, float* depth, float* extras_out,
+                                           long* sel_coords, long* img_out, int n_patch, int patch_sz, int k0, int k1, void* stream) {
+  if (n_patch < 0 || k0 < 0 || k1 < k0 || k1 > n_patch) return SNERF_ERR_ARG;
+  if (n_patch == 0) {
+    if (n == 0) return SNERF_OK;
+    patch_sz = 0;
+  } else {
+    if (patch_sz < 2 || patch_sz > 32 || (patch_sz & 1) != 0) return SNERF_ERR_ARG;
+    const long hr = (long)H - 2L * patch_sz - 1, wc = (long)W - 2L * patch_sz - 1;
+    if (hr < 1 || wc < 1 || hr * wc > 0xFFFFFFFFL) return SNERF_ERR_ARG;
+  }
+  if (mip_batch_bad(images, images_u8, depths, poses, intrinsics, near, far, app, extras, n_extra, i_train, n_train, N, H, W, counter, n, i0, i1,
+                    origins, directions, viewdirs, radii, lossmult, near_out, far_out, app_out, rgb, depth, extras_out, sel_coords, img_out))
+    return SNERF_ERR_ARG;
+  MipBatch a{images, images_u8, depths, poses, intrinsics, near, far, app, extras, n_extra, i_train, n_train, N, H, W,
+             (unsigned)(unsigned long)seed, (unsigned)((unsigned long)seed >> 32), counter, n, i0, i1, origins, directions, viewdirs, radii,
+             lossmult, near_out, far_out, app_out, rgb, depth, extras_out, sel_coords, img_out, patch_sz, k0, k1};
+  const long nl = (i1 - i0) + (long)(k1 - k0) * patch_sz * patch_sz;
+  hipLaunchKernelGGL(mip_image_batch_kernel, dim3((unsigned)(nl > 0 ? (nl + 255) / 256 : 1)), dim3(256), 0, (hipStream_t)stream, a);
+  return snerf_check_launch();
 }
 
 extern "C" int snerf_mip_image_batch(const void* images, int images_u8, const float* depths, const float* poses, const float* intrinsics,
@@ -810,21 +985,9 @@ extern "C" int snerf_mip_image_batch(const void* images, int images_u8, const fl
                                      int n_train, int N, int H, int W, long seed, long* counter, long n, long i0, long i1, float* origins,
                                      float* directions, float* viewdirs, float* radii, float* lossmult, float* near_out, float* far_out,
                                      float* app_out, float* rgb, float* depth, float* extras_out, long* sel_coords, long* img_out, void* stream) {
-  if (n == 0) return SNERF_OK;
-  if (n < 0 || N < 1 || n_train < 1 || H < 3 || W < 1 || n > (long)H * W || i0 < 0 || i1 < i0 || i1 > n || n_extra < 0) return SNERF_ERR_ARG;
-  if (images == nullptr || poses == nullptr || intrinsics == nullptr || near == nullptr || far == nullptr || app == nullptr ||
-      i_train == nullptr || counter == nullptr || img_out == nullptr || (images_u8 != 0 && images_u8 != 1))
-    return SNERF_ERR_ARG;
-  if (origins == nullptr || directions == nullptr || viewdirs == nullptr || radii == nullptr || lossmult == nullptr || near_out == nullptr ||
-      far_out == nullptr || app_out == nullptr || rgb == nullptr || sel_coords == nullptr)
-    return SNERF_ERR_ARG;
-  if ((depth != nullptr && depths == nullptr) || (n_extra > 0 && (extras == nullptr || extras_out == nullptr))) return SNERF_ERR_ARG;
-  MipBatch a{images, images_u8, depths, poses, intrinsics, near, far, app, extras, n_extra, i_train, n_train, N, H, W,
-             (unsigned)(unsigned long)seed, (unsigned)((unsigned long)seed >> 32), counter, n, i0, i1, origins, directions, viewdirs, radii,
-             lossmult, near_out, far_out, app_out, rgb, depth, extras_out, sel_coords, img_out};
-  const long nl = i1 - i0;
-  hipLaunchKernelGGL(mip_image_batch_kernel, dim3((unsigned)(nl > 0 ? (nl + 255) / 256 : 1)), dim3(256), 0, (hipStream_t)stream, a);
-  return snerf_check_launch();
+  return snerf_mip_image_patch_batch(images, images_u8, depths, poses, intrinsics, near, far, app, extras, n_extra, i_train, n_train, N, H, W, seed,
+                                     counter, n, i0, i1, origins, directions, viewdirs, radii, lossmult, near_out, far_out, app_out, rgb, depth,
+                                     extras_out, sel_coords, img_out, 0, 0, 0, 0, stream);
 }
 
 struct ZipBatch {

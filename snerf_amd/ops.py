@@ -1503,6 +1503,58 @@ def mip_image_batch(images, depths, poses, intrinsics, near, far, app, extras, i
     return out
 
 
+def mip_image_patch_batch(images, depths, poses, intrinsics, near, far, app, extras, i_train, seed, counter, n, i0, i1, n_patch, patch_sz, k0,
+                          k1, out):
+    """snerf_mip_image_patch_batch: mip_image_batch's rows [i0, i1) followed by patches [k0, k1) of the step's n_patch depth patches of
+    patch_sz^2 pixels (--smooth_loss) into `out` (as for mip_image_batch, with m = (i1 - i0) + (k1 - k0) patch_sz^2 rows); one launch,
+    advances counter[0].  n_patch = 0 is mip_image_batch."""
+    u8 = _u8_or_f32(images)
+    N, H, W = images.shape[:3]
+    for t in (depths, poses, intrinsics, near, far, app, extras):
+        _f32c(t)
+    assert i_train.dtype == torch.int32 and i_train.is_contiguous() and counter.dtype == torch.int64 and counter.numel() == 2
+    m = (int(i1) - int(i0)) + (int(k1) - int(k0)) * int(patch_sz) ** 2
+    assert out["rgb"].shape[0] == m and out["sel_coords"].shape[0] == m and (out.get("extras") is None or out["extras"].shape[1] == m), \
+        "out: (i1 - i0) + (k1 - k0) patch_sz^2 rows"
+    k = 0 if extras is None else extras.shape[0]
+    _lib.call("snerf_mip_image_patch_batch", _p(images), u8, _p(depths), _p(poses), _p(intrinsics), _p(near), _p(far), _p(app), _p(extras), k,
+              _p(i_train), i_train.numel(), N, H, W, int(seed), _p(counter), int(n), int(i0), int(i1), _p(out["origins"]),
+              _p(out["directions"]), _p(out["viewdirs"]), _p(out["radii"]), _p(out["lossmult"]), _p(out["near"]), _p(out["far"]),
+              _p(out["app"]), _p(out["rgb"]), _p(out.get("depth")), _p(out.get("extras")), _p(out["sel_coords"]), _p(out["img"]),
+              int(n_patch), int(patch_sz), int(k0), int(k1), _stream())
+    return out
+
+
+def smooth_loss_ws(P):
+    """doubles of scratch smooth_loss needs for P patches (snerf_smooth_loss_ws)"""
+    return int(_lib.query("snerf_smooth_loss_ws", int(P)))
+
+
+def smooth_loss(rgb, dist, sky, P, p, weight, out=None, total=None, g_dist=None, accumulate=False, ws=None):
+    """snerf_smooth_loss: the edge-aware smoothness (SmoothLoss over edge_aware_loss_v2) of P patches of p x p rays, value and gradient in
+    one pass.  rgb [P p p, 3] target colours, dist [P p p] renderer distances, sky [P p p] or None (fp32, any shape of that size) ->
+    (out[3] = {weight * (x mean + y mean), x mean, y mean}, g_dist [P p p] = d loss / d dist).  total: a device float the loss is
+    added into; g_dist given: stored into (accumulate=False) or added into (True).  Deterministic (float64 sums in a fixed order, no
+    atomics).  ws: fp64 scratch of >= smooth_loss_ws(P) elements (allocated when None).  P = 0 launches nothing."""
+    P, p = int(P), int(p)
+    dev = dist.device
+    for t in (rgb, dist, sky, total, g_dist, out):
+        _f32c(t)
+    assert rgb.numel() == 3 * P * p * p and dist.numel() == P * p * p and (sky is None or sky.numel() == P * p * p), "rgb [P,p,p,3], dist / sky [P,p,p]"
+    if out is None:
+        out = torch.zeros(3, dtype=torch.float32, device=dev)
+    if g_dist is None:
+        assert not accumulate, "accumulate=True adds into a given g_dist"
+        g_dist = torch.empty(P * p * p, dtype=torch.float32, device=dev)
+    assert out.numel() == 3 and g_dist.numel() == P * p * p and (total is None or total.numel() == 1)
+    if ws is None:
+        ws = torch.empty(max(smooth_loss_ws(P), 1), dtype=torch.float64, device=dev)
+    assert ws.is_cuda and ws.dtype == torch.float64 and ws.is_contiguous()
+    _lib.call("snerf_smooth_loss", _p(rgb), _p(dist), _p(sky), P, p, float(weight), _p(ws), ws.numel(), _p(out), _p(total), _p(g_dist),
+              int(bool(accumulate)), _stream())
+    return out, g_dist
+
+
 def _cam_args(cam):
     """camera index of the pose entries -> (device pointer or None, host index): an int64 [1] device tensor (a batcher's `img`) is read
     by the kernel, anything else is a python int"""

@@ -57,12 +57,7 @@ def sample_patches(H, W, patch_sz, n_patch):
     if hr <= 0 or wc <= 0:
         raise ValueError("image smaller than the smooth-loss patch margin (the reference's np.random.randint(0) raises here too)")
     idx = np.random.randint(hr * wc, size=n_patch)
-    cr, cc = patch_sz + 1 + idx // wc, patch_sz + 1 + idx % wc
-    h = patch_sz // 2
-    dr, dc = np.meshgrid(np.arange(-h, h), np.arange(-h, h), indexing="ij")
-    rows = (cr[:, None, None] + dr[None]).reshape(-1)
-    cols = (cc[:, None, None] + dc[None]).reshape(-1)
-    return np.stack([rows, cols], -1).astype(np.int64)
+    return patch_pixels(np.stack([patch_sz + 1 + idx // wc, patch_sz + 1 + idx % wc], -1), patch_sz)
 
 
 def smooth_loss(image, skymask, sel_coords_smooth, pred_distance_smooth, n_patch, patch_sz, weight, use_skymask=True):
@@ -161,6 +156,44 @@ def image_of_step(i_train, seed, s):
     return int(i_train[keyed_perm(p, nt, 1, e, int(seed))])
 
 
+def bounded_draw(i, v, s, rng, seed):
+    """Lemire's unbiased integer in [0, rng) the batchers draw with: attempts a = 0, 1, ... on the counter (i, 3 << 16 | v << 8 | a,
+    lo32(s), hi32(s)), attempt 255 accepted as it is (csrc/callers.hip)."""
+    thresh = ((1 << 32) - rng) % rng
+    s &= (1 << 64) - 1
+    for a in range(256):
+        m = philox((i, 3 << 16 | v << 8 | a, s & _M32, s >> 32), seed) * rng
+        if (m & _M32) >= thresh:
+            break
+    return m >> 32
+
+
+def _patch_window(H, W, patch_sz):
+    """rows / columns of sample_patches' centre window: the pixels r with patch_sz < r < H - patch_sz (and the same in W)"""
+    return H - 2 * patch_sz - 1, W - 2 * patch_sz - 1
+
+
+def patch_centres_of_step(s, seed, H, W, patch_sz, n_patch):
+    """PatchRayBatcher's patch schedule: centre k of step s = bounded_draw(k, 3, s, hr wc) over the hr x wc pixels of sample_patches'
+    window in row-major order (with replacement, like np.random.randint there) -> int64 [n_patch, 2] of (row, col)."""
+    hr, wc = _patch_window(int(H), int(W), int(patch_sz))
+    if hr <= 0 or wc <= 0:
+        raise ValueError("image smaller than the smooth-loss patch margin")
+    idx = np.asarray([bounded_draw(k, 3, int(s), hr * wc, int(seed)) for k in range(int(n_patch))], dtype=np.int64).reshape(-1)
+    return np.stack([patch_sz + 1 + idx // wc, patch_sz + 1 + idx % wc], -1).astype(np.int64)
+
+
+def patch_pixels(centres, patch_sz):
+    """the pixels of the patches around `centres` [k, 2]: [c - patch_sz // 2, c + patch_sz // 2) in both axes, rows outer, patches in order
+    (the layout half of sample_patches) -> int64 [k (2 (patch_sz // 2))^2, 2] of (row, col)."""
+    c = np.asarray(centres, dtype=np.int64).reshape(-1, 2)
+    h = patch_sz // 2
+    dr, dc = np.meshgrid(np.arange(-h, h), np.arange(-h, h), indexing="ij")
+    rows = (c[:, 0, None, None] + dr[None]).reshape(-1)
+    cols = (c[:, 1, None, None] + dc[None]).reshape(-1)
+    return np.stack([rows, cols], -1).astype(np.int64)
+
+
 def _stack(x, dtype=None):
     if torch.is_tensor(x):
         return x.detach()
@@ -184,11 +217,13 @@ class ImageRayBatcher:
     a single-GPU run.  images: [N,H,W,3] uint8 (decoded to float32(k / 255.0)) or float; extras: per-pixel fp32 maps [N,H,W]
     (confidence maps, sky masks) gathered with the targets."""
 
+    draws_patches = False                            # (PatchRayBatcher: the --smooth_loss patches behind the random pixels)
+
     def __init__(self, args, images, depth_gts, poses, intrinsics, i_train, near, far, camera_index=None, batch_n=None, extras=None, seed=0,
                  rank=0, world=1, device=None):
         _check(args)
-        if getattr(args, "smooth_loss", False):
-            raise NotImplementedError("smooth_loss: the patches of sample_patches are not drawn by the device batcher")
+        if getattr(args, "smooth_loss", False) and not self.draws_patches:
+            raise NotImplementedError("smooth_loss: ImageRayBatcher draws no patches; PatchRayBatcher does")
         if not 0 <= int(seed) < (1 << 63):
             raise ValueError("seed must be in [0, 2^63)")
         device = torch.device(device if device is not None else "cuda")
@@ -265,9 +300,14 @@ class ImageRayBatcher:
         """tell the host mirror that k draws ran inside graph replays"""
         self._step += int(k)
 
+    @property
+    def n_rows(self):
+        """rows of this rank's batch"""
+        return self.i1 - self.i0
+
     def buffers(self):
         """fresh output tensors of one batch (this rank's rows)"""
-        m, dev = self.i1 - self.i0, self.device
+        m, dev = self.n_rows, self.device
         e = lambda *s, dt=torch.float32: torch.empty(*s, dtype=dt, device=dev)
         return dict(origins=e(m, 3), directions=e(m, 3), viewdirs=e(m, 3), radii=e(m, 1), lossmult=e(m, 1), near=e(m, 1), far=e(m, 1),
                     app=e(m, 1), rgb=e(m, 3), depth=e(m), extras=None if self.extras is None else e(self.extras.shape[0], m),
@@ -290,3 +330,62 @@ class ImageRayBatcher:
         rays = Rays(buf["origins"], buf["directions"], buf["viewdirs"], buf["radii"], buf["lossmult"], buf["near"], buf["far"], buf["app"])
         ex = [] if buf["extras"] is None else list(buf["extras"].unbind(0))
         return rays, buf["rgb"], buf["depth"], buf["sel_coords"], buf["img"], ex
+
+
+class PatchRayBatcher(ImageRayBatcher):
+    """ImageRayBatcher for --smooth_loss configs (sample_utils.py:102-103,136-138): every batch is the batch_n random pixels of the
+    step's image followed by n_patch patches of patch_sz x patch_sz pixels of the same image, drawn, cast and gathered by the same ONE
+    launch (`snerf_mip_image_patch_batch`).  The image and the random pixels are those an ImageRayBatcher of the same seed draws at the
+    same step; the patch centres are `patch_centres_of_step(step, seed, H, W, patch_sz, n_patch)` -- with replacement over the pixels
+    strictly more than patch_sz from every border, the window of `sample_patches` -- and their pixels `patch_pixels(centres, patch_sz)`.
+    Every field of a patch row (rays, rgb, depth, extras, sel_coords, bounds, app) is what a pixel row of that pixel holds.
+
+    Rank r of `world` takes pixel rows shard_bounds(batch_n, r, world) and WHOLE patches shard_bounds(n_patch, r, world) (a rank may
+    get none): `n_rgb_rows` pixel rows in front of `n_patch_rows` patch rows.  MipTrainer.step(..., n_rgb=batcher.n_rgb_rows) trains on
+    it; the ranks' pixel rows and patches together are those of a single-GPU run."""
+    draws_patches = True
+
+    def __init__(self, args, images, depth_gts, poses, intrinsics, i_train, near, far, camera_index=None, batch_n=None, extras=None, seed=0,
+                 rank=0, world=1, device=None, n_patch=None, patch_sz=None):
+        n_patch = int(n_patch if n_patch is not None else args.N_patch)
+        p = int(patch_sz if patch_sz is not None else args.patch_sz)
+        if n_patch < 1:
+            raise ValueError(f"n_patch = {n_patch}: a PatchRayBatcher draws at least one patch (ImageRayBatcher draws none)")
+        if p < 2 or p > 32 or p % 2:
+            raise ValueError(f"patch_sz = {p}: an even size in 2..32 (the patch is [c - patch_sz // 2, c + patch_sz // 2) around its centre)")
+        shape = _stack(images).shape
+        if len(shape) == 4:
+            hr, wc = _patch_window(int(shape[1]), int(shape[2]), p)
+            if hr < 1 or wc < 1 or hr * wc >= 1 << 32:
+                raise ValueError(f"images of {int(shape[1])} x {int(shape[2])} leave no pixel more than patch_sz = {p} from every border "
+                                 "(or 2^32 and more of them)")
+        super().__init__(args, images, depth_gts, poses, intrinsics, i_train, near, far, camera_index=camera_index, batch_n=batch_n,
+                         extras=extras, seed=seed, rank=rank, world=world, device=device)
+        from .trainer import shard_bounds
+        self.n_patch, self.patch_sz = n_patch, p
+        self.k0, self.k1 = shard_bounds(n_patch, self.rank, self.world)
+
+    @property
+    def n_rgb_rows(self):
+        """this rank's pixel rows: the rows in front of its patch rows (MipTrainer.step's n_rgb)"""
+        return self.i1 - self.i0
+
+    @property
+    def n_patch_rows(self):
+        """this rank's patch rows: its whole patches times patch_sz^2"""
+        return (self.k1 - self.k0) * self.patch_sz ** 2
+
+    @property
+    def n_rows(self):
+        return self.n_rgb_rows + self.n_patch_rows
+
+    def patch_centres_of_step(self, s):
+        """the n_patch centres of step s, int64 [n_patch, 2] -- on the host, no sync (this rank's are rows [k0, k1))"""
+        return patch_centres_of_step(s, self.seed, self.H, self.W, self.patch_sz, self.n_patch)
+
+    def next_into(self, buf):
+        ops.mip_image_patch_batch(self.images, self.depths, self.poses, self.intrinsics, self.near, self.far, self.app, self.extras,
+                                  self.i_train, self.seed, self.counter, self.batch_n, self.i0, self.i1, self.n_patch, self.patch_sz,
+                                  self.k0, self.k1, buf)
+        self._step += 1
+        return self.view(buf)

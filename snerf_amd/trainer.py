@@ -345,12 +345,14 @@ class MipLossRules:
 
 class MipTrainer(_AdamState):
     rules = None                                     # (class default: loss_and_grads also serves trainers assembled without __init__)
+    smooth_patch_sz = None
 
     def __init__(self, model, lr=5e-4, betas=(0.9, 0.999), eps=1e-8, depth_lambda=0.2, coarse_depth_mult=0.2,
                  proposal_loss=False, proposal_lambda=0.05, disparity_depth=True, process_group=None,
                  nonfinite="zero", grad_max_val=0.0, grad_max_norm=0.0, exchange_when_single=False,
                  pose_net=None, pose_lr=1e-4, pose_betas=(0.9, 0.999), pose_eps=1e-8, semantic_lambda=0.1, loss_rules=None,
-                 conf_net=None, conf_maps=None, conf_lr=1e-3, conf_betas=(0.9, 0.999), conf_eps=1e-8):
+                 conf_net=None, conf_maps=None, conf_lr=1e-3, conf_betas=(0.9, 0.999), conf_eps=1e-8,
+                 smooth_patch_sz=None, smooth_lambda=0.1, smooth_skymask=True):
         """`nonfinite` / `grad_max_val` / `grad_max_norm`: gradient hygiene folded into the Adam launch (ops.adam_step).  The s-nerf
         reference has none (train.py:212-215 drops into pdb on a failing backward); the default "zero" keeps one NaN / Inf gradient
         (1/(depth + eps), a bf16 overflow) from poisoning m, v and the parameters of the whole arena on every rank.  "keep" = plain Adam.
@@ -363,7 +365,10 @@ class MipTrainer(_AdamState):
         `conf_net` + `conf_maps` (confidence.Confidence / ConfidenceMaps; configs: depth_conf = True, precompute_conf = True): the
         per-ray depth confidence is mixed from the precomputed maps with the learned per-image weights and those are trained inside
         the step (`self.conf`, _ConfAdam) -- see `step`.  `conf_lr` / `conf_betas` / `conf_eps`: their own Adam (confidence.py:182-184:
-        lr 1e-3, no schedule)."""
+        lr 1e-3, no schedule).
+        `smooth_patch_sz` (configs: smooth_loss = True; arg_parser's patch_sz; None = off): the edge-aware smoothness of depth patches
+        (train.py:154-177) joins the step -- see `step`'s `n_rgb`.  `smooth_lambda`: its weight (arg_parser's smooth_lambda);
+        `smooth_skymask`: edges whose left / top pixel is sky count twice (SmoothLoss's use_skymask), `step` then needs `smooth_sky`."""
         self.model = model
         self.lr, self.betas, self.eps = lr, betas, eps
         self.nonfinite, self.grad_max_val, self.grad_max_norm = nonfinite, float(grad_max_val), float(grad_max_norm)
@@ -386,6 +391,12 @@ class MipTrainer(_AdamState):
         if (conf_net is None) != (conf_maps is None):
             raise ValueError("MipTrainer: conf_net= and conf_maps= go together (the learned weights and the maps they mix)")
         self.conf = None if conf_net is None else _ConfAdam(conf_net, conf_maps, a.flat.device, conf_lr, conf_betas, conf_eps)
+        self.smooth_patch_sz = None if smooth_patch_sz is None else int(smooth_patch_sz)
+        if self.smooth_patch_sz is not None and not 2 <= self.smooth_patch_sz <= 32:
+            raise ValueError("MipTrainer: smooth_patch_sz in 2..32 (one workgroup lane per patch pixel)")
+        self.smooth_lambda, self.smooth_skymask = float(smooth_lambda), bool(smooth_skymask)
+        self.last_smooth_loss = None
+        self._smooth_bufs = {}                       # the trainer's own depth targets / labels / scratch of the smooth term, by shape
 
     def broadcast_parameters(self, src=0):
         if self.world > 1:
@@ -471,7 +482,7 @@ class MipTrainer(_AdamState):
         return out[4], (g_dist0, None, g_w0, g_rgb1, g_dist1, None, None)      # out[4]: their sum, formed by the same launch
 
     def step(self, rays, target_rgb, target_depth=None, conf=None, randomized=True, s_rand=None, u=None, ray_grads=False, viewc=None, img_i=None,
-             target_semantic=None, sel_coords=None, depth_keep=None):
+             target_semantic=None, sel_coords=None, depth_keep=None, n_rgb=None, smooth_sky=None):
         """`ray_grads=True` (pose refinement, configs: pose_refine = True): `last_ray_grads` = d loss / d (origins, directions, viewdirs)
         of this rank's rays, for the caller's pose optimiser (`rays.origins.backward(g_o)` etc. chains them into the pose parameters).
         `viewc` (fn = 0 models, the view-centred warp): the warp centre the reference passes to every forward (train.py:36,112); a model
@@ -494,7 +505,19 @@ class MipTrainer(_AdamState):
         the batch's rays from the maps with the learned weights of image img_i (ops.conf_apply, never a host read of the index), runs
         the loss tail's g_conf route (loss rules, `depth_keep` and the semantic term keep working), reduces d loss / d conf to the
         gradient of the image's column of the table right behind the tail (ops.conf_grad) and follows the model's Adam (and the pose
-        table's) with the confidence table's.  `last_conf` [n] is the confidence the step used."""
+        table's) with the confidence table's.  `last_conf` [n] is the confidence the step used.
+        With `smooth_patch_sz` = p (train.py:149-191): `n_rgb` = the number of rows in front of the batch's patch rows (a
+        PatchRayBatcher's `n_rgb_rows`); the n - n_rgb rows behind them are whole patches of p^2 rays each, so their number is read from
+        the batch and a rank's share needs no other plumbing.  The RGB and proposal terms count all n rays; the depth terms and the
+        semantic term count the first n_rgb only: the tail is handed a depth target of 0 (what it masks out already; calc_depth_loss
+        averages over target_depth != 0, so this equals the reference's slicing) and a label of -100 on the patch rows, in buffers the
+        trainer owns -- the caller's tensors are never written.  Behind the tail, ops.smooth_loss runs on target_rgb[n_rgb:] and the
+        fine distances [n_rgb:] and adds smooth_lambda * SmoothLoss to the loss and its gradient to the fine level's distance
+        gradient.  `smooth_sky` fp32 [n - n_rgb] (the batcher's sky extra on the patch rows): needed iff `smooth_skymask`.
+        `last_smooth_loss` is a device scalar; `last_losses` keeps its four entries.  A batch without patch rows (n_rgb == n) launches
+        nothing more and the term is 0.  world > 1: every rank averages over its own patches, like the other terms.  The reference
+        slices the semantic rows AFTER its Waymo row mask (train.py:142-144,186-187), which misaligns labels and rays; that is not
+        reproduced: the semantic term counts the first n_rgb rays that pass the rules."""
         self._set_viewc(viewc)
         if self.pose is not None and img_i is None:
             raise ValueError("MipTrainer with a pose_net: step() needs img_i= (the image the rays belong to)")
@@ -510,7 +533,7 @@ class MipTrainer(_AdamState):
         # every block of the gradient arena goes on the wire as soon as the backward pass has finished it (heads, then trunk layer by
         # trunk layer, then the proposal network): the collectives run under the remaining backward kernels
         loss, outs = self._forward_backward(rays, target_rgb, target_depth, conf, randomized, s_rand, u, ray_grads, ex, img_i,
-                                            target_semantic, sel_coords, depth_keep)
+                                            target_semantic, sel_coords, depth_keep, n_rgb, smooth_sky)
         ex.finish()
         self.t += 1
         self._adam()                                      # graph mode: step count and lr live on the device (capture / replay below)
@@ -556,8 +579,53 @@ class MipTrainer(_AdamState):
             img_i = self._img_dev[1]
         return target_semantic, sel_coords, img_i.to(dev), depth_keep
 
+    def _smooth_own(self, key, src, n_rgb, fill):
+        """the trainer's own copy of a per-ray target whose patch rows [n_rgb:] hold `fill` (set once, when the buffer is made); one
+        copy launch per step, the caller's tensor is only read"""
+        key = (key, tuple(src.shape), src.dtype, n_rgb)
+        own = self._smooth_bufs.get(key)
+        if own is None:
+            own = self._smooth_bufs[key] = torch.full_like(src, fill)
+        own[:n_rgb].copy_(src[:n_rgb])
+        return own
+
+    def _smooth_split(self, n, n_rgb, smooth_sky, dev):
+        """checks of step's smooth arguments -> (n_rgb, number of patches, sky [P p^2] or None)"""
+        if self.smooth_patch_sz is None:
+            if n_rgb is not None or smooth_sky is not None:
+                raise ValueError("MipTrainer: n_rgb= / smooth_sky= given, but the smooth term is off (smooth_patch_sz=None)")
+            return n, 0, None
+        if n_rgb is None:
+            raise ValueError("MipTrainer with smooth_patch_sz: step() needs n_rgb= (the rows in front of the patch rows; a PatchRayBatcher's n_rgb_rows)")
+        n_rgb, pp = int(n_rgb), self.smooth_patch_sz ** 2
+        if not 0 <= n_rgb <= n or (n - n_rgb) % pp:
+            raise ValueError(f"MipTrainer: the {n} - n_rgb = {n - n_rgb} patch rows are not whole patches of {pp} rays")
+        if self.smooth_skymask != (smooth_sky is not None):
+            raise ValueError("MipTrainer: smooth_sky= (the sky mask on the patch rows) is needed with smooth_skymask=True and only then")
+        if smooth_sky is not None:
+            smooth_sky = smooth_sky.to(dev, torch.float32).reshape(-1).contiguous()
+            if smooth_sky.shape[0] != n - n_rgb:
+                raise ValueError("MipTrainer: smooth_sky needs one value per patch row")
+        return n_rgb, (n - n_rgb) // pp, smooth_sky
+
+    def _smooth_term(self, outs, target_rgb, n_rgb, P, sky, loss, g):
+        """ops.smooth_loss behind the tail: the loss joins the tail's total (`loss` is that device word), the gradient the fine level's
+        distance gradient -> g with g_dist1 in place"""
+        dist1 = outs[5].reshape(-1)
+        g_dist1, fresh = g[4], g[4] is None
+        if fresh:                                        # (no depth term: the tail formed no distance gradient)
+            g_dist1 = torch.zeros_like(dist1)
+        ws = self._smooth_bufs.get(("ws", P))
+        if ws is None:
+            ws = self._smooth_bufs[("ws", P)] = torch.empty(ops.smooth_loss_ws(P), dtype=torch.float64, device=dist1.device)
+        out = torch.empty(3, dtype=torch.float32, device=dist1.device)
+        ops.smooth_loss(target_rgb[n_rgb:], dist1[n_rgb:], sky, P, self.smooth_patch_sz, self.smooth_lambda, out=out, total=loss,
+                        g_dist=g_dist1.reshape(-1)[n_rgb:], accumulate=not fresh, ws=ws)
+        self.last_smooth_loss = out[0]
+        return g[:4] + (g_dist1,) + g[5:]
+
     def _forward_backward(self, rays, target_rgb, target_depth, conf, randomized, s_rand, u, ray_grads, on_done, img_i=None,
-                          target_semantic=None, sel_coords=None, depth_keep=None):
+                          target_semantic=None, sel_coords=None, depth_keep=None, n_rgb=None, smooth_sky=None):
         """draws, both levels forward, the fused loss tail, the backward pass into the gradient arena (no exchange, no optimiser); with a
         pose table: its row applied to the rays in front, the ray gradients reduced into its gradient buffer behind"""
         m = self.model
@@ -565,6 +633,7 @@ class MipTrainer(_AdamState):
         n = rays.origins.shape[0]
         ps = self.pose
         cf = self.conf
+        n_rgb, n_patches, smooth_sky = self._smooth_split(n, n_rgb, smooth_sky, dev)
         if cf is not None:
             cf.check_views()
             c_coords = sel_coords.to(dev, torch.int64).contiguous()
@@ -576,6 +645,11 @@ class MipTrainer(_AdamState):
         rule_img = None
         if masked:
             target_semantic, sel_coords, rule_img, depth_keep = self._tail_extras(n, dev, target_depth, img_i, target_semantic, sel_coords, depth_keep)
+        if n_patches > 0:                                # the depth and semantic terms leave the patch rows out
+            if target_depth is not None:
+                target_depth = self._smooth_own("depth", target_depth, n_rgb, 0.0)
+            if target_semantic is not None:
+                target_semantic = self._smooth_own("labels", target_semantic, n_rgb, -100)
         if ps is not None:
             ps.check_views()
             f32 = lambda x: x.detach().to(dev, torch.float32).contiguous()
@@ -594,6 +668,10 @@ class MipTrainer(_AdamState):
                 cf.reduce(c_img, c_coords, self.last_g_conf)
         else:
             loss, g = self.loss_and_grads(outs, target_rgb, target_depth, conf)
+        if n_patches > 0:
+            g = self._smooth_term(outs, target_rgb, n_rgb, n_patches, smooth_sky, loss, g)
+        elif self.smooth_patch_sz is not None:
+            self.last_smooth_loss = torch.zeros((), dtype=torch.float32, device=dev)
         self.last_ray_grads = m._backward(ctx, *g, on_done=on_done, ray_grads=ray_grads)
         if ps is not None:
             g_o, g_d, g_v = self.last_ray_grads
@@ -602,7 +680,7 @@ class MipTrainer(_AdamState):
 
     # ---- hipGraph capture of the whole step --------------------------------------------------------------------------------------
     def capture(self, rays, target_rgb, target_depth=None, conf=None, randomized=True, warmup=3, viewc=None, batcher=None, conf_extra=None,
-                img_i=None, sem_extra=None, depth_keep_extra=None):
+                img_i=None, sem_extra=None, depth_keep_extra=None, smooth_sky_extra=None):
         """Capture one full training step (draws, forward, loss tail, backward, Adam: ~130 launches) in a hipGraph over the GIVEN tensors;
         afterwards `replay()` runs a step with one graph launch -- the caller refreshes the batch by copying into those tensors
         (`rays.origins.copy_(...)` etc.).  Worth it when the step is launch-bound: at 512 rays per GPU (the 8-GPU split of the
@@ -637,7 +715,11 @@ class MipTrainer(_AdamState):
         `sem_extra` / `depth_keep_extra`: indices of the batcher's extra maps that serve as `step`'s `target_semantic` (a label map
         stored as fp32) and `depth_keep` (a seg map); with loss rules the captured tail takes `sel_coords` and the image from the batch
         buffers, so every replay applies the rules of the image it drew, without a host read.  (Labels, `depth_keep` and loss rules
-        are captured with a batcher only.)"""
+        are captured with a batcher only.)
+
+        With `smooth_patch_sz` (a sample_utils.PatchRayBatcher only): the captured step takes `n_rgb` from the batcher's `n_rgb_rows`
+        and, with `smooth_skymask`, the sky of the patch rows from the batcher's extra map `smooth_sky_extra`; the trainer-owned target
+        copies, ops.smooth_loss and its finish launch are nodes of the graph.  Nothing on the host depends on the batch."""
         self._set_viewc(viewc)                           # (fn = 0: the centre is a kernel argument, i.e. a constant of the captured graph)
         a = self.model.arena
         dev = a.flat.device
@@ -667,6 +749,17 @@ class MipTrainer(_AdamState):
             b_snap = (batcher.counter.clone(), batcher.step)
             img_i = self.batch[4] if (ps is not None or self.rules is not None or cf is not None) else None
             sel_coords = self.batch[3] if (self.rules is not None or cf is not None) else None
+        n_rgb = smooth_sky = None
+        if self.smooth_patch_sz is not None:
+            if not getattr(batcher, "draws_patches", False) or batcher.patch_sz != self.smooth_patch_sz:
+                raise ValueError("capture() with smooth_patch_sz needs batcher= a PatchRayBatcher of that patch size: the captured step takes "
+                                 "the patch rows from its buffers")
+            if self.smooth_skymask != (smooth_sky_extra is not None):
+                raise ValueError("capture(): smooth_sky_extra= (the batcher's sky extra) is needed with smooth_skymask=True and only then")
+            n_rgb = batcher.n_rgb_rows
+            smooth_sky = None if smooth_sky_extra is None else extras[smooth_sky_extra][n_rgb:]
+        elif smooth_sky_extra is not None:
+            raise ValueError("capture(): smooth_sky_extra= given, but the smooth term is off (smooth_patch_sz=None)")
         if self.rules is not None and batcher is None:
             raise ValueError("capture() with loss_rules needs batcher=: the captured tail takes sel_coords and the image from its buffers")
         if cf is not None and batcher is None:
@@ -674,7 +767,7 @@ class MipTrainer(_AdamState):
         if (ps is not None or self.rules is not None or cf is not None) and not (torch.is_tensor(img_i) and img_i.is_cuda):
             raise ValueError("capture() with a pose_net or loss_rules: img_i= must be an int64 [1] device tensor (a python int would be frozen into the graph)")
         args = (rays, target_rgb, target_depth, conf)
-        tail = dict(target_semantic=target_semantic, sel_coords=sel_coords, depth_keep=depth_keep)
+        tail = dict(target_semantic=target_semantic, sel_coords=sel_coords, depth_keep=depth_keep, n_rgb=n_rgb, smooth_sky=smooth_sky)
 
         def draw():
             if batcher is not None:
