@@ -510,6 +510,49 @@ int snerf_zip_ray_batch(const void* images, int images_u8, const float* depths, 
                         float* origins, float* directions, float* viewdirs, float* radii, float* imageplane, float* base_x,
                         float* base_y, float* lossmult, float* near_out, float* far_out, float* cam_idx, float* glo_idx, float* rgb,
                         float* depth, int* semantic, float* mask, int* pix_x, int* pix_y, void* stream);
+/* snerf_zip_ray_batch for patch_size = p in 2..32 (datasets.py:397-414 next_train, :508-541 _next_train): n % (4 p^2) = 0; the first
+ * n_patch p^2 positions of the global batch, n_patch = (n / 4) / p^2, are whole patches of p x p pixels in order k, rows dy-outer,
+ * dx-inner; the other n - n / 4 positions are single pixels.  Patch k draws its camera, x0 in [border, W - border - p] and y0 in
+ * [border, H - border - p] with snerf_zip_ray_batch's bounded draw as (i, v) = (k p^2, 0 / 1 / 2); its pixels are (x0 + dx, y0 + dy).
+ * A pixel position keeps the draw it has in snerf_zip_ray_batch for the same seed and step; single_image = 1: every row takes the
+ * camera of position 0.  ONE launch writes patches [k0, k1) followed by positions [i0, i1), n_patch p^2 <= i0 <= i1 <= n (a rank's
+ * whole patches, then its pixels): (k1 - k0) p^2 + (i1 - i0) rows in every output; given (x, y, camera), every field of a row is
+ * computed as by snerf_zip_ray_batch.  One counter advance per launch; graph-safe.  n = 0 is a no-op.  Bad arguments (those of
+ * snerf_zip_ray_batch; p outside 2..32; n % (4 p^2) != 0; 2 border + p > W or H; 0 <= k0 <= k1 <= n_patch or the bounds of i0, i1 not
+ * holding) return 1 before any launch. */
+int snerf_zip_ray_patch_batch(const void* images, int images_u8, const float* depths, const int* semantics, const float* masks,
+                              const float* pixtocams, const float* camtoworlds, const int* local2global, int N, int H, int W, float near,
+                              float far, int border, int patch_size, int single_image, long seed, long* counter, long n, long k0, long k1,
+                              long i0, long i1, float* origins, float* directions, float* viewdirs, float* radii, float* imageplane,
+                              float* base_x, float* base_y, float* lossmult, float* near_out, float* far_out, float* cam_idx,
+                              float* glo_idx, float* rgb, float* depth, int* semantic, float* mask, int* pix_x, int* pix_y, void* stream);
+/* The patch terms of s-nerfpp/zipnerf/train.py:280-293 on P patches of p x p rays (p in 2..32, layout [k, dy, dx]), values and gradients
+ * in one pass: d_smo = d_mult * edge_aware_loss_v2(rgb, 1 / (depth + 1e-5), mask) and s_smo = s_mult * edge_aware_loss_for_semantic(rgb,
+ * sem, mask) (internal/train_utils.py:297-315, 337-359, the `mask is not None` branch).  fp32: rgb [P,p,p,3] target colours, depth
+ * [P,p,p] rendered, sem [P,p,p,C] rendered probabilities with row stride ld_sem >= C, C in 1..32 (NULL = no semantic term: s_smo = 0,
+ * g_sem not touched, ld_sem / C ignored), mask [P,p,p] in the batch's convention, > 0 = masked out (NULL = every pixel valid).
+ *   disp = 1 / (depth + 1e-5) (no clamp), u = disp / (patch mean of disp over all p^2 pixels, masked or not, + 1e-7),
+ *   v_c = sem_c / (patch mean of sem_c + 1e-5), w(a, b) = exp(-mean_c |rgb_a - rgb_b|);
+ *   x-edges join (dy, dx) and (dy, dx + 1), y-edges (dy, dx) and (dy + 1, dx); an edge is valid when both pixels are unmasked,
+ *   Nx / Ny = the valid x- / y-edges of all P patches;
+ *   d_smo = d_mult (sum over valid x-edges of |u_a - u_b| w / Nx + the same over y-edges / Ny),
+ *   s_smo = s_mult (sum over valid x-edges of (sum_c |v_c,a - v_c,b|) w / Nx + the same over y-edges / Ny).
+ * Nx = 0 or Ny = 0: both terms and all gradients are exactly 0, as torch.nan_to_num of the empty mean gives.  Other non-finite values
+ * propagate as they are: nan_to_num's mapping of +-inf to the largest float is NOT reproduced.
+ * out[4] = {d_smo, s_smo, Nx, Ny} (the counts as floats); total (nullable device float) += d_smo, then += s_smo.
+ * g_depth [P p^2] and g_sem [P p^2, ld_sem] = grad_mult * d (d_smo + s_smo) / d (depth, sem), stored when accumulate = 0 and ADDED
+ * when 1: grad_mult (the trainer's loss scale) multiplies the gradients and not the values.  The gradients follow torch's rules:
+ * through the patch means (a masked pixel of a patch with valid edges has a gradient) and through 1 / (depth + 1e-5); sign(0) = 0.
+ * One workgroup per patch, float64 throughout, each output rounded to fp32 once.  With a mask the edge counts come from an integer
+ * count launch ahead of the main one (a memset node zeroes the counters); the patches' sums pass through ws (>= snerf_zip_smooth_loss_ws(P)
+ * doubles of device scratch, ws_doubles = its length) and are added in a fixed order by a one-wave launch: no floating-point atomics,
+ * bit-reproducible, graph-safe, no host read.  P = 0 is a no-op; bad arguments (a null rgb / depth / out / g_depth / ws, a short ws,
+ * P < 0, p outside 2..32, accumulate outside {0, 1}; with sem: C outside 1..32, ld_sem < C, a null g_sem) return 1 before any launch. */
+int snerf_zip_smooth_loss(const float* rgb, const float* depth, const float* sem, long ld_sem, int C, const float* mask, long P, int p,
+                          float d_mult, float s_mult, float grad_mult, double* ws, long ws_doubles, float* out, float* total,
+                          float* g_depth, float* g_sem, int accumulate, void* stream);
+/* doubles of scratch snerf_zip_smooth_loss needs for P patches */
+long snerf_zip_smooth_loss_ws(long P);
 /* Per-ray loss tail of s-nerfpp/zipnerf/train.py:250-311, value and gradients w.r.t. the renderer outputs in one pass:
  * data term (internal/train_utils.py:62-90; mse = 0: Charbonnier sqrt(resid^2 + pad^2), 1: resid^2) weighted by lossmult [R]
  * (nullable = 1) and normalised by its sum; disparity L1 |1/(depth+1e-5) - 1/(1e-5+tdepth)| as a masked mean under dmask [R]

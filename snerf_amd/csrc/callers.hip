@@ -718,6 +718,186 @@ extern "C" int snerf_smooth_loss(const float* rgb, const float* dist, const floa
 }
 
 // ---------------------------------------------------------------------------
+// The patch terms of the zipnerf loop (s-nerfpp/zipnerf/train.py:280-293): d_smo = edge_aware_loss_v2 on the rendered disparity,
+// s_smo = edge_aware_loss_for_semantic on the rendered class probabilities (internal/train_utils.py:297-315, 337-359, both in their
+// `mask is not None` branch), values and gradients in one pass.  Per patch of p x p pixels (layout [dy][dx]), valid = !(mask > 0):
+//   disp = 1 / (depth + 1e-5), u = disp / (mean(disp) + 1e-7);  v_c = sem_c / (mean(sem_c) + 1e-5)  (means over all p^2 pixels);
+//   w(a, b) = exp(-mean_c |rgb_a - rgb_b|);  x-edge (a, b = right neighbour), y-edge (a, b = lower neighbour), counted when both
+//   pixels are valid:  depth |u_a - u_b| w,  semantic (sum_c |v_c,a - v_c,b|) w;
+//   term = mult (sum of the valid x-edge values / Nx + the same for y / Ny), Nx / Ny = the valid edges of ALL patches.
+// Nx and Ny scale every gradient, so they are counted first: zip_smooth_count_kernel (one workgroup per patch, wave ballots, one
+// integer atomic per wave into the two counters at the head of ws, zeroed by a memset node ahead of it).  Then one workgroup per
+// patch, one lane per pixel, float64 throughout (the fp32 inputs convert exactly, every output is rounded once): u goes through LDS
+// to the neighbours, each lane owns the edge to its right and the edge below it and leaves their signed, 1/N-scaled weights in LDS,
+// from which every lane collects q = d (sum_x / Nx + sum_y / Ny) / d u of its pixel.  With M = mean + eps and S = sum_i q_i disp_i:
+// d / d disp_j = q_j / M - S / (M^2 p^2) (a masked pixel has q = 0 and keeps the second part), times -1 / (depth + 1e-5)^2 for the
+// depth; sign(0) = 0.  The classes of the semantic term run one after the other through the same LDS arrays.  The patch's four edge
+// sums go to ws and a one-wave finish launch adds them in a fixed order: no floating-point atomics, two calls give the same bits.
+// Nx = 0 or Ny = 0: both terms and every gradient are exactly 0 (torch.nan_to_num of the empty mean, whose gradient is 0).
+// ---------------------------------------------------------------------------
+struct ZipSmoothArgs {
+  const float *rgb, *depth, *sem, *mask;   // [P,p,p,3], [P,p,p], [P,p,p,ld] nullable, [P,p,p] nullable
+  long ld; int C;
+  long P; int p;
+  double d_mult, s_mult, grad_mult;
+  unsigned long long* cnt;                 // ws[0..1] as integers: {Nx, Ny}
+  double* sums;                            // ws + 2: [P,4] = each patch's {depth x, depth y, semantic x, semantic y} edge sums
+  float *out, *total, *g_depth, *g_sem;
+  int accumulate;
+};
+
+__device__ __forceinline__ bool zip_smooth_valid(const ZipSmoothArgs& a, long i) { return a.mask == nullptr || !(a.mask[i] > 0.f); }
+
+__global__ __launch_bounds__(1024) void zip_smooth_count_kernel(ZipSmoothArgs a) {
+  const int p = a.p, pp = p * p, t = (int)threadIdx.x;
+  const long base = (long)blockIdx.x * pp;
+  bool ex = false, ey = false;
+  if (t < pp && zip_smooth_valid(a, base + t)) {
+    const int y = t / p, x = t - y * p;
+    ex = x + 1 < p && zip_smooth_valid(a, base + t + 1);
+    ey = y + 1 < p && zip_smooth_valid(a, base + t + p);
+  }
+  const unsigned long long bx = __ballot(ex), by = __ballot(ey);
+  if ((t & 63) == 0) {
+    if (bx != 0ull) atomicAdd(a.cnt, (unsigned long long)__popcll(bx));
+    if (by != 0ull) atomicAdd(a.cnt + 1, (unsigned long long)__popcll(by));
+  }
+}
+
+// one normalised channel of a patch (disparity, or one class): z = the lane's value, ex / ey = its edges' 1/N-scaled exp weights (0
+// where the edge is missing or masked).  -> d (sum_x / Nx + sum_y / Ny) / d z of this pixel; the edges' |du| w / N are added to vx, vy
+__device__ __forceinline__ double zip_smooth_channel(double z, double eps, bool live, int t, int x, int y, int p, double ex, double ey,
+                                                     double* s_u, double* s_gx, double* s_gy, double* s_part, double& vx, double& vy) {
+  const int pp = p * p;
+  const double M = smooth_block_sum(z, s_part) / (double)pp + eps;
+  const double u = z / M;
+  s_u[t] = u;
+  __syncthreads();
+  double gx = 0.0, gy = 0.0;
+  if (live && x + 1 < p) {
+    const double du = u - s_u[t + 1];
+    vx += fabs(du) * ex;
+    gx = du > 0.0 ? ex : (du < 0.0 ? -ex : 0.0);
+  }
+  if (live && y + 1 < p) {
+    const double du = u - s_u[t + p];
+    vy += fabs(du) * ey;
+    gy = du > 0.0 ? ey : (du < 0.0 ? -ey : 0.0);
+  }
+  s_gx[t] = gx;
+  s_gy[t] = gy;
+  __syncthreads();
+  double q = 0.0;
+  if (live) {
+    q = gx + gy;
+    if (x > 0) q -= s_gx[t - 1];
+    if (y > 0) q -= s_gy[t - p];
+  }
+  const double S = smooth_block_sum(q * z, s_part);
+  return q / M - S / (M * M * (double)pp);
+}
+
+__global__ __launch_bounds__(1024) void zip_smooth_loss_kernel(ZipSmoothArgs a) {
+  __shared__ double s_u[1024], s_gx[1024], s_gy[1024], s_part[16];
+  const int p = a.p, pp = p * p, t = (int)threadIdx.x;
+  const bool live = t < pp;
+  const long base = (long)blockIdx.x * pp;
+  const int y = t / p, x = t - y * p;
+  const long full = a.P * p * (p - 1);
+  const long Nx = a.mask != nullptr ? (long)a.cnt[0] : full, Ny = a.mask != nullptr ? (long)a.cnt[1] : full;
+  if (Nx == 0 || Ny == 0) {                           // the same in every lane of every workgroup
+    if (live && !a.accumulate) {
+      a.g_depth[base + t] = 0.f;
+      if (a.sem != nullptr)
+        for (int c = 0; c < a.C; ++c) a.g_sem[(base + t) * a.ld + c] = 0.f;
+    }
+    if (t < 4) a.sums[4 * blockIdx.x + t] = 0.0;
+    return;
+  }
+  double ex = 0.0, ey = 0.0;                          // exp weight / N of the lane's two edges, 0 where there is none
+  if (live && zip_smooth_valid(a, base + t)) {
+    const float* c0 = a.rgb + 3 * (base + t);
+    if (x + 1 < p && zip_smooth_valid(a, base + t + 1)) {
+      const float* c1 = c0 + 3;
+      ex = exp(-((fabs((double)c0[0] - (double)c1[0]) + fabs((double)c0[1] - (double)c1[1])) + fabs((double)c0[2] - (double)c1[2])) / 3.0) / (double)Nx;
+    }
+    if (y + 1 < p && zip_smooth_valid(a, base + t + p)) {
+      const float* c1 = c0 + 3 * p;
+      ey = exp(-((fabs((double)c0[0] - (double)c1[0]) + fabs((double)c0[1] - (double)c1[1])) + fabs((double)c0[2] - (double)c1[2])) / 3.0) / (double)Ny;
+    }
+  }
+  double dx = 0.0, dy = 0.0, sx = 0.0, sy = 0.0;
+  {
+    const double dd = live ? (double)a.depth[base + t] + 1e-5 : 1.0;
+    const double disp = live ? 1.0 / dd : 0.0;
+    const double g_disp = zip_smooth_channel(disp, 1e-7, live, t, x, y, p, ex, ey, s_u, s_gx, s_gy, s_part, dx, dy);
+    if (live) {
+      const float g = (float)(g_disp * (-1.0 / (dd * dd)) * (a.d_mult * a.grad_mult));
+      a.g_depth[base + t] = a.accumulate ? a.g_depth[base + t] + g : g;
+    }
+  }
+  if (a.sem != nullptr) {
+    for (int c = 0; c < a.C; ++c) {
+      const long i = (base + t) * a.ld + c;
+      const double z = live ? (double)a.sem[i] : 0.0;
+      const double g_z = zip_smooth_channel(z, 1e-5, live, t, x, y, p, ex, ey, s_u, s_gx, s_gy, s_part, sx, sy);
+      if (live) {
+        const float g = (float)(g_z * (a.s_mult * a.grad_mult));
+        a.g_sem[i] = a.accumulate ? a.g_sem[i] + g : g;
+      }
+    }
+  }
+  dx = smooth_block_sum(dx, s_part); dy = smooth_block_sum(dy, s_part);
+  sx = smooth_block_sum(sx, s_part); sy = smooth_block_sum(sy, s_part);
+  if (t == 0) {
+    double* o = a.sums + 4 * blockIdx.x;
+    o[0] = dx; o[1] = dy; o[2] = sx; o[3] = sy;
+  }
+}
+
+__global__ __launch_bounds__(64) void zip_smooth_finish_kernel(ZipSmoothArgs a) {
+  double s[4] = {0.0, 0.0, 0.0, 0.0};
+  for (long k = threadIdx.x; k < a.P; k += 64) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) s[j] += a.sums[4 * k + j];
+  }
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+    for (int o = 32; o > 0; o >>= 1) s[j] += __shfl_xor(s[j], o, 64);
+  if (threadIdx.x == 0) {
+    const long full = a.P * a.p * (a.p - 1);
+    const long Nx = a.mask != nullptr ? (long)a.cnt[0] : full, Ny = a.mask != nullptr ? (long)a.cnt[1] : full;
+    const float d_smo = (float)(a.d_mult * (s[0] + s[1])), s_smo = (float)(a.s_mult * (s[2] + s[3]));    // (the 1 / N are in the sums)
+    a.out[0] = d_smo;
+    a.out[1] = s_smo;
+    a.out[2] = (float)Nx;
+    a.out[3] = (float)Ny;
+    if (a.total != nullptr) *a.total = (*a.total + d_smo) + s_smo;
+  }
+}
+
+extern "C" long snerf_zip_smooth_loss_ws(long P) { return P <= 0 ? 0 : 2 + 4 * P; }
+
+extern "C" int snerf_zip_smooth_loss(const float* rgb, const float* depth, const float* sem, long ld_sem, int C, const float* mask, long P, int p,
+                                     float d_mult, float s_mult, float grad_mult, double* ws, long ws_doubles, float* out, float* total,
+                                     float* g_depth, float* g_sem, int accumulate, void* stream) {
+  if (P == 0) return SNERF_OK;
+  if (P < 0 || P > 0x7FFFFFFFL || p < 2 || p > 32 || (accumulate != 0 && accumulate != 1)) return SNERF_ERR_ARG;
+  if (rgb == nullptr || depth == nullptr || out == nullptr || g_depth == nullptr || ws == nullptr || ws_doubles < 2 + 4 * P) return SNERF_ERR_ARG;
+  if (sem != nullptr && (C < 1 || C > 32 || ld_sem < C || g_sem == nullptr)) return SNERF_ERR_ARG;
+  ZipSmoothArgs a{rgb, depth, sem, mask, ld_sem, C, P, p, (double)d_mult, (double)s_mult, (double)grad_mult, (unsigned long long*)ws, ws + 2,
+                  out, total, g_depth, g_sem, accumulate};
+  const dim3 grid((unsigned)P), block((unsigned)((p * p + 63) / 64 * 64));
+  if (mask != nullptr) {
+    if (hipMemsetAsync(ws, 0, 2 * sizeof(double), (hipStream_t)stream) != hipSuccess) return snerf_check_launch();   // (no count on stale counters)
+    hipLaunchKernelGGL(zip_smooth_count_kernel, grid, block, 0, (hipStream_t)stream, a);
+  }
+  hipLaunchKernelGGL(zip_smooth_loss_kernel, grid, block, 0, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(zip_smooth_finish_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, a);
+  return snerf_check_launch();
+}
+
+// ---------------------------------------------------------------------------
 // zipnerf (path C) ray generation: s-nerfpp/zipnerf/internal/camera_utils.py:453-563 (pixels_to_rays), perspective camera, no
 // distortion, no NDC.  numpy promotes to float64 there (integer pixels + .5); the dataset casts the result to fp32.  One lane
 // per ray, float64 arithmetic, one rounding per emitted value.
@@ -810,6 +990,7 @@ extern "C" int snerf_zip_pixels_to_rays(const int* pix_x, const int* pix_y, cons
 //   2^32 mod range (Lemire's unbiased bounded integers); value = lo + hi32(m).  Attempt 255 is accepted as it is (a rejection has
 //   probability range / 2^32).  batching 'single_image': every ray takes the camera of ray 0.
 //   snerf_mip_image_patch_batch, step s, patch k: the same bounded draw with (i, v) = (k, 3) over the patch-centre window (below).
+//   snerf_zip_ray_patch_batch, step s, patch k of p x p pixels: camera, x0, y0 = the same draw with (i, v) = (k p^2, 0 / 1 / 2).
 // A ray's draws depend on (seed, step, i) only: not on the rank slice [i0, i1) a launch writes, nor on the launch geometry.
 // Step counter ctr[2] (int64, device): ctr[0] = step.  Every workgroup reads it and takes a ticket (ctr[1]); the last one stores
 // step + 1 and resets the ticket: a replayed graph launch draws a new batch every time.
@@ -1003,16 +1184,11 @@ struct ZipBatch {
   float *origins, *directions, *viewdirs, *radii, *imageplane, *base_x, *base_y, *lossmult, *near_out, *far_out, *cam_out, *glo_out;
   float *rgb, *depth; int* semantic; float* mask;
   int *pix_x, *pix_y;
+  int patch; long pk0, pk1;                         // snerf_zip_ray_patch_batch: patches [pk0, pk1) of patch^2 pixels ahead of the pixel rows
 };
 
-__global__ __launch_bounds__(256) void zip_ray_batch_kernel(ZipBatch a) {
-  const long s = batch_step(a.ctr);
-  const long i = a.i0 + (long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= a.i1) return;
-  const long r = i - a.i0;
-  const int cam = bounded_draw(a.single_image ? 0u : (unsigned)i, 0u, s, (unsigned)a.N, a.k0, a.k1);
-  const int x = a.border + bounded_draw((unsigned)i, 1u, s, (unsigned)(a.W - 2 * a.border), a.k0, a.k1);
-  const int y = a.border + bounded_draw((unsigned)i, 2u, s, (unsigned)(a.H - 2 * a.border), a.k0, a.k1);
+// one row of a path C batch: the ray and the gathered targets of pixel (x, y) of camera cam into row r
+__device__ __forceinline__ void zip_batch_row(const ZipBatch& a, int cam, int x, int y, long r) {
   zip_ray(a.pixtocams + 9 * (long)cam, a.camtoworlds + 12 * (long)cam, x, y, r, a.origins, a.directions, a.viewdirs, a.radii, a.imageplane,
           a.base_x, a.base_y);
   const long pix = ((long)cam * a.H + y) * a.W + x;
@@ -1028,6 +1204,42 @@ __global__ __launch_bounds__(256) void zip_ray_batch_kernel(ZipBatch a) {
   if (a.mask != nullptr) a.mask[r] = a.masks[pix];
   a.pix_x[r] = x;
   a.pix_y[r] = y;
+}
+
+__global__ __launch_bounds__(256) void zip_ray_batch_kernel(ZipBatch a) {
+  const long s = batch_step(a.ctr);
+  const long i = a.i0 + (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= a.i1) return;
+  const int cam = bounded_draw(a.single_image ? 0u : (unsigned)i, 0u, s, (unsigned)a.N, a.k0, a.k1);
+  const int x = a.border + bounded_draw((unsigned)i, 1u, s, (unsigned)(a.W - 2 * a.border), a.k0, a.k1);
+  const int y = a.border + bounded_draw((unsigned)i, 2u, s, (unsigned)(a.H - 2 * a.border), a.k0, a.k1);
+  zip_batch_row(a, cam, x, y, i - a.i0);
+}
+
+// Patch batches (datasets.py:397-414, 508-541): the first n_patch p^2 positions of the global batch are n_patch whole patches of p x p
+// pixels, rows [dy][dx]; patch k draws its camera and its corner (x0, y0) in [border, W - border - p] x [border, H - border - p] with
+// the bounded draw of its first position, (i, v) = (k p^2, 0 / 1 / 2).  The positions behind them are single pixels with the draw
+// they have in snerf_zip_ray_batch.  A launch writes patches [pk0, pk1) followed by positions [i0, i1).
+__global__ __launch_bounds__(256) void zip_ray_patch_batch_kernel(ZipBatch a) {
+  const long s = batch_step(a.ctr);
+  const long r = (long)blockIdx.x * 256 + threadIdx.x;
+  const long pp = (long)a.patch * a.patch, npr = (a.pk1 - a.pk0) * pp;
+  if (r >= npr + (a.i1 - a.i0)) return;
+  if (r < npr) {
+    const long k = a.pk0 + r / pp;
+    const int t = (int)(r % pp), dy = t / a.patch, dx = t - dy * a.patch;
+    const unsigned i = (unsigned)(k * pp);
+    const int cam = bounded_draw(a.single_image ? 0u : i, 0u, s, (unsigned)a.N, a.k0, a.k1);
+    const int x0 = a.border + bounded_draw(i, 1u, s, (unsigned)(a.W - 2 * a.border - a.patch + 1), a.k0, a.k1);
+    const int y0 = a.border + bounded_draw(i, 2u, s, (unsigned)(a.H - 2 * a.border - a.patch + 1), a.k0, a.k1);
+    zip_batch_row(a, cam, x0 + dx, y0 + dy, r);
+  } else {
+    const long i = a.i0 + (r - npr);
+    const int cam = bounded_draw(a.single_image ? 0u : (unsigned)i, 0u, s, (unsigned)a.N, a.k0, a.k1);
+    const int x = a.border + bounded_draw((unsigned)i, 1u, s, (unsigned)(a.W - 2 * a.border), a.k0, a.k1);
+    const int y = a.border + bounded_draw((unsigned)i, 2u, s, (unsigned)(a.H - 2 * a.border), a.k0, a.k1);
+    zip_batch_row(a, cam, x, y, r);
+  }
 }
 
 extern "C" int snerf_zip_ray_batch(const void* images, int images_u8, const float* depths, const int* semantics, const float* masks,
@@ -1052,6 +1264,35 @@ extern "C" int snerf_zip_ray_batch(const void* images, int images_u8, const floa
              imageplane, base_x, base_y, lossmult, near_out, far_out, cam_idx, glo_idx, rgb, depth, semantic, mask, pix_x, pix_y};
   const long nl = i1 - i0;
   hipLaunchKernelGGL(zip_ray_batch_kernel, dim3((unsigned)(nl > 0 ? (nl + 255) / 256 : 1)), dim3(256), 0, (hipStream_t)stream, a);
+  return snerf_check_launch();
+}
+
+extern "C" int snerf_zip_ray_patch_batch(const void* images, int images_u8, const float* depths, const int* semantics, const float* masks,
+                                         const float* pixtocams, const float* camtoworlds, const int* local2global, int N, int H, int W,
+                                         float near, float far, int border, int patch_size, int single_image, long seed, long* counter, long n,
+                                         long k0, long k1, long i0, long i1, float* origins, float* directions, float* viewdirs, float* radii,
+                                         float* imageplane, float* base_x, float* base_y, float* lossmult, float* near_out, float* far_out,
+                                         float* cam_idx, float* glo_idx, float* rgb, float* depth, int* semantic, float* mask, int* pix_x,
+                                         int* pix_y, void* stream) {
+  if (n == 0) return SNERF_OK;
+  if (n < 0 || N < 1 || H < 1 || W < 1 || border < 0 || patch_size < 2 || patch_size > 32 || n > 0xFFFFFFFFL ||
+      (single_image != 0 && single_image != 1) || (images_u8 != 0 && images_u8 != 1))
+    return SNERF_ERR_ARG;
+  const long pp = (long)patch_size * patch_size, n_patch = n / 4 / pp;
+  if (n % (4 * pp) != 0 || 2L * border + patch_size > W || 2L * border + patch_size > H) return SNERF_ERR_ARG;
+  if (k0 < 0 || k1 < k0 || k1 > n_patch || i0 < n_patch * pp || i1 < i0 || i1 > n) return SNERF_ERR_ARG;
+  if (images == nullptr || pixtocams == nullptr || camtoworlds == nullptr || counter == nullptr || origins == nullptr || directions == nullptr ||
+      viewdirs == nullptr || radii == nullptr || base_x == nullptr || base_y == nullptr || lossmult == nullptr || near_out == nullptr ||
+      far_out == nullptr || cam_idx == nullptr || rgb == nullptr || pix_x == nullptr || pix_y == nullptr)
+    return SNERF_ERR_ARG;
+  if ((depth != nullptr && depths == nullptr) || (semantic != nullptr && semantics == nullptr) || (mask != nullptr && masks == nullptr) ||
+      (glo_idx != nullptr && local2global == nullptr))
+    return SNERF_ERR_ARG;
+  ZipBatch a{images, images_u8, depths, semantics, masks, pixtocams, camtoworlds, local2global, N, H, W, border, single_image, near, far,
+             (unsigned)(unsigned long)seed, (unsigned)((unsigned long)seed >> 32), counter, n, i0, i1, origins, directions, viewdirs, radii,
+             imageplane, base_x, base_y, lossmult, near_out, far_out, cam_idx, glo_idx, rgb, depth, semantic, mask, pix_x, pix_y, patch_size, k0, k1};
+  const long nl = (k1 - k0) * pp + (i1 - i0);
+  hipLaunchKernelGGL(zip_ray_patch_batch_kernel, dim3((unsigned)(nl > 0 ? (nl + 255) / 256 : 1)), dim3(256), 0, (hipStream_t)stream, a);
   return snerf_check_launch();
 }
 

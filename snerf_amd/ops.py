@@ -1708,6 +1708,72 @@ def zip_ray_batch(images, depths, semantics, masks, pixtocams, camtoworlds, loca
     return out
 
 
+def zip_ray_patch_batch(images, depths, semantics, masks, pixtocams, camtoworlds, local2global, near, far, border, patch_size, single_image,
+                        seed, counter, n, k0, k1, i0, i1, out):
+    """snerf_zip_ray_patch_batch: patches [k0, k1) of step counter[0]'s n_patch = (n // 4) // patch_size^2 patches, then positions
+    [i0, i1) of its single pixels (n_patch patch_size^2 <= i0), into the preallocated `out` (as for zip_ray_batch, with
+    m = (k1 - k0) patch_size^2 + (i1 - i0) rows); one launch, advances counter[0]."""
+    u8 = _u8_or_f32(images)
+    N, H, W = images.shape[:3]
+    for t in (depths, masks, pixtocams, camtoworlds):
+        _f32c(t)
+    for t in (semantics, local2global):
+        assert t is None or (t.dtype == torch.int32 and t.is_contiguous())
+    assert counter.dtype == torch.int64 and counter.numel() == 2
+    m = (int(k1) - int(k0)) * int(patch_size) ** 2 + (int(i1) - int(i0))
+    assert all(v is None or v.shape[0] == m for v in out.values()), "out: (k1 - k0) patch_size^2 + (i1 - i0) rows"
+    _lib.call("snerf_zip_ray_patch_batch", _p(images), u8, _p(depths), _p(semantics), _p(masks), _p(pixtocams), _p(camtoworlds),
+              _p(local2global), N, H, W, float(near), float(far), int(border), int(patch_size), int(bool(single_image)), int(seed), _p(counter),
+              int(n), int(k0), int(k1), int(i0), int(i1), _p(out["origins"]), _p(out["directions"]), _p(out["viewdirs"]), _p(out["radii"]),
+              _p(out.get("imageplane")), _p(out["base_x"]), _p(out["base_y"]), _p(out["lossmult"]), _p(out["near"]), _p(out["far"]),
+              _p(out["cam_idx"]), _p(out.get("glo_idx")), _p(out["rgb"]), _p(out.get("depth")), _p(out.get("semantic")), _p(out.get("mask")),
+              _p(out["pix_x_int"]), _p(out["pix_y_int"]), _stream())
+    return out
+
+
+def zip_smooth_loss_ws(P):
+    """doubles of scratch zip_smooth_loss needs for P patches (snerf_zip_smooth_loss_ws)"""
+    return int(_lib.query("snerf_zip_smooth_loss_ws", int(P)))
+
+
+def zip_smooth_loss(rgb, depth, sem, mask, P, p, d_mult=0.001, s_mult=0.001, grad_mult=1.0, out=None, total=None, g_depth=None, g_sem=None,
+                    accumulate=False, ws=None):
+    """snerf_zip_smooth_loss: the patch terms of the zipnerf loop (d_smo, s_smo: masked edge-aware smoothness of the rendered disparity
+    and class probabilities) of P patches of p x p rays, values and gradients in one pass.  rgb [P p p, 3] target colours, depth [P p p]
+    rendered, sem [P p p, C] rendered probabilities (a row-major view, row stride >= C) or None, mask [P p p] (> 0 = masked out) or None
+    (fp32; rgb / depth / mask of any shape of that size) -> (out[4] = {d_smo, s_smo, Nx, Ny}, g_depth [P p p], g_sem like sem or None)
+    = grad_mult * d (d_smo + s_smo) / d (depth, sem).  total: a device float the two values are added into; g_depth / g_sem given:
+    stored into (accumulate=False) or added into (True); g_sem has sem's row stride.  Deterministic (float64 sums in a fixed order, no
+    float atomics).  ws: fp64 scratch of >= zip_smooth_loss_ws(P) elements (allocated when None).  P = 0 launches nothing."""
+    P, p = int(P), int(p)
+    n, dev = P * p * p, depth.device
+    for t in (rgb, depth, mask, total, g_depth, out):
+        _f32c(t)
+    assert rgb.numel() == 3 * n and depth.numel() == n and (mask is None or mask.numel() == n), "rgb [P,p,p,3], depth / mask [P,p,p]"
+    C = ld = 0
+    if sem is not None:
+        _chk2d(sem, torch.float32)
+        C, ld = sem.shape[1], sem.stride(0) if n > 1 else sem.shape[1]
+        assert sem.shape[0] == n and ld >= C, "sem [P p p, C]"
+        if g_sem is None:
+            assert not accumulate, "accumulate=True adds into a given g_sem"
+            g_sem = torch.empty_strided((n, C), (ld, 1), dtype=torch.float32, device=dev)
+        _chk2d(g_sem, torch.float32)
+        assert g_sem.shape == sem.shape and (n <= 1 or g_sem.stride(0) == ld), "g_sem: sem's shape and row stride"
+    if out is None:
+        out = torch.zeros(4, dtype=torch.float32, device=dev)
+    if g_depth is None:
+        assert not accumulate, "accumulate=True adds into a given g_depth"
+        g_depth = torch.empty(n, dtype=torch.float32, device=dev)
+    assert out.numel() == 4 and g_depth.numel() == n and (total is None or total.numel() == 1)
+    if ws is None:
+        ws = torch.empty(max(zip_smooth_loss_ws(P), 1), dtype=torch.float64, device=dev)
+    assert ws.is_cuda and ws.dtype == torch.float64 and ws.is_contiguous()
+    _lib.call("snerf_zip_smooth_loss", _p(rgb), _p(depth), _p(sem), ld, C, _p(mask), P, p, float(d_mult), float(s_mult), float(grad_mult),
+              _p(ws), ws.numel(), _p(out), _p(total), _p(g_depth), _p(g_sem) if sem is not None else None, int(bool(accumulate)), _stream())
+    return out, g_depth, (g_sem if sem is not None else None)
+
+
 ZIP_LOSS_NAMES = ("data", "mse", "depth", "d_complete", "sem", "interlevel", "distortion")
 
 

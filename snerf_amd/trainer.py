@@ -962,7 +962,8 @@ class ZipTrainer(_AdamState):
 
     `loss_cfg` overrides the reference defaults (internal/configs.py:60-66,85; train.py:253,272,298): charb_padding 0.001, data_mult
     1, depth_lambda 0.5, com_mult 0.2, sem_mult 0.04, pulse_width (0.03, 0.003), interlevel_mult 0.01, distortion_mult 0.005, mse False,
-    hash_decay_mult 0.1 (`snerf_hash_decay`, one pass over the three tables, value appended to `last_losses`).
+    hash_decay_mult 0.1 (`snerf_hash_decay`, one pass over the three tables, value appended to `last_losses`), d_smo_mult / s_smo_mult
+    0.001 (train.py:281-282: the patch terms of `step(n_patch=...)`, `snerf_zip_smooth_loss`, values in `last_smooth_losses`).
     Further caller-defined terms on the ray histories go through `aux_loss_fn(ray_history) -> scalar` (torch autograd on detached
     leaf copies of every level's `weights`; its d(loss)/d(weights) is added to the fused tail's)."""
 
@@ -986,6 +987,9 @@ class ZipTrainer(_AdamState):
         self.loss_cfg.update(loss_cfg or {})
         # hash-grid weight decay (train_utils.py:184-203; configs.py:74): a term on the parameters, not on the rays
         self.hash_decay_mult = float(self.loss_cfg.pop("hash_decay_mult", 0.1))
+        # the patch terms (train.py:280-293; step(n_patch=...)): computed behind the fused tail, not arguments of it
+        self.d_smo_mult, self.s_smo_mult = float(self.loss_cfg.pop("d_smo_mult", 0.001)), float(self.loss_cfg.pop("s_smo_mult", 0.001))
+        self.last_smooth_losses, self._patch_own, self._patch_ws = None, {}, None
         a = model.arena
         self.m, self.v, self.t = torch.zeros_like(a.flat), torch.zeros_like(a.flat), 0
         self.pg = process_group
@@ -1043,15 +1047,82 @@ class ZipTrainer(_AdamState):
         a.grad.zero_()
         return True
 
-    def step(self, batch, target_rgb, train_frac=1.0, rand=True, aux_loss_fn=None, draws=None, sample_n=7, sample_m=3, targets=None, zero_glo=False):
+    def _patch_targets(self, t, R, rows, dev):
+        """the targets with the patch rows [0, rows) left out of the data, depth, depth-completion and semantic terms (train.py:231-264,
+        296: mask_rgb): lossmult and the three masks with those rows zeroed, in buffers of the trainer -- the caller's tensors are not
+        written.  The loss tail reads an absent lossmult, and an absent semantic_mask beside labels, as 1 on every row: those two become
+        ones with zero patch rows; an absent depth_mask or complete_mask turns its term off and stays absent"""
+        t = dict(t)
+        for key in ("lossmult", "depth_mask", "complete_mask", "semantic_mask"):
+            src = t.get(key)
+            if src is None and not (key == "lossmult" or (key == "semantic_mask" and t.get("semantic") is not None)):
+                continue
+            own = self._patch_own.get(key)
+            if own is None or own.shape[0] != R:
+                own = self._patch_own[key] = torch.empty(R, dtype=torch.float32, device=dev)
+            if src is None:
+                own.fill_(1.0)
+            else:
+                own.copy_(src.reshape(R))
+            own[:rows].zero_()
+            t[key] = own
+        return t
+
+    def _patch_terms(self, fin, target_rgb, n_patch, p, patch_mask, G, ls, dev):
+        """d_smo + s_smo of the patch rows (ops.zip_smooth_loss) ADDED into the tail's g_depth / g_sem (zero buffers where the tail had
+        none), the loss scale in their gradients -> the sum of the two values (device scalar); `last_smooth_losses` = {d_smo, s_smo}"""
+        rows, R = n_patch * p * p, target_rgb.shape[0]
+        sem = fin.get("semantic")
+        if G["depth"] is None:
+            G["depth"] = torch.zeros(R, dtype=torch.float32, device=dev)
+        if sem is not None and G["semantic"] is None:
+            G["semantic"] = torch.zeros(R, sem.shape[1], dtype=torch.float32, device=dev)
+        n_ws = ops.zip_smooth_loss_ws(n_patch)
+        if self._patch_ws is None or self._patch_ws.numel() < n_ws:
+            self._patch_ws = torch.empty(n_ws, dtype=torch.float64, device=dev)
+        out = torch.zeros(4, dtype=torch.float32, device=dev)
+        ops.zip_smooth_loss(target_rgb[:rows], fin["depth"].reshape(-1)[:rows], None if sem is None else sem[:rows], patch_mask, n_patch, p,
+                            d_mult=self.d_smo_mult, s_mult=self.s_smo_mult, grad_mult=ls, out=out, g_depth=G["depth"].reshape(-1)[:rows],
+                            g_sem=None if sem is None else G["semantic"][:rows], accumulate=True, ws=self._patch_ws)
+        self.last_smooth_losses = out[:2]
+        return out[0] + out[1]
+
+    def step(self, batch, target_rgb, train_frac=1.0, rand=True, aux_loss_fn=None, draws=None, sample_n=7, sample_m=3, targets=None, zero_glo=False,
+             n_patch=None, patch_size=None, patch_mask=None):
         """`targets` (all optional, per ray): lossmult [R] (the reference's mask_rgb as 0/1 floats), depth [R] + depth_mask [R]
         (+ complete_mask [R]), semantic int32 labels [R] + semantic_mask [R].  `zero_glo` (models with GLO vectors): train with zero
-        vectors instead of the rows batch['cam_idx'] selects (zipnerf/train.py:235 passes zero_glo=False)."""
+        vectors instead of the rows batch['cam_idx'] selects (zipnerf/train.py:235 passes zero_glo=False).
+        `n_patch` > 0 with `patch_size` = p (a batch of zipnerf.PatchRayBatcher: n_patch = its n_patch_local): rows [0, n_patch p^2) are
+        whole p x p patches.  They leave the data, depth, depth-completion and semantic terms (train.py:231-264, 296) and carry the patch
+        terms of train.py:280-293 instead, d_smo and s_smo (loss_cfg d_smo_mult / s_smo_mult, 0.001 each; s_smo only with a semantic
+        head), computed behind the loss tail by ops.zip_smooth_loss on target_rgb and the NeRF level's depth and semantic outputs;
+        interlevel and distortion keep every ray.  `patch_mask` [n_patch p^2]: the batch's mask on those rows, > 0 = masked out (None =
+        all valid, the reference's use_mask = False).  The two values are in `last_smooth_losses` (device; None after a step without
+        patches) and in the returned loss; `last_losses` is what it is without patches.  With several ranks each averages over its own
+        patches; a rank that has none passes n_patch = 0 (an empty patch_mask is accepted there) and takes the plain step."""
         m = self.model
         m._zero_glo = bool(zero_glo)
         dev = m.arena.flat.device
         R = batch['origins'].shape[0]
         t = targets or {}
+        n_patch = int(n_patch or 0)
+        if n_patch < 0 or (n_patch > 0 and patch_size is None):
+            raise ValueError("n_patch: a count of patches >= 0, with patch_size")
+        if n_patch == 0:
+            self.last_smooth_losses = None             # (a step without patches, a rank with none: nothing stale for a logger)
+        if n_patch > 0:
+            p = int(patch_size)
+            if not 2 <= p <= 32:
+                raise ValueError(f"patch_size {p}: 2..32")
+            if n_patch * p * p > R:
+                raise ValueError(f"{n_patch} patches of {p} x {p} rays are more than the batch's {R} rows")
+            if patch_mask is not None and patch_mask.numel() != n_patch * p * p:
+                raise ValueError(f"patch_mask: one value per patch row ({n_patch * p * p}), got {patch_mask.numel()}")
+            if target_rgb.shape[0] != R:
+                raise ValueError("target_rgb: one row per ray")
+            t = self._patch_targets(t, R, n_patch * p * p, dev)
+        elif patch_mask is not None and patch_mask.numel() != 0:      # (the empty mask of a rank without patches is a plain step)
+            raise ValueError("patch_mask without n_patch")
         if draws is None:
             draws = m._draws(R, rand, dev, sample_n)
         levels, ctx = m._run(batch, True, float(train_frac), draws, sample_n, sample_m)
@@ -1078,6 +1149,9 @@ class ZipTrainer(_AdamState):
                                self.hash_decay_mult, decay, grad_mult=ls)
         self.last_losses = torch.cat([out[4:], decay])     # ops.ZIP_LOSS_NAMES + ("hash_decay",)
         loss = out[4] + out[6:].sum() + decay[0]
+        if n_patch > 0:
+            pm = None if patch_mask is None else patch_mask.detach().reshape(-1).to(dev, torch.float32).contiguous()
+            loss = loss + self._patch_terms(fin, target_rgb, n_patch, p, pm, G, ls, dev)
         g_w = [G["w0"], G["w1"], G["w2"]]
         if aux_loss_fn is not None:
             with torch.enable_grad():

@@ -598,7 +598,8 @@ class RayBatcher:
     def __init__(self, images, pixtocams, camtoworlds, near, far, depths=None, semantics=None, masks=None, local2global=None, batch_size=65536,
                  border=0, batching='all_images', patch_size=1, seed=0, rank=0, world=1, device="cuda"):
         if int(patch_size) != 1:
-            raise NotImplementedError("patch_size > 1: the batcher draws single pixels (the reference's default patch_size = 1)")
+            raise NotImplementedError("patch_size > 1: this batcher draws single pixels (the reference's default patch_size = 1); "
+                                      "PatchRayBatcher draws the patch batches")
         if batching not in ('all_images', 'single_image'):
             raise ValueError(f"batching: 'all_images' or 'single_image', not {batching!r}")
         if not 0 <= int(seed) < (1 << 63):
@@ -638,6 +639,11 @@ class RayBatcher:
         """the step of the next draw (host mirror of the device counter; `advance_host` after graph replays of `next_into`)"""
         return self._step
 
+    @property
+    def rows(self):
+        """rows of this rank's batch"""
+        return self.i1 - self.i0
+
     def state_dict(self):
         return {"seed": self.seed, "step": self._step}
 
@@ -651,7 +657,7 @@ class RayBatcher:
 
     def buffers(self):
         """fresh output tensors of one batch (this rank's rows)"""
-        m, dev = self.i1 - self.i0, self.device
+        m, dev = self.rows, self.device
         e = lambda *s, dt=torch.float32: torch.empty(*s, dtype=dt, device=dev)
         b = dict(origins=e(m, 3), directions=e(m, 3), viewdirs=e(m, 3), radii=e(m, 1), imageplane=e(m, 2), lossmult=e(m, 1), near=e(m, 1),
                  far=e(m, 1), cam_idx=e(m, 1), base_x=e(m, 3), base_y=e(m, 3), rgb=e(m, 3))
@@ -676,3 +682,46 @@ class RayBatcher:
     def next(self):
         """-> the batch dict of the next step in new tensors (they stay valid)"""
         return self.next_into(self.buffers())
+
+
+class PatchRayBatcher(RayBatcher):
+    """RayBatcher for `patch_size` = p in 2..32 (datasets.py:397-414 next_train, :508-541 _next_train): a quarter of the batch is whole
+    patches.  `batch_size % (4 p^2) == 0`; the first `n_patch` p^2 rows of the global batch, n_patch = (batch_size // 4) // p^2, are the
+    patches in order k, each [dy, dx] row-major, the other batch_size - batch_size // 4 rows single pixels.  Patch k draws its camera and
+    its corner (x0, y0) in [border, W - border - p] x [border, H - border - p] with the bounded draw of its first row; a pixel row has the
+    draw of the same row of RayBatcher(seed, step): rows [n_patch p^2, batch_size) of the two batchers are equal bit for bit.  One launch
+    (`snerf_zip_ray_patch_batch`) and one counter advance per batch, graph-capturable like RayBatcher.
+
+    `batching='single_image'`: every row takes the camera of row 0 (the reference draws one camera for the patches and another for
+    the pixels there, its two _next_train calls).  Rank r of `world` computes patches shard_bounds(n_patch, r, world) followed by the
+    pixel rows shard_bounds of the pixel part: `n_patch_local` whole patches (`n_patch_rows` rows) ahead of its pixels, which is what
+    ZipTrainer.step(n_patch=batcher.n_patch_local, patch_size=p) expects."""
+
+    def __init__(self, images, pixtocams, camtoworlds, near, far, patch_size, batch_size=65536, border=0, rank=0, world=1, **kw):
+        p, n = int(patch_size), int(batch_size)
+        if not 2 <= p <= 32:
+            raise ValueError(f"patch_size {p}: 2..32 (RayBatcher draws single pixels)")
+        if n <= 0 or n % (4 * p * p) != 0:
+            raise ValueError(f"batch_size {n} is not a multiple of 4 patch_size^2 = {4 * p * p}")
+        shape = tuple(getattr(images, "shape", ()))
+        if len(shape) == 4 and int(border) >= 0 and 2 * int(border) + p > min(shape[1:3]):      # (before anything goes to the device)
+            raise ValueError(f"no {p} x {p} patch fits a {shape[1]} x {shape[2]} image inside a border of {int(border)}")
+        super().__init__(images, pixtocams, camtoworlds, near, far, batch_size=n, border=border, patch_size=1, rank=rank, world=world, **kw)
+        from .trainer import shard_bounds
+        self.patch_size, self.n_patch = p, (n // 4) // (p * p)
+        self.k0, self.k1 = shard_bounds(self.n_patch, self.rank, self.world)
+        first = self.n_patch * p * p
+        self.i0, self.i1 = (first + b for b in shard_bounds(n - first, self.rank, self.world))
+        self.n_patch_local = self.k1 - self.k0
+        self.n_patch_rows = self.n_patch_local * p * p
+
+    @property
+    def rows(self):
+        return self.n_patch_rows + (self.i1 - self.i0)
+
+    def next_into(self, buf):
+        ops.zip_ray_patch_batch(self.images, self.depths, self.semantics, self.masks, self.pixtocams, self.camtoworlds, self.local2global,
+                                self.near, self.far, self.border, self.patch_size, self.single_image, self.seed, self.counter, self.batch_size,
+                                self.k0, self.k1, self.i0, self.i1, buf)
+        self._step += 1
+        return buf
