@@ -75,89 +75,190 @@ class _GradExchange:
 
 
 class _AdamState:
-    """Checkpointing of the fused Adam launch's state in torch.optim.Adam's `state_dict()` layout over `model.parameters()` -- what the
-    reference stores next to the weights (s-nerf/train.py:264-273 'optimzer', resumed at utils/model_utils.py:44-63; zipnerf/train.py:432-440
-    'optimizer', internal/checkpoints.py:52-54): a checkpoint written by the reference's training loop resumes here and the other way round
-    (`torch.optim.Adam(model.parameters()).load_state_dict(trainer.state_dict())`)."""
+    """A flat fp32 buffer trained by one fused Adam launch (ops.adam_step): the moments `m` / `v`, the step count `t`, `lr` / `betas` /
+    `eps` (plain attributes, read at step time), the device step / lr words of a captured step, and the checkpoint of all that in
+    torch.optim.Adam's `state_dict()` layout -- what the reference stores next to the weights (s-nerf/train.py:264-273 'optimzer',
+    resumed at utils/model_utils.py:44-63; zipnerf/train.py:432-440 'optimizer', internal/checkpoints.py:52-54): a checkpoint written by
+    the reference's training loop resumes here and the other way round
+    (`torch.optim.Adam(model.parameters()).load_state_dict(trainer.state_dict())`).
+    The class that trains a buffer supplies `_buffers()` -> (parameters, gradients), `_layout()` -> [(name, offset, count, shape)] of the
+    parameters in the buffer, and `what`, the buffer's name in messages."""
+    step_dev = lr_dev = _graph = None               # (step_dev / lr_dev: int32 [1] / fp32 [1] on the device once a captured step holds the Adam)
 
     def _moments(self):
         return self.m, self.v
 
+    def adam(self, grad_scale, nonfinite, lo=None, hi=None, grad=None, **hygiene):
+        """the fused Adam launch over the whole buffer, or over its slice [lo, hi) with `grad` (a reduced shard) in place of the buffer's
+        own gradient slice; zeroes the gradients it read.  `hygiene`: ops.adam_step's grad_max_val / clip_coef / dropped"""
+        flat, g = self._buffers()
+        m, v = self.m, self.v
+        if lo is not None:
+            flat, g, m, v = flat[lo:hi], g[lo:hi], m[lo:hi], v[lo:hi]
+        ops.adam_step(flat, g if grad is None else grad, m, v, self.lr, self.betas[0], self.betas[1], self.eps, self.t, grad_scale=grad_scale,
+                      zero_grad=True, nonfinite=nonfinite, step_dev=self.step_dev, lr_dev=self.lr_dev, **hygiene)
+
+    def arm(self):
+        """step count and learning rate move into device memory, where a captured Adam launch reads them"""
+        self.step_dev = torch.tensor([self.t], dtype=torch.int32, device=self.m.device)
+        self.lr_dev = torch.tensor([self.lr], dtype=torch.float32, device=self.m.device)
+
+    def snapshot(self):
+        return self._buffers()[0].clone(), self.m.clone(), self.v.clone(), self.t
+
+    def restore(self, snap):
+        flat, grad = self._buffers()
+        with torch.no_grad():
+            flat.copy_(snap[0]); self.m.copy_(snap[1]); self.v.copy_(snap[2])
+            self.t = snap[3]
+            grad.zero_()
+            if self.step_dev is not None:
+                self.step_dev.fill_(self.t)
+
     def state_dict(self):
-        a = self.model.arena
         m, v = self._moments()
-        names = [n for n, _ in self.model.named_parameters()]
-        state = {}
-        for i, n in enumerate(names):
-            lo, cnt = a._offs[n]
-            state[i] = {"step": torch.tensor(float(self.t)), "exp_avg": m[lo:lo + cnt].view(a.shapes[n]).clone(),
-                        "exp_avg_sq": v[lo:lo + cnt].view(a.shapes[n]).clone()}
+        layout = self._layout()
+        state = {i: {"step": torch.tensor(float(self.t)), "exp_avg": m[lo:lo + cnt].view(shape).clone(), "exp_avg_sq": v[lo:lo + cnt].view(shape).clone()}
+                 for i, (_, lo, cnt, shape) in enumerate(layout)}
         group = {"lr": self.lr, "betas": tuple(self.betas), "eps": self.eps, "weight_decay": 0, "amsgrad": False, "maximize": False,
-                 "foreach": None, "capturable": False, "differentiable": False, "fused": None, "params": list(range(len(names)))}
-        sd = {"state": state, "param_groups": [group], "param_names": names}
-        if getattr(self, "scaler", None) is not None:
-            sd["loss_scaler"] = self.scaler.state_dict()
-        elif getattr(self, "loss_scale", None) is not None:
-            sd["static_loss_scale"] = float(self.loss_scale)
+                 "foreach": None, "capturable": False, "differentiable": False, "fused": None, "params": list(range(len(layout)))}
+        return {"state": state, "param_groups": [group]}
+
+    def load_state_dict(self, sd):
+        """every check comes before the first write: a refused state leaves the moments, t, lr / betas / eps and the device step word alone"""
+        layout = self._layout()
+        groups = sd["param_groups"]
+        order = [i for g in groups for i in g["params"]]
+        if len(order) != len(layout):
+            raise ValueError(f"{self.what} optimizer state for {len(order)} parameters, {len(layout)} expected ({', '.join(n for n, *_ in layout)})")
+        hyper = lambda g: (float(g["lr"]), tuple(float(b) for b in g["betas"]), float(g["eps"]))
+        lr, betas, eps = hyper(groups[0])
+        if any(hyper(g) != (lr, betas, eps) for g in groups[1:]):   # one launch, one set of hyper-parameters
+            raise ValueError(f"the fused Adam launch covers the {self.what} parameters with one lr / betas / eps: the saved param_groups differ")
+        if any(float(g.get("weight_decay", 0) or 0) != 0 or g.get("amsgrad", False) for g in groups):
+            raise ValueError("the fused Adam launch has no weight decay / amsgrad")
+        if (self.step_dev is not None or self._graph is not None) and (betas, eps) != (tuple(float(b) for b in self.betas), float(self.eps)):
+            # betas / eps are host kernel arguments baked into the captured hipGraph (lr and the step count live on the device)
+            raise ValueError("load_state_dict after capture(): the checkpoint's betas / eps differ from the captured step's -- load before capturing")
+        saved, steps = [], set()
+        for pos, (name, _, _, shape) in zip(order, layout):
+            st = sd["state"].get(pos, sd["state"].get(str(pos)))    # (None: a parameter the saved optimizer never stepped)
+            if st is not None:
+                for key in ("exp_avg", "exp_avg_sq"):
+                    if tuple(st[key].shape) != tuple(shape):
+                        raise ValueError(f"{self.what} optimizer state of {name}: {key} has shape {tuple(st[key].shape)}, the parameter has {tuple(shape)}")
+                steps.add(int(float(st["step"])))
+            saved.append(st)
+        if len(steps) > 1:
+            raise ValueError(f"one Adam launch covers the {self.what} parameters: the saved parameters disagree on the step count ({sorted(steps)})")
+        with torch.no_grad():
+            for st, (_, lo, cnt, _) in zip(saved, layout):
+                for buf, key in ((self.m, "exp_avg"), (self.v, "exp_avg_sq")):
+                    if st is None:
+                        buf[lo:lo + cnt].zero_()
+                    else:
+                        buf[lo:lo + cnt].copy_(st[key].reshape(-1).to(buf.device, torch.float32))
+        self.t = steps.pop() if steps else 0
+        self.lr, self.betas, self.eps = lr, betas, eps
+        if self.step_dev is not None:
+            self.step_dev.fill_(self.t)
+
+
+class _ArenaAdam(_AdamState):
+    """_AdamState over a model's flat arena, in the order of `model.parameters()`: what MipTrainer and ZipTrainer share.  The checkpoint
+    also names the parameters (`param_names`) and is refused for a model with other names."""
+    what = "model"
+    side = ()                                       # (the side tables trained beside the model: MipTrainer's)
+    _step_dev, _lr_dev = property(lambda self: self.step_dev), property(lambda self: self.lr_dev)
+
+    def _arena_buffers(self, model, lr, betas, eps, nonfinite, grad_max_val, grad_max_norm, process_group):
+        self.model, self.lr, self.betas, self.eps = model, lr, betas, eps
+        self.nonfinite, self.grad_max_val, self.grad_max_norm = nonfinite, float(grad_max_val), float(grad_max_norm)
+        self.m, self.v, self.t = torch.zeros_like(model.arena.flat), torch.zeros_like(model.arena.flat), 0
+        self.pg = process_group
+        self.world = dist.get_world_size(process_group) if (dist.is_available() and dist.is_initialized()) else 1
+        model.arena.grad.zero_()
+
+    def _buffers(self):
+        return self.model.arena.flat, self.model.arena.grad
+
+    def broadcast_parameters(self, src=0):
+        if self.world > 1:
+            dist.broadcast(self.model.arena.flat, src=src, group=self.pg)
+            self.model.arena.bump()
+            for table in self.side:
+                for p in table.broadcast_tensors():
+                    dist.broadcast(p, src=src, group=self.pg)
+
+    def _layout(self):
+        a = self.model.arena
+        return [(n, *a._offs[n], a.shapes[n]) for n, _ in self.model.named_parameters()]
+
+    def state_dict(self):
+        sd = super().state_dict()
+        sd["param_names"] = [n for n, *_ in self._layout()]
         return sd
 
     def load_state_dict(self, sd):
-        a = self.model.arena
-        names = [n for n, _ in self.model.named_parameters()]
-        groups = sd["param_groups"]
-        if sum(len(g["params"]) for g in groups) != len(names):
-            raise ValueError(f"optimizer state for {sum(len(g['params']) for g in groups)} parameters, the model has {len(names)}")
-        if "param_names" in sd and list(sd["param_names"]) != names:
+        if "param_names" in sd and list(sd["param_names"]) != [n for n, *_ in self._layout()]:
             raise ValueError("optimizer state was saved for other parameter names")
-        order = [i for g in groups for i in g["params"]]
-        steps = set()
-        with torch.no_grad():
-            for pos, n in zip(order, names):
-                lo, cnt = a._offs[n]
-                st = sd["state"].get(pos, sd["state"].get(str(pos)))
-                if st is None:                              # (a parameter the saved optimizer never stepped)
-                    self.m[lo:lo + cnt].zero_(); self.v[lo:lo + cnt].zero_()
-                    continue
-                if tuple(st["exp_avg"].shape) != tuple(a.shapes[n]):
-                    raise ValueError(f"optimizer state of {n}: shape {tuple(st['exp_avg'].shape)}, the parameter has {tuple(a.shapes[n])}")
-                self.m[lo:lo + cnt].copy_(st["exp_avg"].reshape(-1).to(self.m.device, torch.float32))
-                self.v[lo:lo + cnt].copy_(st["exp_avg_sq"].reshape(-1).to(self.v.device, torch.float32))
-                steps.add(int(float(st["step"])))
-        if len(steps) > 1:
-            raise ValueError(f"one Adam launch covers the whole arena: the saved parameters disagree on the step count ({sorted(steps)})")
-        self.t = steps.pop() if steps else 0
-        g0 = groups[0]
-        for g in groups[1:]:                                # one launch, one set of hyper-parameters
-            if (float(g["lr"]), tuple(g["betas"]), float(g["eps"])) != (float(g0["lr"]), tuple(g0["betas"]), float(g0["eps"])):
-                raise ValueError("the fused Adam launch covers the whole arena with one lr / betas / eps: the saved param_groups differ")
-        new_betas, new_eps = tuple(float(b) for b in g0["betas"]), float(g0["eps"])
-        if getattr(self, "_graph", None) is not None and (new_betas != tuple(float(b) for b in self.betas) or new_eps != float(self.eps)):
-            # betas / eps are host kernel arguments baked into the captured hipGraph (lr and the step count live on the device)
-            raise ValueError("load_state_dict after capture(): the checkpoint's betas / eps differ from the captured step's -- load before capturing")
-        self.lr, self.betas, self.eps = float(g0["lr"]), new_betas, new_eps
-        if float(g0.get("weight_decay", 0) or 0) != 0 or g0.get("amsgrad", False):
-            raise ValueError("the fused Adam launch has no weight decay / amsgrad")
-        if getattr(self, "_step_dev", None) is not None:
-            self._step_dev.fill_(self.t)
-        if getattr(self, "scaler", None) is not None and "loss_scaler" in sd:
-            self.scaler.load_state_dict(sd["loss_scaler"])
-            self.loss_scale = self.scaler.scale
-        elif getattr(self, "scaler", None) is None and "static_loss_scale" in sd and getattr(self, "loss_scale", None) is not None \
-                and float(sd["static_loss_scale"]) != float(self.loss_scale):
-            import warnings
-            warnings.warn(f"resuming with a static loss scale of {self.loss_scale:g}; the checkpoint was trained with {float(sd['static_loss_scale']):g}")
+        super().load_state_dict(sd)
+
+    def _arena_adam(self, grad_scale, **hygiene):
+        """one fused Adam launch over the flat arena; folds `grad_scale` (the data-parallel mean, the loss scale), the gradient hygiene and
+        zero_grad"""
+        a = self.model.arena
+        coef = ops.grad_clip_coef(a.grad, grad_scale, self.grad_max_norm) if self.grad_max_norm > 0 else None
+        self.adam(grad_scale, self.nonfinite, grad_max_val=self.grad_max_val, clip_coef=coef, **hygiene)
+        a.bump()
 
 
-class _PoseAdam:
+class _SideTable(_AdamState):
+    """A small table of per-image parameters that MipTrainer trains beside the model, with an Adam of its own: `flat` with a gradient
+    buffer `grad` and the moments in its layout.  Dense over the whole table like torch.optim.Adam: an entry visited earlier keeps
+    moving on its momentum, an entry never visited has m = v = 0 and stays put exactly.  The module must stay where the trainer put it:
+    a later `.to(...)` / `.float()` that reallocates its parameters would cut them off from `flat` (`check_views` raises then, before a
+    step trains a table the module no longer sees).  A table supplies `ws_need` (its gradient kernel's fp64 scratch for n rays) and,
+    where a rank needs more of it than `flat`, `broadcast_tensors`."""
+
+    def _table_buffers(self, lr, betas, eps):
+        self.grad, self.m, self.v = torch.zeros_like(self.flat), torch.zeros_like(self.flat), torch.zeros_like(self.flat)
+        self.lr, self.betas, self.eps, self.t = float(lr), tuple(betas), float(eps), 0
+        self._ws = None
+
+    def _buffers(self):
+        return self.flat, self.grad
+
+    def check_views(self):
+        for n, lo, _, _ in self._layout():
+            if getattr(self.net, n).data_ptr() != self.flat.data_ptr() + 4 * lo:
+                raise RuntimeError(f"{self.what}: the module's {n} no longer lives in the trainer's flat {self.what} buffer (was the module moved or "
+                                   "cast after MipTrainer took it?)")
+
+    def broadcast_tensors(self):
+        return [self.flat]
+
+    def workspace(self, n):
+        """fp64 scratch of the table's gradient kernel for n rays, kept between steps"""
+        need = self.ws_need(n)
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = torch.empty(need, dtype=torch.float64, device=self.flat.device)
+        return self._ws
+
+    def train(self, world, group, nonfinite):
+        """the table's Adam step (after the model's): the ranks' table gradients are summed like the model's, 1 / world folded in"""
+        if world > 1:
+            dist.all_reduce(self.grad, op=dist.ReduceOp.SUM, group=group)
+        self.t += 1
+        self.adam(1.0 / world, nonfinite)
+
+
+class _PoseAdam(_SideTable):
     """The learned camera poses of a trainer (poses.LearnPose) and their Adam (utils/model_utils.py:36-42: its own optimiser, lr 1e-4) on
     the device: the trained parameters -- `r`, then `t` when it is trained -- are moved into one flat fp32 buffer (the module's
-    parameters become views of it, so `pose_net.state_dict()` / `load_state_dict()` keep working), with a gradient buffer and two moment
-    buffers of the same layout; one ops.adam_step covers them.  Dense over the whole table like torch.optim.Adam: a row visited earlier
-    keeps moving on its momentum, a row never visited has m = v = 0 and stays put exactly.  State in the layout of
-    torch.optim.Adam([{'params': [...], 'lr': 1e-4}]).state_dict(): the `optimizer` entry of the reference's pose/NNNNNN.tar.
-    The module must stay where the trainer put it: a later `pose_net.to(...)` / `.float()` that reallocates its parameters would cut
-    them off from the flat buffer (`check_views` raises then, before a step trains a table the module no longer sees)."""
-    what = "pose"                                   # (names the table in the messages of load_state_dict; _ConfAdam shares them)
+    parameters become views of it, so `pose_net.state_dict()` / `load_state_dict()` keep working).  State in the layout of
+    torch.optim.Adam([{'params': [...], 'lr': 1e-4}]).state_dict(): the `optimizer` entry of the reference's pose/NNNNNN.tar."""
+    what = "pose"
 
     def __init__(self, pose_net, device, lr, betas, eps):
         self.net = pose_net
@@ -172,7 +273,7 @@ class _PoseAdam:
                 raise ValueError(f"pose_net.{n}: fp32 [num_cams, 3] expected")
         k = 3 * pose_net.num_cams
         self.flat = torch.zeros(k * len(self.names), dtype=torch.float32, device=device)
-        self.grad, self.m, self.v = torch.zeros_like(self.flat), torch.zeros_like(self.flat), torch.zeros_like(self.flat)
+        self._table_buffers(lr, betas, eps)
         self.g = {}
         for i, n in enumerate(self.names):
             p = getattr(pose_net, n)
@@ -180,86 +281,23 @@ class _PoseAdam:
             view.copy_(p.data)
             p.data = view
             self.g[n] = self.grad[i * k:(i + 1) * k].view(-1, 3)
-        self.lr, self.betas, self.eps, self.t = float(lr), tuple(betas), float(eps), 0
-        self.step_dev = self.lr_dev = None
-        self._ws = None
 
-    def check_views(self):
+    def _layout(self):
         k = 3 * self.net.num_cams
-        for i, n in enumerate(self.names):
-            if getattr(self.net, n).data_ptr() != self.flat.data_ptr() + 4 * i * k:
-                raise RuntimeError(f"pose_net.{n} no longer lives in the trainer's flat pose buffer (was the module moved or cast after MipTrainer took it?)")
+        return [(n, i * k, k, self.shape) for i, n in enumerate(self.names)]
 
-    def workspace(self, n):
-        """fp64 scratch of ops.pose_grad for n rays, kept between steps"""
-        need = ops.pose_grad_ws(n)
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty(need, dtype=torch.float64, device=self.flat.device)
-        return self._ws
+    def ws_need(self, n):
+        return ops.pose_grad_ws(n)
 
-    def snapshot(self):
-        return self.flat.clone(), self.m.clone(), self.v.clone(), self.t
-
-    def restore(self, snap):
-        with torch.no_grad():
-            self.flat.copy_(snap[0]); self.m.copy_(snap[1]); self.v.copy_(snap[2])
-            self.t = snap[3]
-            self.grad.zero_()
-            if self.step_dev is not None:
-                self.step_dev.fill_(self.t)
-
-    def step(self, world, nonfinite):
-        """one fused Adam launch over the trained pose parameters; folds the data-parallel mean and zeroes the gradient buffer"""
-        ops.adam_step(self.flat, self.grad, self.m, self.v, self.lr, self.betas[0], self.betas[1], self.eps, self.t, grad_scale=1.0 / world,
-                      zero_grad=True, nonfinite=nonfinite, step_dev=self.step_dev, lr_dev=self.lr_dev)
-
-    def state_dict(self):
-        k = self.shape[0] * self.shape[1]
-        state = {i: {"step": torch.tensor(float(self.t)), "exp_avg": self.m[i * k:(i + 1) * k].view(self.shape).clone(),
-                     "exp_avg_sq": self.v[i * k:(i + 1) * k].view(self.shape).clone()} for i in range(len(self.names))}
-        group = {"lr": self.lr, "betas": tuple(self.betas), "eps": self.eps, "weight_decay": 0, "amsgrad": False, "maximize": False,
-                 "foreach": None, "capturable": False, "differentiable": False, "fused": None, "params": list(range(len(self.names)))}
-        return {"state": state, "param_groups": [group]}
-
-    def load_state_dict(self, sd):
-        k = self.shape[0] * self.shape[1]
-        groups = sd["param_groups"]
-        order = [i for g in groups for i in g["params"]]
-        if len(groups) != 1 or len(order) != len(self.names):
-            raise ValueError(f"{self.what} optimizer state: one param group over {len(self.names)} parameters ({', '.join(self.names)}) expected")
-        g0 = groups[0]
-        if float(g0.get("weight_decay", 0) or 0) != 0 or g0.get("amsgrad", False):
-            raise ValueError("the fused Adam launch has no weight decay / amsgrad")
-        new_betas, new_eps = tuple(float(b) for b in g0["betas"]), float(g0["eps"])
-        if self.step_dev is not None and (new_betas != tuple(float(b) for b in self.betas) or new_eps != float(self.eps)):
-            raise ValueError("load_state_dict after capture(): the checkpoint's betas / eps differ from the captured step's -- load before capturing")
-        steps = set()
-        with torch.no_grad():
-            for i, pos in enumerate(order):
-                st = sd["state"].get(pos, sd["state"].get(str(pos)))
-                if st is None:                              # (the saved optimizer never stepped)
-                    self.m[i * k:(i + 1) * k].zero_(); self.v[i * k:(i + 1) * k].zero_()
-                    continue
-                if tuple(st["exp_avg"].shape) != self.shape:
-                    raise ValueError(f"{self.what} optimizer state of {self.names[i]}: shape {tuple(st['exp_avg'].shape)}, the table has {self.shape}")
-                self.m[i * k:(i + 1) * k].copy_(st["exp_avg"].reshape(-1).to(self.m.device, torch.float32))
-                self.v[i * k:(i + 1) * k].copy_(st["exp_avg_sq"].reshape(-1).to(self.v.device, torch.float32))
-                steps.add(int(float(st["step"])))
-        if len(steps) > 1:
-            raise ValueError(f"one Adam launch covers the {self.what} parameters: the saved parameters disagree on the step count ({sorted(steps)})")
-        self.t = steps.pop() if steps else 0
-        self.lr, self.betas, self.eps = float(g0["lr"]), new_betas, new_eps
-        if self.step_dev is not None:
-            self.step_dev.fill_(self.t)
+    def broadcast_tensors(self):
+        """the whole table: an untrained t (learn_t=False) is applied to the rays all the same"""
+        return [self.net.r.data, self.net.t.data]
 
 
-class _ConfAdam(_PoseAdam):
+class _ConfAdam(_SideTable):
     """The learned depth confidence of a trainer (confidence.Confidence + confidence.ConfidenceMaps) and its Adam (model/confidence.py:182-184:
-    its own optimiser, lr 1e-3) on the device: the flat buffer is `lambdas` itself (moved to the device once), with a gradient buffer and
-    two moment buffers of its shape; one ops.adam_step covers the table.  Dense over the whole table like torch.optim.Adam: a column
-    visited earlier keeps moving on its momentum, a column never visited has m = v = 0 and stays put exactly.  State in the layout of
-    torch.optim.Adam([{'params': [lambdas], 'lr': 1e-3}]).state_dict(): the `optimizer_conf` entry of the reference's checkpoint
-    (_PoseAdam's code, over the one parameter).  The module must stay where the trainer put it (`check_views`, as for the pose table)."""
+    its own optimiser, lr 1e-3) on the device: the flat buffer is `lambdas` itself (moved to the device once).  State in the layout of
+    torch.optim.Adam([{'params': [lambdas], 'lr': 1e-3}]).state_dict(): the `optimizer_conf` entry of the reference's checkpoint."""
     what = "confidence"
 
     def __init__(self, conf_net, maps, device, lr, betas, eps):
@@ -272,22 +310,14 @@ class _ConfAdam(_PoseAdam):
         self.maps = maps.for_model(conf_net).to(device)
         self.names, self.shape = ["lambdas"], tuple(p.shape)
         self.flat = p.data.view(-1)
-        self.grad, self.m, self.v = torch.zeros_like(self.flat), torch.zeros_like(self.flat), torch.zeros_like(self.flat)
+        self._table_buffers(lr, betas, eps)
         self.g = self.grad.view(p.shape)
-        self.lr, self.betas, self.eps, self.t = float(lr), tuple(betas), float(eps), 0
-        self.step_dev = self.lr_dev = None
-        self._ws = None
 
-    def check_views(self):
-        if self.net.lambdas.data_ptr() != self.flat.data_ptr():
-            raise RuntimeError("conf_net.lambdas no longer lives where the trainer trains it (was the module moved or cast after MipTrainer took it?)")
+    def _layout(self):
+        return [("lambdas", 0, self.flat.numel(), self.shape)]
 
-    def workspace(self, n):
-        """fp64 scratch of ops.conf_grad for n rays, kept between steps"""
-        need = ops.conf_grad_ws(n)
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty(need, dtype=torch.float64, device=self.flat.device)
-        return self._ws
+    def ws_need(self, n):
+        return ops.conf_grad_ws(n)
 
     def apply(self, img, coords):
         """-> the confidence of the rays at pixels coords of image img, [n]"""
@@ -298,6 +328,7 @@ class _ConfAdam(_PoseAdam):
         """d loss / d conf [n] into the gradient buffer's column of image img"""
         m = self.maps
         ops.conf_grad(m.maps, m.slot_of_image, self.net.lambdas.data, m.sky, img, coords, g_conf, self.g, ws=self.workspace(coords.shape[0]))
+
 
 
 class MipLossRules:
@@ -343,7 +374,7 @@ class MipLossRules:
         return self._dev[key]
 
 
-class MipTrainer(_AdamState):
+class MipTrainer(_ArenaAdam):
     rules = None                                     # (class default: loss_and_grads also serves trainers assembled without __init__)
     smooth_patch_sz = None
 
@@ -369,20 +400,11 @@ class MipTrainer(_AdamState):
         `smooth_patch_sz` (configs: smooth_loss = True; arg_parser's patch_sz; None = off): the edge-aware smoothness of depth patches
         (train.py:154-177) joins the step -- see `step`'s `n_rgb`.  `smooth_lambda`: its weight (arg_parser's smooth_lambda);
         `smooth_skymask`: edges whose left / top pixel is sky count twice (SmoothLoss's use_skymask), `step` then needs `smooth_sky`."""
-        self.model = model
-        self.lr, self.betas, self.eps = lr, betas, eps
-        self.nonfinite, self.grad_max_val, self.grad_max_norm = nonfinite, float(grad_max_val), float(grad_max_norm)
+        self._arena_buffers(model, lr, betas, eps, nonfinite, grad_max_val, grad_max_norm, process_group)
         self.depth_lambda, self.coarse_depth_mult = depth_lambda, coarse_depth_mult
         self.proposal_loss, self.proposal_lambda, self.disparity_depth = proposal_loss, proposal_lambda, disparity_depth
         a = model.arena
-        self.m = torch.zeros_like(a.flat)
-        self.v = torch.zeros_like(a.flat)
-        self.t = 0
-        self.pg = process_group
-        self.world = dist.get_world_size(process_group) if (dist.is_available() and dist.is_initialized()) else 1
         self.single_rank_exchange = bool(exchange_when_single) and dist.is_available() and dist.is_initialized()
-        self._step_dev = self._lr_dev = self._graph = None
-        a.grad.zero_()
         self.pose = None if pose_net is None else _PoseAdam(pose_net, a.flat.device, pose_lr, pose_betas, pose_eps)
         self.semantic_lambda, self.rules = float(semantic_lambda), loss_rules
         self._rule_tables = None if loss_rules is None else loss_rules.on(a.flat.device)
@@ -391,22 +413,13 @@ class MipTrainer(_AdamState):
         if (conf_net is None) != (conf_maps is None):
             raise ValueError("MipTrainer: conf_net= and conf_maps= go together (the learned weights and the maps they mix)")
         self.conf = None if conf_net is None else _ConfAdam(conf_net, conf_maps, a.flat.device, conf_lr, conf_betas, conf_eps)
+        self.side = [x for x in (self.pose, self.conf) if x is not None]      # the side tables there are, in the order of their Adam launches
         self.smooth_patch_sz = None if smooth_patch_sz is None else int(smooth_patch_sz)
         if self.smooth_patch_sz is not None and not 2 <= self.smooth_patch_sz <= 32:
             raise ValueError("MipTrainer: smooth_patch_sz in 2..32 (one workgroup lane per patch pixel)")
         self.smooth_lambda, self.smooth_skymask = float(smooth_lambda), bool(smooth_skymask)
         self.last_smooth_loss = None
         self._smooth_bufs = {}                       # the trainer's own depth targets / labels / scratch of the smooth term, by shape
-
-    def broadcast_parameters(self, src=0):
-        if self.world > 1:
-            dist.broadcast(self.model.arena.flat, src=src, group=self.pg)
-            self.model.arena.bump()
-            if self.pose is not None:                    # the whole table: an untrained t (learn_t=False) is applied to the rays all the same
-                for p in (self.pose.net.r, self.pose.net.t):
-                    dist.broadcast(p.data, src=src, group=self.pg)
-            if self.conf is not None:
-                dist.broadcast(self.conf.flat, src=src, group=self.pg)
 
     def pose_state_dict(self):
         """the pose optimiser's state in torch.optim.Adam's layout (the `optimizer` entry of the reference's pose/NNNNNN.tar; the table
@@ -416,13 +429,6 @@ class MipTrainer(_AdamState):
     def load_pose_state_dict(self, sd):
         self.pose.load_state_dict(sd)
 
-    def _pose_adam(self):
-        """the pose table's Adam step (after the model's): the rank's pose gradients are summed like the model's, 1 / world folded in"""
-        if self.world > 1:
-            dist.all_reduce(self.pose.grad, op=dist.ReduceOp.SUM, group=self.pg)
-        self.pose.t += 1
-        self.pose.step(self.world, self.nonfinite)
-
     def conf_state_dict(self):
         """the confidence optimiser's state in torch.optim.Adam's layout (the `optimizer_conf` entry of the reference's checkpoint; the
         table itself is `conf_net.state_dict()`, its `confidence` entry)"""
@@ -431,21 +437,12 @@ class MipTrainer(_AdamState):
     def load_conf_state_dict(self, sd):
         self.conf.load_state_dict(sd)
 
-    def _conf_adam(self):
-        """the confidence table's Adam step (after the model's): the ranks' table gradients are summed like the model's, 1 / world folded in"""
-        if self.world > 1:
-            dist.all_reduce(self.conf.grad, op=dist.ReduceOp.SUM, group=self.pg)
-        self.conf.t += 1
-        self.conf.step(self.world, self.nonfinite)
-
-    def _adam(self):
-        """One fused Adam launch over the flat arena; folds the data-parallel mean, the gradient hygiene and zero_grad."""
-        a = self.model.arena
-        coef = ops.grad_clip_coef(a.grad, 1.0 / self.world, self.grad_max_norm) if self.grad_max_norm > 0 else None
-        ops.adam_step(a.flat, a.grad, self.m, self.v, self.lr, self.betas[0], self.betas[1], self.eps, self.t, grad_scale=1.0 / self.world,
-                      zero_grad=True, nonfinite=self.nonfinite, grad_max_val=self.grad_max_val, clip_coef=coef,
-                      step_dev=self._step_dev, lr_dev=self._lr_dev)
-        a.bump()
+    def _update(self):
+        """the model's Adam, then the side tables'; graph mode: step counts and learning rates live on the device (capture / replay below)"""
+        self.t += 1
+        self._arena_adam(1.0 / self.world)
+        for table in self.side:
+            table.train(self.world, self.pg, self.nonfinite)
 
     def loss_and_grads(self, outs, target_rgb, target_depth, conf, target_semantic=None, sel_coords=None, img_i=None, depth_keep=None,
                        want_g_conf=False):
@@ -457,16 +454,16 @@ class MipTrainer(_AdamState):
         its four entries; `last_semantic_loss` and `last_counts` = (#depth rays, #rgb rays, #semantic rays) are device scalars too.
         `want_g_conf` (the learned confidence): the masked tail's g_conf route; `last_g_conf` [n] = d loss / d conf."""
         dist0, acc0, s0, w0, rgb1, dist1, acc1, s1, w1 = outs[:9]
-        prop = self.proposal_loss
         rules = self.rules
+        dist1, dist0 = (dist1, dist0) if target_depth is not None else (None, None)
+        hists = (s1, w1, s0, w0) if self.proposal_loss else (None, None, None, None)
+        args = (rgb1, target_rgb, dist1, dist0, target_depth, conf, *hists, self.disparity_depth, self.depth_lambda, self.coarse_depth_mult,
+                self.proposal_lambda)
         if target_semantic is not None or depth_keep is not None or rules is not None or want_g_conf:
             tables = self._rule_tables if rules is not None else (None, None, None)
             with_sem = target_semantic is not None
             out, g_rgb1, g_dist1, g_dist0, g_w0, g_sem, *g_conf = ops.mip_loss_tail_masked(
-                rgb1, target_rgb, dist1 if target_depth is not None else None, dist0 if target_depth is not None else None,
-                target_depth, conf, s1 if prop else None, w1 if prop else None, s0 if prop else None, w0 if prop else None,
-                self.disparity_depth, self.depth_lambda, self.coarse_depth_mult, self.proposal_lambda,
-                sem=outs[9] if with_sem else None, labels=target_semantic, semantic_lambda=self.semantic_lambda,
+                *args, sem=outs[9] if with_sem else None, labels=target_semantic, semantic_lambda=self.semantic_lambda,
                 rows=sel_coords if rules is not None else None, img_i=img_i if rules is not None else None,
                 rgb_row_limit=tables[0], depth_row_limit=tables[1], sem_valid=tables[2], depth_keep=depth_keep,
                 **(dict(want_g_conf=True) if want_g_conf else {}))
@@ -474,10 +471,7 @@ class MipTrainer(_AdamState):
             self.last_losses = out[:4]
             self.last_semantic_loss, self.last_counts = out[5], (out[0], out[6], out[7])
             return out[4], (g_dist0, None, g_w0, g_rgb1, g_dist1, None, None, g_sem)
-        out, g_rgb1, g_dist1, g_dist0, g_w0 = ops.mip_loss_tail(
-            rgb1, target_rgb, dist1 if target_depth is not None else None, dist0 if target_depth is not None else None,
-            target_depth, conf, s1 if prop else None, w1 if prop else None, s0 if prop else None, w0 if prop else None,
-            self.disparity_depth, self.depth_lambda, self.coarse_depth_mult, self.proposal_lambda)
+        out, g_rgb1, g_dist1, g_dist0, g_w0 = ops.mip_loss_tail(*args)
         self.last_losses = out[:4]                               # {#valid depth rays, rgb, depth, proposal}: stays on the device
         return out[4], (g_dist0, None, g_w0, g_rgb1, g_dist1, None, None)      # out[4]: their sum, formed by the same launch
 
@@ -535,12 +529,7 @@ class MipTrainer(_AdamState):
         loss, outs = self._forward_backward(rays, target_rgb, target_depth, conf, randomized, s_rand, u, ray_grads, ex, img_i,
                                             target_semantic, sel_coords, depth_keep, n_rgb, smooth_sky)
         ex.finish()
-        self.t += 1
-        self._adam()                                      # graph mode: step count and lr live on the device (capture / replay below)
-        if self.pose is not None:
-            self._pose_adam()
-        if self.conf is not None:
-            self._conf_adam()
+        self._update()
         return loss, outs
 
     def _set_viewc(self, viewc):
@@ -550,8 +539,30 @@ class MipTrainer(_AdamState):
         elif m.fn == 0 and not getattr(m, "_viewc_given", False):
             raise ValueError("MipTrainer: the model warps around a view centre (fn = 0): pass viewc= (train.py:36,112) or call model.set_viewc first")
 
-    def _tail_extras(self, n, dev, target_depth, img_i, target_semantic, sel_coords, depth_keep):
-        """checks and device forms of the masked tail's inputs -> (target_semantic, sel_coords, img_i, depth_keep)"""
+    def _batch_index(self, n, dev, img_i, sel_coords):
+        """the batch's image and pixels in the forms the step's kernels take -> (img, img_dev, coords): `img` for the pose and confidence
+        kernels (a python int stays one, a device tensor is never read on the host), `img_dev` for the rules of the loss tail (always a
+        device tensor), `coords` int64 [n, 2] on the device where the confidence or the rules look pixels up, else None"""
+        indexed = self.rules is not None or self.conf is not None
+        if self.rules is not None and (sel_coords is None or img_i is None):
+            raise ValueError("MipTrainer with loss_rules: step() needs sel_coords= and img_i= (the pixels and the image of the batch)")
+        img = img_dev = coords = None
+        if torch.is_tensor(img_i):
+            img = img_dev = img_i.to(dev)
+        elif img_i is not None:
+            img = int(img_i)
+            if self.rules is not None:                   # wrapped once per value: steps on the same image upload nothing
+                if self._img_dev is None or self._img_dev[0] != img:
+                    self._img_dev = (img, torch.tensor([img], dtype=torch.int64, device=dev))
+                img_dev = self._img_dev[1]
+        if indexed:
+            coords = sel_coords.to(dev, torch.int64).contiguous()
+            if tuple(coords.shape) != (n, 2):
+                raise ValueError("MipTrainer: sel_coords is the batcher's [n, 2] (row, col) per ray")
+        return img, img_dev, coords
+
+    def _tail_extras(self, n, dev, target_depth, target_semantic, depth_keep):
+        """checks and device forms of the masked tail's per-ray inputs -> (target_semantic, depth_keep)"""
         if target_semantic is not None:
             if not getattr(self.model, "semantic", False):
                 raise ValueError("MipTrainer: target_semantic= given, but the model has no semantic head (semantic=True)")
@@ -566,18 +577,7 @@ class MipTrainer(_AdamState):
             if target_depth is None:
                 raise ValueError("MipTrainer: depth_keep= masks the depth term: it needs target_depth=")
             depth_keep = depth_keep.to(dev, torch.float32).reshape(-1).contiguous()
-        if self.rules is None:
-            return target_semantic, None, None, depth_keep
-        if sel_coords is None or img_i is None:
-            raise ValueError("MipTrainer with loss_rules: step() needs sel_coords= and img_i= (the pixels and the image of the batch)")
-        sel_coords = sel_coords.to(dev, torch.int64).contiguous()
-        if tuple(sel_coords.shape) != (n, 2):
-            raise ValueError("MipTrainer: sel_coords is the batcher's [n, 2] (row, col) per ray")
-        if not torch.is_tensor(img_i):                   # wrapped once per value: steps on the same image upload nothing
-            if self._img_dev is None or self._img_dev[0] != int(img_i):
-                self._img_dev = (int(img_i), torch.tensor([int(img_i)], dtype=torch.int64, device=dev))
-            img_i = self._img_dev[1]
-        return target_semantic, sel_coords, img_i.to(dev), depth_keep
+        return target_semantic, depth_keep
 
     def _smooth_own(self, key, src, n_rgb, fill):
         """the trainer's own copy of a per-ray target whose patch rows [n_rgb:] hold `fill` (set once, when the buffer is made); one
@@ -634,40 +634,29 @@ class MipTrainer(_AdamState):
         ps = self.pose
         cf = self.conf
         n_rgb, n_patches, smooth_sky = self._smooth_split(n, n_rgb, smooth_sky, dev)
+        for table in self.side:
+            table.check_views()
+        img, img_dev, coords = self._batch_index(n, dev, img_i, sel_coords)
         if cf is not None:
-            cf.check_views()
-            c_coords = sel_coords.to(dev, torch.int64).contiguous()
-            if tuple(c_coords.shape) != (n, 2):
-                raise ValueError("MipTrainer: sel_coords is the batcher's [n, 2] (row, col) per ray")
-            c_img = img_i.to(dev) if torch.is_tensor(img_i) else int(img_i)
-            conf = self.last_conf = cf.apply(c_img, c_coords)
-        masked = target_semantic is not None or depth_keep is not None or self.rules is not None
-        rule_img = None
-        if masked:
-            target_semantic, sel_coords, rule_img, depth_keep = self._tail_extras(n, dev, target_depth, img_i, target_semantic, sel_coords, depth_keep)
+            conf = self.last_conf = cf.apply(img, coords)
+        target_semantic, depth_keep = self._tail_extras(n, dev, target_depth, target_semantic, depth_keep)
         if n_patches > 0:                                # the depth and semantic terms leave the patch rows out
             if target_depth is not None:
                 target_depth = self._smooth_own("depth", target_depth, n_rgb, 0.0)
             if target_semantic is not None:
                 target_semantic = self._smooth_own("labels", target_semantic, n_rgb, -100)
         if ps is not None:
-            ps.check_views()
             f32 = lambda x: x.detach().to(dev, torch.float32).contiguous()
             o, d, v = f32(rays.origins), f32(rays.directions), f32(rays.viewdirs)
-            cam = img_i.to(dev) if torch.is_tensor(img_i) else int(img_i)
-            rays = rays._replace(**dict(zip(("origins", "directions", "viewdirs"), ops.pose_apply(ps.net.r.data, ps.net.t.data, cam, o, d, v))))
+            rays = rays._replace(**dict(zip(("origins", "directions", "viewdirs"), ops.pose_apply(ps.net.r.data, ps.net.t.data, img, o, d, v))))
             ray_grads = True
         ds_rand, du, noise0, noise1 = m._draws(n, randomized, dev)
         s_rand = ds_rand if s_rand is None else s_rand
         u = du if u is None else u
         outs, ctx = m._run(rays, True, False, s_rand, u.contiguous(), noise0, noise1)
-        if masked or cf is not None:
-            loss, g = self.loss_and_grads(outs, target_rgb, target_depth, conf, target_semantic, sel_coords if masked else None, rule_img,
-                                          depth_keep, want_g_conf=cf is not None)
-            if cf is not None:
-                cf.reduce(c_img, c_coords, self.last_g_conf)
-        else:
-            loss, g = self.loss_and_grads(outs, target_rgb, target_depth, conf)
+        loss, g = self.loss_and_grads(outs, target_rgb, target_depth, conf, target_semantic, coords, img_dev, depth_keep, want_g_conf=cf is not None)
+        if cf is not None:
+            cf.reduce(img, coords, self.last_g_conf)
         if n_patches > 0:
             g = self._smooth_term(outs, target_rgb, n_rgb, n_patches, smooth_sky, loss, g)
         elif self.smooth_patch_sz is not None:
@@ -675,7 +664,7 @@ class MipTrainer(_AdamState):
         self.last_ray_grads = m._backward(ctx, *g, on_done=on_done, ray_grads=ray_grads)
         if ps is not None:
             g_o, g_d, g_v = self.last_ray_grads
-            ops.pose_grad(ps.net.r.data, cam, g_o, g_d, g_v, d, v, ps.g.get("r"), ps.g.get("t"), ws=ps.workspace(n))
+            ops.pose_grad(ps.net.r.data, img, g_o, g_d, g_v, d, v, ps.g.get("r"), ps.g.get("t"), ws=ps.workspace(n))
         return loss, outs
 
     # ---- hipGraph capture of the whole step --------------------------------------------------------------------------------------
@@ -720,54 +709,48 @@ class MipTrainer(_AdamState):
         With `smooth_patch_sz` (a sample_utils.PatchRayBatcher only): the captured step takes `n_rgb` from the batcher's `n_rgb_rows`
         and, with `smooth_skymask`, the sky of the patch rows from the batcher's extra map `smooth_sky_extra`; the trainer-owned target
         copies, ops.smooth_loss and its finish launch are nodes of the graph.  Nothing on the host depends on the batch."""
-        self._set_viewc(viewc)                           # (fn = 0: the centre is a kernel argument, i.e. a constant of the captured graph)
         a = self.model.arena
         dev = a.flat.device
-        snap = (a.flat.clone(), self.m.clone(), self.v.clone(), self.t)
-        ps = self.pose
-        p_snap = None if ps is None else ps.snapshot()
-        cf = self.conf
-        c_snap = None if cf is None else cf.snapshot()
-        if self.world == 1:
-            self._step_dev = torch.tensor([self.t], dtype=torch.int32, device=dev)
-            self._lr_dev = torch.tensor([self.lr], dtype=torch.float32, device=dev)
-            if ps is not None:
-                ps.step_dev = torch.tensor([ps.t], dtype=torch.int32, device=dev)
-                ps.lr_dev = torch.tensor([ps.lr], dtype=torch.float32, device=dev)
-            if cf is not None:
-                cf.step_dev = torch.tensor([cf.t], dtype=torch.int32, device=dev)
-                cf.lr_dev = torch.tensor([cf.lr], dtype=torch.float32, device=dev)
-        self._batcher = batcher
-        target_semantic = sel_coords = depth_keep = None
-        if batcher is not None:
-            buf = batcher.buffers()
-            self.batch = batcher.view(buf)
-            rays, target_rgb, target_depth, _, _, extras = self.batch
-            conf = None if conf_extra is None else extras[conf_extra]
-            target_semantic = None if sem_extra is None else extras[sem_extra]
-            depth_keep = None if depth_keep_extra is None else extras[depth_keep_extra]
-            b_snap = (batcher.counter.clone(), batcher.step)
-            img_i = self.batch[4] if (ps is not None or self.rules is not None or cf is not None) else None
-            sel_coords = self.batch[3] if (self.rules is not None or cf is not None) else None
-        n_rgb = smooth_sky = None
+        indexed = bool(self.side) or self.rules is not None
+        # every refusal first: a refused capture leaves the trainer as it was
         if self.smooth_patch_sz is not None:
             if not getattr(batcher, "draws_patches", False) or batcher.patch_sz != self.smooth_patch_sz:
                 raise ValueError("capture() with smooth_patch_sz needs batcher= a PatchRayBatcher of that patch size: the captured step takes "
                                  "the patch rows from its buffers")
             if self.smooth_skymask != (smooth_sky_extra is not None):
                 raise ValueError("capture(): smooth_sky_extra= (the batcher's sky extra) is needed with smooth_skymask=True and only then")
-            n_rgb = batcher.n_rgb_rows
-            smooth_sky = None if smooth_sky_extra is None else extras[smooth_sky_extra][n_rgb:]
         elif smooth_sky_extra is not None:
             raise ValueError("capture(): smooth_sky_extra= given, but the smooth term is off (smooth_patch_sz=None)")
         if self.rules is not None and batcher is None:
             raise ValueError("capture() with loss_rules needs batcher=: the captured tail takes sel_coords and the image from its buffers")
-        if cf is not None and batcher is None:
+        if self.conf is not None and batcher is None:
             raise ValueError("capture() with a conf_net needs batcher=: the captured step takes sel_coords and the image from its buffers")
-        if (ps is not None or self.rules is not None or cf is not None) and not (torch.is_tensor(img_i) and img_i.is_cuda):
+        tail = dict(target_semantic=None, sel_coords=None, depth_keep=None, n_rgb=None, smooth_sky=None)
+        if batcher is not None:
+            buf = batcher.buffers()
+            batch = batcher.view(buf)
+            rays, target_rgb, target_depth, coords, img, extras = batch
+            extra = lambda i: None if i is None else extras[i]
+            conf = extra(conf_extra)
+            tail.update(target_semantic=extra(sem_extra), depth_keep=extra(depth_keep_extra))
+            img_i = img if indexed else None
+            if self.rules is not None or self.conf is not None:
+                tail.update(sel_coords=coords)
+            if self.smooth_patch_sz is not None:
+                tail.update(n_rgb=batcher.n_rgb_rows, smooth_sky=None if smooth_sky_extra is None else extras[smooth_sky_extra][batcher.n_rgb_rows:])
+        if indexed and not (torch.is_tensor(img_i) and img_i.is_cuda):
             raise ValueError("capture() with a pose_net or loss_rules: img_i= must be an int64 [1] device tensor (a python int would be frozen into the graph)")
-        args = (rays, target_rgb, target_depth, conf)
-        tail = dict(target_semantic=target_semantic, sel_coords=sel_coords, depth_keep=depth_keep, n_rgb=n_rgb, smooth_sky=smooth_sky)
+        self._set_viewc(viewc)                           # (fn = 0: the centre is a kernel argument, i.e. a constant of the captured graph)
+        trained = [self] + self.side
+        snaps = [x.snapshot() for x in trained]
+        if self.world == 1:
+            for x in trained:
+                x.arm()
+        self._batcher = batcher
+        if batcher is not None:
+            self.batch = batch
+            b_snap = (batcher.counter.clone(), batcher.step)
+        step = dict(rays=rays, target_rgb=target_rgb, target_depth=target_depth, conf=conf, randomized=randomized, img_i=img_i, **tail)
 
         def draw():
             if batcher is not None:
@@ -777,36 +760,25 @@ class MipTrainer(_AdamState):
         with torch.cuda.stream(side):                    # warm-up on a side stream
             for _ in range(warmup):
                 draw()
-                self.step(*args, randomized=randomized, img_i=img_i, **tail)
+                self.step(**step)
         torch.cuda.current_stream(dev).wait_stream(side)
-        with torch.no_grad():
-            a.flat.copy_(snap[0]); self.m.copy_(snap[1]); self.v.copy_(snap[2])
-            self.t = snap[3]
-            if self._step_dev is not None:
-                self._step_dev.fill_(self.t)
-            a.grad.zero_()
-            if batcher is not None:                      # capturing uses up no draws
-                batcher.counter.copy_(b_snap[0])
-        if ps is not None:
-            ps.restore(p_snap)
-        if cf is not None:
-            cf.restore(c_snap)
+        for x, snap in zip(trained, snaps):
+            x.restore(snap)
+        if batcher is not None:                          # capturing uses up no draws
+            batcher.counter.copy_(b_snap[0])
         a.bump()
         self._graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self._graph):
             draw()
             if self.world == 1:
-                self._graph_loss, self._graph_outs = self.step(*args, randomized=randomized, img_i=img_i, **tail)
+                self._graph_loss, self._graph_outs = self.step(**step)
             else:
-                self._graph_loss, self._graph_outs = self._forward_backward(*args, randomized, None, None, False, None, img_i, **tail)
+                self._graph_loss, self._graph_outs = self._forward_backward(s_rand=None, u=None, ray_grads=False, on_done=None, **step)
         if batcher is not None:
             batcher._step = b_snap[1]
         if self.world == 1:
-            self.t -= 1                                  # capturing records the step, it does not run it
-            if ps is not None:
-                ps.t -= 1
-            if cf is not None:
-                cf.t -= 1
+            for x in trained:
+                x.t -= 1                                 # capturing records the step, it does not run it
         return self._graph_loss
 
     def replay(self):
@@ -814,25 +786,16 @@ class MipTrainer(_AdamState):
         if getattr(self, "_batcher", None) is not None:
             self._batcher.advance_host(1)                # the graph's first node drew the batch and advanced the device counter
         if self.world == 1:
-            self._lr_dev.fill_(self.lr)                  # the graph reads the learning rate from the device
-            if self.pose is not None:
-                self.pose.lr_dev.fill_(self.pose.lr)
-                self.pose.t += 1
-            if self.conf is not None:
-                self.conf.lr_dev.fill_(self.conf.lr)
-                self.conf.t += 1
+            for x in [self] + self.side:
+                x.lr_dev.fill_(x.lr)                     # the graph reads the learning rates from the device
+            for table in self.side:
+                table.t += 1
             self._graph.replay()
             self.t += 1
-            return self._graph_loss, self._graph_outs
-        self._graph.replay()                             # forward + loss tail + backward of this rank's shard
-        ex = _GradExchange(self.model.arena, self.world, self.pg)
-        ex.finish()                                      # one all-reduce of the flat gradient arena
-        self.t += 1
-        self._adam()
-        if self.pose is not None:
-            self._pose_adam()
-        if self.conf is not None:
-            self._conf_adam()
+        else:
+            self._graph.replay()                         # forward + loss tail + backward of this rank's shard
+            _GradExchange(self.model.arena, self.world, self.pg).finish()       # one all-reduce of the flat gradient arena
+            self._update()
         return self._graph_loss, self._graph_outs
 
 
@@ -952,7 +915,7 @@ class LossScaler:
         self.growth_interval, self.good_steps, self.skipped_steps = int(d["growth_interval"]), int(d["good_steps"]), int(d.get("skipped_steps", 0))
 
 
-class ZipTrainer(_AdamState):
+class ZipTrainer(_ArenaAdam):
     """Train step of the S-NeRF++ / zipnerf background model (s-nerfpp/zipnerf/train.py hot loop :218-331: Model.forward, the loss
     terms, loss.backward(), optimizer.step()) on the flat arenas: forward, ONE fused loss-tail launch (ops.zip_loss_tail: Charbonnier
     data term, disparity-L1 depth terms, semantic NLL, anti-interlevel and distortion regularisers, with their gradients), backward
@@ -981,8 +944,7 @@ class ZipTrainer(_AdamState):
         zipnerf/train.py:336; configs.py:83-84 defaults 0 = off), folded into the Adam launch.  The reference always ends with
         param.grad.nan_to_num_(); "zero" (default) also drops +-Inf instead of mapping it to +-FLT_MAX (which would leave v = inf,
         i.e. that parameter frozen for good); "nan_to_num" reproduces the reference exactly."""
-        self.model, self.lr, self.betas, self.eps = model, lr, betas, eps
-        self.nonfinite, self.grad_max_val, self.grad_max_norm = nonfinite, float(grad_max_val), float(grad_max_norm)
+        self._arena_buffers(model, lr, betas, eps, nonfinite, grad_max_val, grad_max_norm, process_group)
         self.loss_cfg = dict(charb_padding=charb_padding)
         self.loss_cfg.update(loss_cfg or {})
         # hash-grid weight decay (train_utils.py:184-203; configs.py:74): a term on the parameters, not on the rays
@@ -991,9 +953,6 @@ class ZipTrainer(_AdamState):
         self.d_smo_mult, self.s_smo_mult = float(self.loss_cfg.pop("d_smo_mult", 0.001)), float(self.loss_cfg.pop("s_smo_mult", 0.001))
         self.last_smooth_losses, self._patch_own, self._patch_ws = None, {}, None
         a = model.arena
-        self.m, self.v, self.t = torch.zeros_like(a.flat), torch.zeros_like(a.flat), 0
-        self.pg = process_group
-        self.world = dist.get_world_size(process_group) if (dist.is_available() and dist.is_initialized()) else 1
         self.last_losses = None
         # running count of NaN / +-Inf gradient elements the Adam launches met (device int64, no host sync; read it when logging): a
         # persistently overflowing fp16 run with the static scale looks healthy otherwise -- the `nonfinite` policy drops them silently
@@ -1006,7 +965,6 @@ class ZipTrainer(_AdamState):
             self._found_inf = torch.zeros(1, dtype=torch.int32, device=a.flat.device)
         else:
             self.loss_scale = float(loss_scale) if loss_scale is not None else (4096.0 if getattr(model, "dt", None) == ops.F16 else 1.0)
-        a.grad.zero_()
         # the hash tables' gradients: "sharded" (default for N > 1) = reduce-scatter + Adam on the rank's slice + all-gather of the updated
         # parameters (_TableShards); "allreduce" = part of the bucketed all-reduce like the MLP parameters (the reference's DDP behaviour)
         if table_exchange not in ("sharded", "allreduce"):
@@ -1016,11 +974,6 @@ class ZipTrainer(_AdamState):
         if table_exchange == "sharded" and self.world > 1 and self.grad_max_norm <= 0 and \
                 all((a.span(n)[1] - a.span(n)[0]) % self.world == 0 for n in self.tables):
             self.shards = _TableShards(a, self.tables, self.world, process_group)
-
-    def broadcast_parameters(self, src=0):
-        if self.world > 1:
-            dist.broadcast(self.model.arena.flat, src=src, group=self.pg)
-            self.model.arena.bump()
 
     def _moments(self):
         """sharded table updates keep a rank's Adam moments current on its own slices only: a checkpoint gathers them (collective: every
@@ -1032,6 +985,23 @@ class ZipTrainer(_AdamState):
             self.shards.all_gather_span(m, name)
             self.shards.all_gather_span(v, name)
         return m, v
+
+    def state_dict(self):
+        sd = super().state_dict()
+        if self.scaler is not None:
+            sd["loss_scaler"] = self.scaler.state_dict()
+        else:
+            sd["static_loss_scale"] = float(self.loss_scale)
+        return sd
+
+    def load_state_dict(self, sd):
+        super().load_state_dict(sd)                    # (refuses before it writes: the scaler of a refused state stays as it was)
+        if self.scaler is not None and "loss_scaler" in sd:
+            self.scaler.load_state_dict(sd["loss_scaler"])
+            self.loss_scale = self.scaler.scale
+        elif self.scaler is None and "static_loss_scale" in sd and float(sd["static_loss_scale"]) != float(self.loss_scale):
+            import warnings
+            warnings.warn(f"resuming with a static loss scale of {self.loss_scale:g}; the checkpoint was trained with {float(sd['static_loss_scale']):g}")
 
     def _overflowed(self, a, shards):
         """dynamic loss scaling: the found-inf pass over the exchanged gradients and the scaler's update; -> True = the step is skipped
@@ -1104,28 +1074,40 @@ class ZipTrainer(_AdamState):
         m._zero_glo = bool(zero_glo)
         dev = m.arena.flat.device
         R = batch['origins'].shape[0]
-        t = targets or {}
+        n_patch, p, t = self._step_args(R, target_rgb, targets or {}, n_patch, patch_size, patch_mask, dev)
+        if draws is None:
+            draws = m._draws(R, rand, dev, sample_n)
+        levels, ctx = m._run(batch, True, float(train_frac), draws, sample_n, sample_m)
+        loss, G, g_w = self._loss_and_grads(levels, target_rgb, t, n_patch, p, patch_mask, aux_loss_fn, dev)
+        mine = self._backward(ctx, G, g_w)
+        self._update(mine)
+        return loss, levels
+
+    def _step_args(self, R, target_rgb, t, n_patch, patch_size, patch_mask, dev):
+        """checks of step's patch arguments -> (n_patch, p, the targets the loss tail sees)"""
         n_patch = int(n_patch or 0)
         if n_patch < 0 or (n_patch > 0 and patch_size is None):
             raise ValueError("n_patch: a count of patches >= 0, with patch_size")
         if n_patch == 0:
             self.last_smooth_losses = None             # (a step without patches, a rank with none: nothing stale for a logger)
-        if n_patch > 0:
-            p = int(patch_size)
-            if not 2 <= p <= 32:
-                raise ValueError(f"patch_size {p}: 2..32")
-            if n_patch * p * p > R:
-                raise ValueError(f"{n_patch} patches of {p} x {p} rays are more than the batch's {R} rows")
-            if patch_mask is not None and patch_mask.numel() != n_patch * p * p:
-                raise ValueError(f"patch_mask: one value per patch row ({n_patch * p * p}), got {patch_mask.numel()}")
-            if target_rgb.shape[0] != R:
-                raise ValueError("target_rgb: one row per ray")
-            t = self._patch_targets(t, R, n_patch * p * p, dev)
-        elif patch_mask is not None and patch_mask.numel() != 0:      # (the empty mask of a rank without patches is a plain step)
-            raise ValueError("patch_mask without n_patch")
-        if draws is None:
-            draws = m._draws(R, rand, dev, sample_n)
-        levels, ctx = m._run(batch, True, float(train_frac), draws, sample_n, sample_m)
+            if patch_mask is not None and patch_mask.numel() != 0:    # (the empty mask of a rank without patches is a plain step)
+                raise ValueError("patch_mask without n_patch")
+            return 0, None, t
+        p = int(patch_size)
+        if not 2 <= p <= 32:
+            raise ValueError(f"patch_size {p}: 2..32")
+        if n_patch * p * p > R:
+            raise ValueError(f"{n_patch} patches of {p} x {p} rays are more than the batch's {R} rows")
+        if patch_mask is not None and patch_mask.numel() != n_patch * p * p:
+            raise ValueError(f"patch_mask: one value per patch row ({n_patch * p * p}), got {patch_mask.numel()}")
+        if target_rgb.shape[0] != R:
+            raise ValueError("target_rgb: one row per ray")
+        return n_patch, p, self._patch_targets(t, R, n_patch * p * p, dev)
+
+    def _loss_and_grads(self, levels, target_rgb, t, n_patch, p, patch_mask, aux_loss_fn, dev):
+        """the fused loss tail, hash decay, the patch terms and `aux_loss_fn` -> (loss, the tail's output gradients G with the loss scale
+        in them, the three levels' weight gradients)"""
+        m = self.model
         fin = levels[2]
         with_depth = t.get("depth") is not None
         with_sem = t.get("semantic") is not None and fin.get("semantic") is not None
@@ -1162,6 +1144,11 @@ class ZipTrainer(_AdamState):
             gs = [b if (b is None or ls == 1.0) else b * ls for b in gs]
             g_w = [a if b is None else (b if a is None else a + b) for a, b in zip(g_w, gs)]
             loss = loss + aux.detach()
+        return loss, G, g_w
+
+    def _backward(self, ctx, G, g_w):
+        """the backward pass with the gradient exchange under it -> this rank's reduced table slices (_TableShards.finish), or None"""
+        m = self.model
         ex = _GradExchange(m.arena, self.world, self.pg)
         sh = self.shards
         if sh is not None:
@@ -1176,31 +1163,30 @@ class ZipTrainer(_AdamState):
             ex(prefix)
         m._backward(ctx, [(None, None, None, g_w[0]), (None, None, None, g_w[1]), (G["rgb"], G["depth"], None, g_w[2], G["semantic"])], on_done=level_done)
         ex.finish()
-        a = m.arena
-        mine = sh.finish() if sh is not None else None
+        return sh.finish() if sh is not None else None
+
+    def _update(self, mine):
+        """the overflow test of a dynamic loss scale, then Adam with the loss scale and the data-parallel mean folded in: one launch over the
+        arena, or with sharded tables (`mine`) one per table slice of this rank and one per stretch between the table spans"""
+        a, sh = self.model.arena, self.shards
         if self.scaler is not None and self._overflowed(a, mine):
-            return loss, levels
+            return
         self.t += 1
-        adam = lambda lo, hi, g=None: ops.adam_step(a.flat[lo:hi], a.grad[lo:hi] if g is None else g, self.m[lo:hi], self.v[lo:hi], self.lr, self.betas[0],
-                                                    self.betas[1], self.eps, self.t, grad_scale=1.0 / (self.world * ls), zero_grad=True,
-                                                    nonfinite=self.nonfinite, grad_max_val=self.grad_max_val, dropped=self.dropped_nonfinite)
+        grad_scale = 1.0 / (self.world * self.loss_scale)
         if sh is None:
-            coef = ops.grad_clip_coef(a.grad, 1.0 / (self.world * ls), self.grad_max_norm) if self.grad_max_norm > 0 else None
-            ops.adam_step(a.flat, a.grad, self.m, self.v, self.lr, self.betas[0], self.betas[1], self.eps, self.t,
-                          grad_scale=1.0 / (self.world * ls), zero_grad=True, nonfinite=self.nonfinite, grad_max_val=self.grad_max_val, clip_coef=coef,
-                          dropped=self.dropped_nonfinite)
-        else:
-            # tables: this rank's slice only, then the updated slices are gathered; everything between the table spans: the usual pass
-            for name, lo, hi, gshard in mine:
-                adam(lo, hi, gshard)
-            pos = 0
-            for ta, tb in sorted(a.span(n) for n in self.tables) + [(a.numel, a.numel)]:
-                if ta > pos:
-                    adam(pos, ta)
-                if tb > ta:
-                    a.grad[ta:tb].zero_()
-                pos = max(pos, tb)
-            for name in self.tables:
-                sh.all_gather_params(name)
-        m.arena.bump()
-        return loss, levels
+            self._arena_adam(grad_scale, dropped=self.dropped_nonfinite)
+            return
+        # tables: this rank's slice only, then the updated slices are gathered; everything between the table spans: the usual pass
+        hygiene = dict(grad_max_val=self.grad_max_val, dropped=self.dropped_nonfinite)
+        for name, lo, hi, gshard in mine:
+            self.adam(grad_scale, self.nonfinite, lo, hi, gshard, **hygiene)
+        pos = 0
+        for ta, tb in sorted(a.span(n) for n in self.tables) + [(a.numel, a.numel)]:
+            if ta > pos:
+                self.adam(grad_scale, self.nonfinite, pos, ta, **hygiene)
+            if tb > ta:
+                a.grad[ta:tb].zero_()
+            pos = max(pos, tb)
+        for name in self.tables:
+            sh.all_gather_params(name)
+        a.bump()

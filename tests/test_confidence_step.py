@@ -243,12 +243,41 @@ def test_trainer_argument_errors_with_a_confidence_table():
                 tr.step(rays, tgt, **kw)
         with pytest.raises(ValueError, match="batcher"):                 # the table is captured with a batcher only
             tr.capture(rays, tgt, td, img_i=torch.zeros(1, dtype=torch.int64))
+        assert tr._step_dev is None and tr.conf.step_dev is None         # a refused capture arms nothing: later eager steps count on the host
         # the optimiser state has torch.optim.Adam's layout before the first step as well
         sd = tr.conf_state_dict()
         assert sd["param_groups"][0]["lr"] == 2e-3 and sd["param_groups"][0]["params"] == [0] and float(sd["state"][0]["step"]) == 0
         opt = torch.optim.Adam([{"params": [confidence.Confidence(modes, N_IMG).lambdas], "lr": 1.0}])
         opt.load_state_dict(sd)
         assert opt.param_groups[0]["lr"] == 2e-3
+        # a refused optimiser state writes nothing: the table holds the moments of an accepted load, then refuses a wrong shape ...
+        from snerf_amd import poses
+        g = torch.Generator().manual_seed(4)
+        sd["state"][0] = {"step": torch.tensor(5.), "exp_avg": torch.randn(3, N_IMG, generator=g), "exp_avg_sq": torch.rand(3, N_IMG, generator=g)}
+        tr.load_conf_state_dict(sd)
+        assert tr.conf.t == 5 and torch.equal(tr.conf.m.view(3, N_IMG), sd["state"][0]["exp_avg"])
+        assert torch.equal(tr.conf.v.view(3, N_IMG), sd["state"][0]["exp_avg_sq"])
+        bad = tr.conf_state_dict()
+        bad["state"][0]["exp_avg"] = torch.zeros(N_IMG, 3)
+        bad["state"][0]["step"] = torch.tensor(9.)
+        with pytest.raises(ValueError):
+            tr.load_conf_state_dict(bad)
+        assert tr.conf.t == 5 and torch.equal(tr.conf.m.view(3, N_IMG), sd["state"][0]["exp_avg"])
+        assert torch.equal(tr.conf.v.view(3, N_IMG), sd["state"][0]["exp_avg_sq"])
+        # ... and the pose table (two entries) one whose entries disagree on the step count
+        tp = MipTrainer(model, pose_net=poses.LearnPose(N_IMG, True, True))
+        ok = tp.pose_state_dict()
+        for i in (0, 1):
+            ok["state"][i] = {"step": torch.tensor(3.), "exp_avg": torch.randn(N_IMG, 3, generator=g), "exp_avg_sq": torch.rand(N_IMG, 3, generator=g)}
+        tp.load_pose_state_dict(ok)
+        kept = (tp.pose.m.clone(), tp.pose.v.clone())
+        assert tp.pose.t == 3 and torch.equal(kept[0][3 * N_IMG:].view(N_IMG, 3), ok["state"][1]["exp_avg"]) and bool(kept[1].any())
+        split = tp.pose_state_dict()
+        split["state"][0]["exp_avg"] = torch.ones(N_IMG, 3)
+        split["state"][1]["step"] = torch.tensor(4.)
+        with pytest.raises(ValueError):
+            tp.load_pose_state_dict(split)
+        assert tp.pose.t == 3 and torch.equal(tp.pose.m, kept[0]) and torch.equal(tp.pose.v, kept[1])
         # a module whose parameter was reallocated after the trainer took it is refused, not trained past
         net.double()
         with pytest.raises(RuntimeError, match="no longer lives"):

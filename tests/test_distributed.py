@@ -518,18 +518,26 @@ def test_trainer_checkpoints_are_torch_adam_state_dicts():
             lo, cnt = model3.arena._offs[nme]
             assert torch.equal(tr3.m[lo:lo + cnt].view(p_.shape), opt3.state[p_]["exp_avg"])
             assert torch.equal(tr3.v[lo:lo + cnt].view(p_.shape), opt3.state[p_]["exp_avg_sq"])
+        before = (tr3.m.clone(), tr3.v.clone(), tr3.t, tr3.lr, tr3.betas, tr3.eps)
+        assert bool(before[0].any()) and bool(before[1].any())
+
+        def untouched():                                    # a refused state writes nothing
+            return torch.equal(tr3.m, before[0]) and torch.equal(tr3.v, before[1]) and (tr3.t, tr3.lr, tr3.betas, tr3.eps) == before[2:]
         bad = opt3.state_dict()
         bad["param_groups"][0]["params"] = bad["param_groups"][0]["params"][:-1]
         with pytest.raises(ValueError):
             tr3.load_state_dict(bad)
+        assert untouched()
         wd = opt3.state_dict()
         wd["param_groups"][0]["weight_decay"] = 0.1
         with pytest.raises(ValueError):
             tr3.load_state_dict(wd)
+        assert untouched()
         ps = list(model3.parameters())
         two = torch.optim.Adam([{"params": ps[:3], "lr": 1e-3}, {"params": ps[3:], "lr": 1e-4}])
         with pytest.raises(ValueError):
             tr3.load_state_dict(two.state_dict())           # two learning rates cannot ride in one launch
+        assert untouched()
         same = torch.optim.Adam([{"params": ps[:3]}, {"params": ps[3:]}], lr=2e-3)
         tr3.load_state_dict(same.state_dict())              # (never stepped: empty state -> zero moments, t = 0)
         assert tr3.t == 0 and tr3.lr == 2e-3 and not bool(tr3.m.any()) and not bool(tr3.v.any())

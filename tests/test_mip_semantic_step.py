@@ -309,6 +309,7 @@ def test_step_without_the_new_arguments_calls_the_plain_tail(monkeypatch):
             ruled.step(mipnerf.Rays(**rc), x["tgt"], sel_coords=x["sel"])
         with pytest.raises(ValueError, match="batcher"):                 # rules are captured with a batcher only
             ruled.capture(mipnerf.Rays(**rc), x["tgt"], img_i=torch.zeros(1, dtype=torch.int64))
+        assert ruled._step_dev is None                                   # a refused capture arms nothing: the steps below count on the host
         # a python int as the image is wrapped once per value
         ruled.step(mipnerf.Rays(**rc), x["tgt"], randomized=False, img_i=1, sel_coords=x["sel"])
         first = ruled._img_dev[1]
