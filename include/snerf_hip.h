@@ -912,6 +912,23 @@ int snerf_pose_grad(const float* r, int n_cams, const long* cam_dev, int cam_hos
                     void* stream);
 /* doubles of scratch snerf_pose_grad needs for n rays */
 long snerf_pose_grad_ws(long n);
+/* The learned pose COMPOSED with the initial one (test-time pose refinement, s-nerf/eval.py:77-114: rays generated from
+ * make_c2w(r, t) @ init_c2w[img]), applied to the rays of the initial pose: R as in snerf_pose_apply (double, rounded once);
+ * directions_out = R d, viewdirs_out = R v, origins_out = (R o) + t -- the camera centre turns with the rotation -- as separate fp32
+ * operations in a fixed order, not contracted; t NULL: origins_out = R o.  r = 0 with t NULL or zero returns the three inputs bit for
+ * bit.  Camera index (device or host; a device index outside the table stores nothing), pose_out, n = 0, the overlap rules and bad
+ * arguments as for snerf_pose_apply. */
+int snerf_pose_compose_apply(const float* r, const float* t, int n_cams, const long* cam_dev, int cam_host, const float* origins,
+                             const float* directions, const float* viewdirs, long n, float* origins_out, float* directions_out,
+                             float* viewdirs_out, float* pose_out, void* stream);
+/* The gradient of table row `cam` under snerf_pose_compose_apply: g_t = sum g_o and G[i][j] = sum (g_d[i] d[j] + g_v[i] v[j] +
+ * g_o[i] o[j]) with the UNtransformed origins / directions / viewdirs [n,3], summed, chained and ADDED into grad_r / grad_t (either
+ * nullable, not both) exactly as snerf_pose_grad does: doubles in an order that depends on n only, no floating-point atomics, the
+ * same bits every call.  g_o and origins are required, with or without grad_t.  ws: >= snerf_pose_grad_ws(n) doubles (there are
+ * still twelve sums).  Camera index, n = 0 and bad arguments as for snerf_pose_grad.  Linear in the rays: per-slice results add up. */
+int snerf_pose_compose_grad(const float* r, int n_cams, const long* cam_dev, int cam_host, const float* g_o, const float* g_d,
+                            const float* g_v, const float* origins, const float* directions, const float* viewdirs, long n, double* ws,
+                            long ws_doubles, float* grad_r, float* grad_t, void* stream);
 
 /* Learned depth confidence (depth_conf = True, precompute_conf = True; s-nerf/model/confidence.py:65-73,193-206) on the rays of one
  * batch: conf[r] = sum_k w_k maps[k, slot, row_r, col_r] / sum_k w_k with w_k = sigmoid(lambdas[k, i]), i the image of the batch and

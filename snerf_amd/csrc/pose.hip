@@ -9,6 +9,10 @@
 // -ffp-contract=off).  At r = 0 every entry of K is a zero, so R = I exactly and the transformed rays are the inputs bit for bit.
 // The camera index comes from device memory (int64 [1], the batchers' `img` output: no host read) or from the host; an index outside the
 // table makes the kernels return without a store.
+//
+// The COMPOSED form (test-time pose refinement, s-nerf/eval.py:77-114: rays generated from make_c2w(r, t) @ init_c2w[img]) turns the
+// camera centre as well: origins' = (R o) + t on the rays of the initial pose, and the rotation's gradient gains sum g_o o^T
+// (snerf_pose_compose_apply / snerf_pose_compose_grad: the same kernels, instantiated with COMPOSE).
 #include "common.h"
 #include <math.h>
 
@@ -37,6 +41,7 @@ struct PoseApply {
   float* pose_out;                  // [3,4], nullable
 };
 
+template <bool COMPOSE>
 __global__ __launch_bounds__(256) void pose_apply_kernel(PoseApply a) {
   __shared__ float s_R[9], s_t[3];
   __shared__ int s_ok;
@@ -66,6 +71,18 @@ __global__ __launch_bounds__(256) void pose_apply_kernel(PoseApply a) {
   if (i >= a.n) return;
   const float d0 = a.d[3 * i], d1 = a.d[3 * i + 1], d2 = a.d[3 * i + 2];
   const float v0 = a.v[3 * i], v1 = a.v[3 * i + 1], v2 = a.v[3 * i + 2];
+  if constexpr (COMPOSE) {
+    const float o0 = a.o[3 * i], o1 = a.o[3 * i + 1], o2 = a.o[3 * i + 2];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const float r0 = s_R[3 * c], r1 = s_R[3 * c + 1], r2 = s_R[3 * c + 2];
+      a.d_out[3 * i + c] = (r0 * d0 + r1 * d1) + r2 * d2;
+      a.v_out[3 * i + c] = (r0 * v0 + r1 * v1) + r2 * v2;
+      const float ro = (r0 * o0 + r1 * o1) + r2 * o2;
+      a.o_out[3 * i + c] = a.t != nullptr ? ro + s_t[c] : ro;
+    }
+    return;
+  }
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
     const float r0 = s_R[3 * c], r1 = s_R[3 * c + 1], r2 = s_R[3 * c + 2];
@@ -81,9 +98,10 @@ static inline bool pose_overlap(const float* a, uintptr_t la, const float* b, ui
   return a != nullptr && b != nullptr && x < y + lb && y < x + la;
 }
 
-extern "C" int snerf_pose_apply(const float* r, const float* t, int n_cams, const long* cam_dev, int cam_host, const float* origins,
-                                const float* directions, const float* viewdirs, long n, float* origins_out, float* directions_out,
-                                float* viewdirs_out, float* pose_out, void* stream) {
+template <bool COMPOSE>
+static int pose_apply_go(const float* r, const float* t, int n_cams, const long* cam_dev, int cam_host, const float* origins,
+                         const float* directions, const float* viewdirs, long n, float* origins_out, float* directions_out,
+                         float* viewdirs_out, float* pose_out, void* stream) {
   if (n == 0) return SNERF_OK;
   if (n < 0 || n_cams < 1 || r == nullptr) return SNERF_ERR_ARG;
   if (cam_dev == nullptr && (cam_host < 0 || cam_host >= n_cams)) return SNERF_ERR_ARG;
@@ -102,8 +120,22 @@ extern "C" int snerf_pose_apply(const float* r, const float* t, int n_cams, cons
     if (pose_overlap(out[i], len, pose_out, 48)) return SNERF_ERR_ARG;
   }
   PoseApply a{r, t, n_cams, cam_dev, cam_host, origins, directions, viewdirs, n, origins_out, directions_out, viewdirs_out, pose_out};
-  hipLaunchKernelGGL(pose_apply_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(pose_apply_kernel<COMPOSE>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
   return snerf_check_launch();
+}
+
+extern "C" int snerf_pose_apply(const float* r, const float* t, int n_cams, const long* cam_dev, int cam_host, const float* origins,
+                                const float* directions, const float* viewdirs, long n, float* origins_out, float* directions_out,
+                                float* viewdirs_out, float* pose_out, void* stream) {
+  return pose_apply_go<false>(r, t, n_cams, cam_dev, cam_host, origins, directions, viewdirs, n, origins_out, directions_out, viewdirs_out,
+                              pose_out, stream);
+}
+
+extern "C" int snerf_pose_compose_apply(const float* r, const float* t, int n_cams, const long* cam_dev, int cam_host, const float* origins,
+                                        const float* directions, const float* viewdirs, long n, float* origins_out, float* directions_out,
+                                        float* viewdirs_out, float* pose_out, void* stream) {
+  return pose_apply_go<true>(r, t, n_cams, cam_dev, cam_host, origins, directions, viewdirs, n, origins_out, directions_out, viewdirs_out,
+                             pose_out, stream);
 }
 
 // ---------------------------------------------------------------------------
@@ -116,6 +148,8 @@ extern "C" int snerf_pose_apply(const float* r, const float* t, int n_cams, cons
 //   A' = (th cos th - sin th) / th^2,   B' = (th sin th - 2 (1 - cos th)) / th^3,
 // without the last term at |r| = 0 (the norm's subgradient there is 0: training starts there), rounds once to fp32 and ADDS into row
 // `cam` of grad_r / grad_t.
+// COMPOSE: the rotation reached the origins too, G[i][j] = sum ((g_d[i] d[j] + g_v[i] v[j]) + g_o[i] o[j]) with the UNtransformed o -- still
+// twelve sums, the same scratch, the same fold and chain.
 // ---------------------------------------------------------------------------
 #define POSE_MAX_BLOCKS 256
 static inline int pose_grad_blocks(long n) {
@@ -128,7 +162,8 @@ extern "C" long snerf_pose_grad_ws(long n) { return n <= 0 ? 0 : 12L * pose_grad
 struct PoseGrad {
   const float* r; int n_cams;
   const long* cam_dev; int cam_host;
-  const float *g_o, *g_d, *g_v, *d, *v;   // [n,3]; g_o nullable (no translation gradient wanted)
+  const float *g_o, *g_d, *g_v, *d, *v;   // [n,3]; g_o nullable (no translation gradient wanted; never in the composed form)
+  const float* o;                         // [n,3] untransformed origins: the composed form only
   long n;
   double* ws;                             // [12 blocks]
   int blocks;
@@ -140,6 +175,7 @@ __device__ __forceinline__ bool pose_cam(const long* cam_dev, int cam_host, int 
   return *cam >= 0 && *cam < n_cams;
 }
 
+template <bool COMPOSE>
 __global__ __launch_bounds__(256) void pose_grad_partial_kernel(PoseGrad a) {
   __shared__ double red[4][12];
   long cam;
@@ -151,6 +187,19 @@ __global__ __launch_bounds__(256) void pose_grad_partial_kernel(PoseGrad a) {
     double d[3], v[3];
 #pragma unroll
     for (int c = 0; c < 3; ++c) { d[c] = (double)a.d[3 * i + c]; v[c] = (double)a.v[3 * i + c]; }
+    if constexpr (COMPOSE) {
+      double o[3];
+#pragma unroll
+      for (int c = 0; c < 3; ++c) o[c] = (double)a.o[3 * i + c];
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const double gd = (double)a.g_d[3 * i + c], gv = (double)a.g_v[3 * i + c], go = (double)a.g_o[3 * i + c];
+#pragma unroll
+        for (int j = 0; j < 3; ++j) acc[3 * c + j] += (gd * d[j] + gv * v[j]) + go * o[j];
+        acc[9 + c] += go;
+      }
+      continue;
+    }
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
       const double gd = (double)a.g_d[3 * i + c], gv = (double)a.g_v[3 * i + c];
@@ -245,8 +294,24 @@ extern "C" int snerf_pose_grad(const float* r, int n_cams, const long* cam_dev, 
   if ((grad_r == nullptr && grad_t == nullptr) || (grad_t != nullptr && g_o == nullptr)) return SNERF_ERR_ARG;
   const int blocks = pose_grad_blocks(n);
   if (ws == nullptr || ws_doubles < 12L * blocks) return SNERF_ERR_ARG;
-  PoseGrad a{r, n_cams, cam_dev, cam_host, grad_t != nullptr ? g_o : nullptr, g_d, g_v, directions, viewdirs, n, ws, blocks, grad_r, grad_t};
-  hipLaunchKernelGGL(pose_grad_partial_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
+  PoseGrad a{r, n_cams, cam_dev, cam_host, grad_t != nullptr ? g_o : nullptr, g_d, g_v, directions, viewdirs, nullptr, n, ws, blocks, grad_r, grad_t};
+  hipLaunchKernelGGL(pose_grad_partial_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(pose_grad_finish_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, a);
+  return snerf_check_launch();
+}
+
+extern "C" int snerf_pose_compose_grad(const float* r, int n_cams, const long* cam_dev, int cam_host, const float* g_o, const float* g_d,
+                                       const float* g_v, const float* origins, const float* directions, const float* viewdirs, long n,
+                                       double* ws, long ws_doubles, float* grad_r, float* grad_t, void* stream) {
+  if (n == 0) return SNERF_OK;
+  if (n < 0 || n_cams < 1 || r == nullptr) return SNERF_ERR_ARG;
+  if (cam_dev == nullptr && (cam_host < 0 || cam_host >= n_cams)) return SNERF_ERR_ARG;
+  if (g_o == nullptr || g_d == nullptr || g_v == nullptr || origins == nullptr || directions == nullptr || viewdirs == nullptr) return SNERF_ERR_ARG;
+  if (grad_r == nullptr && grad_t == nullptr) return SNERF_ERR_ARG;
+  const int blocks = pose_grad_blocks(n);
+  if (ws == nullptr || ws_doubles < 12L * blocks) return SNERF_ERR_ARG;
+  PoseGrad a{r, n_cams, cam_dev, cam_host, g_o, g_d, g_v, directions, viewdirs, origins, n, ws, blocks, grad_r, grad_t};
+  hipLaunchKernelGGL(pose_grad_partial_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
   hipLaunchKernelGGL(pose_grad_finish_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, a);
   return snerf_check_launch();
 }

@@ -212,15 +212,20 @@ class MipNerfModel(_ArenaModule):
         raw_rgb, raw_d1, saved1 = self.nerf.forward(SKIP, CB, keep)
         return raw_rgb, raw_d1, (self.nerf.raw_sem if self.semantic else None), saved1
 
-    def _backward(self, ctx, g_dist0, g_acc0, g_w0, g_rgb1, g_dist1, g_acc1, g_w1, g_sem1=None, on_done=None, ray_grads=False):
+    def _backward(self, ctx, g_dist0, g_acc0, g_w0, g_rgb1, g_dist1, g_acc1, g_w1, g_sem1=None, on_done=None, ray_grads=False, weight_grads=True):
         """Accumulates parameter gradients into the arena.  `on_done(prefix or [prefixes])` is called as soon as the gradients of the
         parameters whose names start with a prefix are final -- the NeRF MLP's heads, then each of its trunk layers as the backward
         reaches it, then the proposal network -- and the trainer starts that block's all-reduce while the rest of the backward runs.
         `ray_grads`: also return d loss / d (origins, directions, viewdirs) [n,3] each -- the reference's pose refinement
         (utils/sample_utils.py:410-435) back-propagates through the encoders into the camera pose: the data gradient is carried one GEMM
         further to the IPE / view encodings, then through integrated_pos_enc, the contraction and its Jacobian, lift_gaussian and the
-        interval lengths (t1 - t0)|d| of the compositing.  Fence posts carry no ray gradient (level 1 is detached, mip.py:318)."""
+        interval lengths (t1 - t0)|d| of the compositing.  Fence posts carry no ray gradient (level 1 is detached, mip.py:318).
+        `weight_grads=False` (the network held fixed: test-time pose refinement, eval.py:77-114): the data path alone -- the same launches
+        in the same order, so the ray gradients carry the same bits -- and nothing that only serves a parameter gradient: no weight-gradient
+        GEMM, no bias-gradient column sum, no embedding gradient, no `on_done` call, no write into the gradient arena."""
         c = ctx
+        if not weight_grads:
+            on_done = None
         warp = None if self.fn == 1 else (self._viewc, c["far"].max().reshape(1))      # (the forward's warp argument, _run)
         g_o = g_d = g_vd = None
         if ray_grads:
@@ -243,9 +248,9 @@ class MipNerfModel(_ArenaModule):
                                   c["white"], self.rgb_padding, self.density_bias, c["w1"], c["dist1"], cc(g_rgb1), cc(g_dist1),
                                   cc(g_acc1), cc(g_w1), d_rgb, d_den, g_dirs=gdir)
             layer_done = None if on_done is None else (lambda names: on_done(["mlp." + n for n in names]))
-            ig = self.nerf.backward(d_rgb, d_den, c["saved1"], d_raw_sem, want_input_grad=ray_grads, want_cond_grad=self.encode_appearance,
-                                    on_done=layer_done)
-            if self.encode_appearance:     # d loss / d emb.weight from the condition block's gradient (its columns right of the view encoding)
+            ig = self.nerf.backward(d_rgb, d_den, c["saved1"], d_raw_sem, want_input_grad=ray_grads,
+                                    want_cond_grad=self.encode_appearance and weight_grads, on_done=layer_done, weight_grads=weight_grads)
+            if self.encode_appearance and weight_grads:     # d loss / d emb.weight from the condition block's gradient (its columns right of the view encoding)
                 dVc = ig[1] if ray_grads else ig
                 ops.app_embed_bwd(dVc[:, self.view_dim:], c["app"], S1, self.arena.g["emb.weight"], deterministic=getattr(self, "_deterministic", False))
             if ray_grads:
@@ -261,7 +266,7 @@ class MipNerfModel(_ArenaModule):
             ops.mip_composite_bwd(None, c["raw_d0"], c["noise0"], c["s0"], c["d"], c["near"], c["far"], self.transform_idx,
                                   c["white"], self.rgb_padding, self.density_bias, c["w0"], c["dist0"], None, cc(g_dist0),
                                   cc(g_acc0), cc(g_w0), None, d_den0, g_dirs=gdir)
-            dE0 = self.prop.backward(d_den0, c["acts0"], want_input_grad=ray_grads)
+            dE0 = self.prop.backward(d_den0, c["acts0"], want_input_grad=ray_grads, weight_grads=weight_grads)
             if ray_grads:
                 eo, ed = ops.mip_encode_bwd(c["s0"], c["o"], c["d"], c["radii"], c["near"], c["far"], c["cone"], self.transform_idx, self.max_deg_point, dE0, warp=warp)
                 g_o += eo; g_d += ed + gdir
@@ -351,6 +356,13 @@ class _MipFn(torch.autograd.Function):
         if ctx.c is None:
             raise RuntimeError("MipNerfModel.forward ran without saved activations")
         m = ctx.model
+        if ctx.ray_meta is not None and not any(ctx.needs_input_grad[11:]):
+            # every parameter has requires_grad=False (a trained network held fixed while a camera pose is fitted against it, eval.py:77-114):
+            # the data path alone -- no weight gradient is formed, cloned or zeroed
+            rg = m._backward(ctx.c, g_dist0, g_acc0, g_w0, g_rgb1, g_dist1, g_acc1, g_w1, g_sem1, ray_grads=True, weight_grads=False)
+            ctx.c = None
+            rays_g = tuple(g.reshape(sh).to(device=dev, dtype=dt) for g, (sh, dt, dev) in zip(rg, ctx.ray_meta))
+            return (None,) * 8 + rays_g + (None,) * len(m._pnames)
         m.arena.grad.zero_()
         rg = m._backward(ctx.c, g_dist0, g_acc0, g_w0, g_rgb1, g_dist1, g_acc1, g_w1, g_sem1, ray_grads=ctx.ray_meta is not None)
         ctx.c = None

@@ -299,14 +299,20 @@ class _Net:
         """fp16 gradient GEMMs (behind the fp16 + fp8 forward, or compute="fp16" on the mip path): they run on scaled gradients (_scaled_backward)"""
         return (self.bwd_plain and self.bwd_dt == ops.F16) or self.dt == ops.F16
 
-    def _scaled_backward(self, grads, run, on_done=None):
+    def _scaled_backward(self, grads, run, on_done=None, weight_grads=True):
         """fp16 backward (behind the fp16 + fp8 forward): `grads` = the fp32 gradients entering the network (None entries allowed), `run(scaled
         grads)` the backward body.  The gradients are multiplied by S = 2^k with max |g| S in [512, 1024) -- device-side, no read-back --, the body
         accumulates S x (parameter gradients) into a zeroed scratch copy of this network's span of the gradient arena, which is then added to
-        the real one times 1 / S; tensors `run` returns (gradients w.r.t. the encodings) are scaled back too."""
+        the real one times 1 / S; tensors `run` returns (gradients w.r.t. the encodings) are scaled back too.  Without `weight_grads` the body
+        forms no parameter gradient: the scratch span is neither zeroed nor folded, the scaling of the data path is the same."""
         live = [g for g in grads if g is not None]
         amax = torch.stack([g.abs().amax() for g in live]).amax()
         S = torch.exp2(torch.floor(torch.log2(1024.0 / amax.clamp(min=1e-30)))).clamp(2.0 ** -24, 2.0 ** 40)
+        unscale = lambda t: t * inv if torch.is_tensor(t) else t
+        if not weight_grads:
+            out = run([None if g is None else g * S for g in grads])
+            inv = 1.0 / S
+            return tuple(unscale(t) for t in out) if isinstance(out, tuple) else unscale(out)
         a, b = self.a.span(self.pre)
         if getattr(self, "_gscratch", None) is None:
             self._gscratch = torch.zeros(b - a, dtype=torch.float32, device=self.dev)
@@ -322,7 +328,6 @@ class _Net:
         self.a.grad[a:b].addcmul_(self._gscratch, inv.expand_as(self._gscratch))
         if on_done is not None:
             on_done([""])
-        unscale = lambda t: t * inv if torch.is_tensor(t) else t
         return tuple(unscale(t) for t in out) if isinstance(out, tuple) else unscale(out)
 
     def _build_plan(self, fill):
@@ -450,6 +455,16 @@ class _Net:
 
     def colsum(self, x, C, out):
         ops.colsum_f32(x, C, out, deterministic=self.deterministic)
+
+    def _bias_scratch(self, widths):
+        """fp32 vectors of the given lengths for the mandatory bias-gradient outputs of the fused gradient chains in a pass without weight
+        gradients (backward(weight_grads=False)): the kernels add into them, nothing reads them, the gradient arena stays untouched"""
+        key = tuple(widths)
+        hit = self.__dict__.setdefault("_bscratch", {}).get(key)
+        if hit is None:
+            flat = torch.zeros(sum(key), dtype=torch.float32, device=self.dev)
+            hit = self._bscratch[key] = list(flat.split(list(key)))
+        return hit
 
     def ensure_packed(self, train: bool):
         # ReLU bit masks written by this forward's layers (keyed by the activation view), read by the data-gradient GEMMs
@@ -991,36 +1006,44 @@ class MipProposalNet(_Net):
         self.fwd("density", x, H, out, 1, ACT_NONE, out_f32=True)
         return out, (acts if keep else None)
 
-    def backward(self, d_raw_density, acts, want_input_grad=False):
-        """-> None, or with `want_input_grad` the fp32 gradient [M, Ew] w.r.t. the encoded samples."""
+    def backward(self, d_raw_density, acts, want_input_grad=False, weight_grads=True):
+        """-> None, or with `want_input_grad` the fp32 gradient [M, Ew] w.r.t. the encoded samples.  `weight_grads=False`: the data
+        path alone (see MipNerfNet._backward)."""
         with self._bwd():
             if self._fp16_backward():
-                return self._scaled_backward([d_raw_density], lambda g: self._backward(g[0], acts, want_input_grad))
-            return self._backward(d_raw_density, acts, want_input_grad)
+                return self._scaled_backward([d_raw_density], lambda g: self._backward(g[0], acts, want_input_grad, weight_grads),
+                                             weight_grads=weight_grads)
+            return self._backward(d_raw_density, acts, want_input_grad, weight_grads)
 
-    def _backward(self, d_raw_density, acts, want_input_grad):
+    def _backward(self, d_raw_density, acts, want_input_grad, weight_grads=True):
         H, M = self.H, d_raw_density.shape[0]
-        self.colsum(d_raw_density, 1, self.gB("density_layer"))
+        wg = weight_grads
+        gB = self.gB if wg else (lambda name: None)       # (no bias gradient: the data-gradient GEMMs run without their colsum epilogue)
+        if wg:
+            self.colsum(d_raw_density, 1, self.gB("density_layer"))
         dz = self.head_grad(d_raw_density, 1)
         xl = acts[-1][2]
-        self.wgrad("density_layer", dz, xl, 1, H)
+        if wg:
+            self.wgrad("density_layer", dz, xl, 1, H)
         cb = getattr(self, "_chain_bits", None)
         if cb is not None and cb[0] == acts[0][2].data_ptr() and self.chain_ok():
             dZs = [self.buf(M, H) for _ in range(self.L)]                 # d layers.3 .. .0 in ONE launch
             ops.fchain_bwd(ops.CHAIN_PROPOSAL, d_raw_density, self._chain_stream(), cb[1], dZs,
-                           [self.gB(f"layers.{i}.layers.0") for i in range(self.L - 1, -1, -1)])
+                           [self.gB(f"layers.{i}.layers.0") for i in range(self.L - 1, -1, -1)] if wg else self._bias_scratch([H] * self.L))
             for i in range(self.L - 1, -1, -1):
-                self.wgrad(f"layers.{i}.layers.0", dZs[self.L - 1 - i], acts[i][0], H, self.fd if i == 0 else H)
+                if wg:
+                    self.wgrad(f"layers.{i}.layers.0", dZs[self.L - 1 - i], acts[i][0], H, self.fd if i == 0 else H)
             return self.input_grad("enc", dZs[-1], H, self.Ew) if want_input_grad else None
         dZ = self.buf(M, H)
-        self.dgrad("density", dz, self.g, dZ, H, mask=xl, colsum=self.gB(f"layers.{self.L - 1}.layers.0"))
+        self.dgrad("density", dz, self.g, dZ, H, mask=xl, colsum=gB(f"layers.{self.L - 1}.layers.0"))
         for i in range(self.L - 1, -1, -1):
             x, k, y = acts[i]
             n = f"layers.{i}.layers.0"
-            self.wgrad(n, dZ, x, H, self.fd if i == 0 else H)
+            if wg:
+                self.wgrad(n, dZ, x, H, self.fd if i == 0 else H)
             if i > 0:
                 dX = self.buf(M, H)
-                self.dgrad(n, dZ, H, dX, H, mask=x, colsum=self.gB(f"layers.{i - 1}.layers.0"))
+                self.dgrad(n, dZ, H, dX, H, mask=x, colsum=gB(f"layers.{i - 1}.layers.0"))
                 dZ = dX
         return self.input_grad("enc", dZ, H, self.Ew) if want_input_grad else None
 
@@ -1186,32 +1209,47 @@ class MipNerfNet(_Net):
             self.fwd("sem1", S0, self.Hs, self.raw_sem, self.sc, ACT_NONE, out_f32=True)
         return raw_rgb, raw_d, ((acts, cacts, SKIP, CB, S0) if keep else None)
 
-    def backward(self, d_raw_rgb, d_raw_density, saved, d_raw_sem=None, want_input_grad=False, want_cond_grad=False, on_done=None):
+    def backward(self, d_raw_rgb, d_raw_density, saved, d_raw_sem=None, want_input_grad=False, want_cond_grad=False, on_done=None,
+                 weight_grads=True):
         """see _backward; under `bwd_plain` (compute="bf16x3_fwd" / "f16f8") the whole pass runs as plain bf16 / scaled fp16 launches (_Net._bwd)"""
         with self._bwd():
             if self._fp16_backward():
                 return self._scaled_backward([d_raw_rgb, d_raw_density, d_raw_sem],
-                                             lambda g: self._backward(g[0], g[1], saved, g[2], want_input_grad, want_cond_grad, None), on_done)
-            return self._backward(d_raw_rgb, d_raw_density, saved, d_raw_sem, want_input_grad, want_cond_grad, on_done)
+                                             lambda g: self._backward(g[0], g[1], saved, g[2], want_input_grad, want_cond_grad, None, weight_grads),
+                                             on_done if weight_grads else None, weight_grads=weight_grads)
+            return self._backward(d_raw_rgb, d_raw_density, saved, d_raw_sem, want_input_grad, want_cond_grad, on_done, weight_grads)
 
-    def _backward(self, d_raw_rgb, d_raw_density, saved, d_raw_sem=None, want_input_grad=False, want_cond_grad=False, on_done=None):
+    def _backward(self, d_raw_rgb, d_raw_density, saved, d_raw_sem=None, want_input_grad=False, want_cond_grad=False, on_done=None,
+                  weight_grads=True):
         """-> None, or with `want_input_grad` (dE fp32 [M, Ew], dV fp32 [M, Cw]): the gradients w.r.t. the IPE and view encodings;
         with `want_cond_grad` alone: dV (the appearance embedding's columns of the condition block need it in every training step).
         `on_done(names)`: called with a list of parameter-name prefixes (relative to this network) as soon as their gradients are final --
         the heads first, then every trunk layer right after its weight gradient -- so that a data-parallel trainer can put each block
-        on the wire while the rest of the backward pass still runs (the trunk is back-propagated last layer first)."""
+        on the wire while the rest of the backward pass still runs (the trunk is back-propagated last layer first).
+        `weight_grads=False` (a network held fixed: test-time pose refinement): the data path alone -- today's data-gradient launches in
+        today's order, so the returned gradients carry the same bits -- without any launch whose only product is a parameter gradient:
+        no weight-gradient GEMM, no column sum of a head gradient, no bias-gradient epilogue on a data-gradient GEMM, no `on_done` call;
+        nothing is written into the gradient arena.  The fused colour-head chain takes its mandatory bias-gradient outputs in scratch
+        vectors of this network (_bias_scratch)."""
+        wg = weight_grads
+        gB = self.gB if wg else (lambda name: None)       # (no bias gradient: the data-gradient GEMMs run without their colsum epilogue)
+        if not wg:
+            on_done = None
         acts, cacts, SKIP, CB, S0 = saved
         H, g, cu, M = self.H, self.g, self.cu, d_raw_rgb.shape[0]
         dV = None
         DZE = self.buf(M, H * len(self.enc_layers)) if want_input_grad else None
-        self.colsum(d_raw_rgb, 3, self.gB("rgb_layer"))
-        self.colsum(d_raw_density, 1, self.gB("density_layer"))
-        dz = self.head_grad(d_raw_rgb, 3)
+        if wg:
+            self.colsum(d_raw_rgb, 3, self.gB("rgb_layer"))
+            self.colsum(d_raw_density, 1, self.gB("density_layer"))
         fused = cacts[-1] if (len(cacts) == self.nc + 1 and cacts[-1][0] == "fused") else None
         if fused is not None:
             cacts = cacts[:-1]
         clast = cacts[-1][2]
-        self.wgrad("rgb_layer", dz, clast, 3, cu)
+        if wg or fused is None:                                     # (the fused chain reads d_raw_rgb itself: dz feeds rgb_layer's weight gradient only)
+            dz = self.head_grad(d_raw_rgb, 3)
+        if wg:
+            self.wgrad("rgb_layer", dz, clast, 3, cu)
         DB = self.buf(M, H + g + (self.Hs if self.sc else 0))       # [d bottleneck | d raw density (+pad) | d semantic hidden]
         if fused is not None:
             # the whole data-gradient chain d raw_rgb -> dC2 -> dC1 -> dC0 -> d bottleneck, masks and the four bias gradients: one launch
@@ -1219,25 +1257,27 @@ class MipNerfNet(_Net):
             dCs = [self.buf(M, cu) for _ in range(self.nc)]                       # [dC2, dC1, dC0]
             ops.fcolour_bwd(d_raw_rgb, self._cbwd[0], [cbits[2], cbits[1], cbits[0], bbits], dCs, self.cs(DB, 0, H),
                             [self.gB("cond_layers.2.layers.0"), self.gB("cond_layers.1.layers.0"), self.gB("cond_layers.0.layers.0"),
-                             self.gB("bottleneck_layer.layers.0")])
+                             self.gB("bottleneck_layer.layers.0")] if wg else self._bias_scratch([cu] * self.nc + [H]))
             for j in range(self.nc - 1, -1, -1):
                 cx, ck, cy = cacts[j]
-                self.wgrad(f"cond_layers.{j}.layers.0", dCs[self.nc - 1 - j], cx, cu, H + self.cd if j == 0 else cu)
+                if wg:
+                    self.wgrad(f"cond_layers.{j}.layers.0", dCs[self.nc - 1 - j], cx, cu, H + self.cd if j == 0 else cu)
             if want_input_grad or want_cond_grad:
                 dV = self.input_grad("cenc", dCs[-1], cu, self.Cw)
         else:
             dC = self.buf(M, cu)
-            self.dgrad("rgb", dz, g, dC, cu, mask=clast, colsum=self.gB(f"cond_layers.{self.nc - 1}.layers.0"))
+            self.dgrad("rgb", dz, g, dC, cu, mask=clast, colsum=gB(f"cond_layers.{self.nc - 1}.layers.0"))
             for j in range(self.nc - 1, -1, -1):
                 cx, ck, cy = cacts[j]
                 n = f"cond_layers.{j}.layers.0"
-                self.wgrad(n, dC, cx, cu, H + self.cd if j == 0 else cu)
+                if wg:
+                    self.wgrad(n, dC, cx, cu, H + self.cd if j == 0 else cu)
                 if j > 0:
                     dX = self.buf(M, cu)
-                    self.dgrad(n, dC, cu, dX, cu, mask=cx, colsum=self.gB(f"cond_layers.{j - 1}.layers.0"))
+                    self.dgrad(n, dC, cu, dX, cu, mask=cx, colsum=gB(f"cond_layers.{j - 1}.layers.0"))
                     dC = dX
                 else:
-                    self.dgrad(n, dC, cu, DB, H, mask=CB, colsum=self.gB("bottleneck_layer.layers.0"))
+                    self.dgrad(n, dC, cu, DB, H, mask=CB, colsum=gB("bottleneck_layer.layers.0"))
                     if want_input_grad or want_cond_grad:
                         dV = self.input_grad("cenc", dC, cu, self.Cw)
         ops.cast_pad(d_raw_density, 1, self.cs(DB, H, H + g), g, self.dt)
@@ -1248,22 +1288,27 @@ class MipNerfNet(_Net):
             if d_raw_sem is None:
                 dS0.zero_()
             else:
-                self.colsum(d_raw_sem, self.sc, self.gB("semantic_layer.1"))
+                if wg:
+                    self.colsum(d_raw_sem, self.sc, self.gB("semantic_layer.1"))
                 dzs = self.head_grad(d_raw_sem, self.sc)
-                self.wgrad("semantic_layer.1", dzs, S0, self.sc, self.Hs)
-                self.dgrad("sem1", dzs, roundup(self.sc, g), dS0, self.Hs, mask=S0, colsum=self.gB("semantic_layer.0.layers.0"))
-                self.wgrad("semantic_layer.0.layers.0", dS0, xl, self.Hs, H)
+                if wg:
+                    self.wgrad("semantic_layer.1", dzs, S0, self.sc, self.Hs)
+                self.dgrad("sem1", dzs, roundup(self.sc, g), dS0, self.Hs, mask=S0, colsum=gB("semantic_layer.0.layers.0"))
+                if wg:
+                    self.wgrad("semantic_layer.0.layers.0", dS0, xl, self.Hs, H)
             kb += self.Hs
-        self.wgrad("bottleneck_layer.layers.0", self.cs(DB, 0, H), xl, H, H)
-        self.wgrad("density_layer", self.cs(DB, H, H + g), xl, 1, H)
+        if wg:
+            self.wgrad("bottleneck_layer.layers.0", self.cs(DB, 0, H), xl, H, H)
+            self.wgrad("density_layer", self.cs(DB, H, H + g), xl, 1, H)
         dZ = self.buf(M, H)
-        self.dgrad("bd", DB, kb, dZ, H, mask=xl, colsum=self.gB(f"layers.{self.L - 1}.layers.0"))
+        self.dgrad("bd", DB, kb, dZ, H, mask=xl, colsum=gB(f"layers.{self.L - 1}.layers.0"))
         if on_done is not None:      # everything behind the trunk in the arena: density head, bottleneck, colour head (, semantic head)
             on_done(["density_layer", "bottleneck_layer", "cond_layers", "rgb_layer"] + (["semantic_layer"] if self.sc else []))
         for i in range(self.L - 1, -1, -1):
             x, k, y = acts[i]
             n = f"layers.{i}.layers.0"
-            self.wgrad(n, dZ, x, H, self.fd if i == 0 else (H + self.fd if self._is_skip_in(i) else H))
+            if wg:
+                self.wgrad(n, dZ, x, H, self.fd if i == 0 else (H + self.fd if self._is_skip_in(i) else H))
             if on_done is not None:  # weight: just now; bias: the column sums of the data gradient that produced dZ
                 on_done([f"layers.{i}."])
             if i > 0:
@@ -1273,7 +1318,7 @@ class MipNerfNet(_Net):
                     dX = self.cs(DZE, k * H, (k + 1) * H)
                 else:
                     dX = self.buf(M, H)
-                self.dgrad(n, dZ, H, dX, H, mask=xin, colsum=self.gB(f"layers.{i - 1}.layers.0"))
+                self.dgrad(n, dZ, H, dX, H, mask=xin, colsum=gB(f"layers.{i - 1}.layers.0"))
                 dZ = dX
         if want_input_grad:
             return self.input_grad("enc", DZE, H * len(self.enc_layers), self.Ew), dV

@@ -1606,6 +1606,42 @@ def pose_grad(r, cam, g_o, g_d, g_v, directions, viewdirs, grad_r, grad_t=None, 
               ws.numel(), _p(grad_r), _p(grad_t), _stream())
 
 
+def pose_compose_apply(r, t, cam, origins, directions, viewdirs, pose_out=None):
+    """snerf_pose_compose_apply: row `cam` of the LearnPose table composed with the initial pose (eval.py:88-89, make_c2w(r, t) @
+    init_c2w[img]) on the rays of the INITIAL pose -> new (R origins + t, R directions, R viewdirs); t None = no translation.  Arguments
+    as pose_apply; the inputs are left as they are (pose_compose_grad needs all three)."""
+    for x in (r, t, origins, directions, viewdirs, pose_out):
+        _f32c(x)
+    n = origins.shape[0]
+    assert r.dim() == 2 and r.shape[1] == 3 and (t is None or t.shape == r.shape)
+    assert tuple(origins.shape) == (n, 3) == tuple(directions.shape) == tuple(viewdirs.shape)
+    assert pose_out is None or pose_out.numel() == 12
+    o2, d2, v2 = torch.empty_like(origins), torch.empty_like(directions), torch.empty_like(viewdirs)
+    cam_dev, cam_host = _cam_args(cam)
+    _lib.call("snerf_pose_compose_apply", _p(r), _p(t), r.shape[0], cam_dev, cam_host, _p(origins), _p(directions), _p(viewdirs), n, _p(o2),
+              _p(d2), _p(v2), _p(pose_out), _stream())
+    return o2, d2, v2
+
+
+def pose_compose_grad(r, cam, g_o, g_d, g_v, origins, directions, viewdirs, grad_r, grad_t=None, ws=None):
+    """snerf_pose_compose_grad: pose_grad for rays moved by pose_compose_apply -- the UNtransformed origins join the reduction (the
+    rotation's gradient gains sum g_o o^T), so g_o is needed with or without grad_t.  ws: fp64 scratch of >= pose_grad_ws(n) elements."""
+    for x in (r, g_o, g_d, g_v, origins, directions, viewdirs, grad_r, grad_t):
+        _f32c(x)
+    n = g_d.shape[0]
+    assert r.dim() == 2 and r.shape[1] == 3
+    for x in (g_o, g_d, g_v, origins, directions, viewdirs):
+        assert x is not None and tuple(x.shape) == (n, 3)
+    for g in (grad_r, grad_t):
+        assert g is None or g.shape == r.shape
+    if ws is None:
+        ws = torch.empty(pose_grad_ws(n), dtype=torch.float64, device=r.device)
+    assert ws.is_cuda and ws.dtype == torch.float64 and ws.is_contiguous()
+    cam_dev, cam_host = _cam_args(cam)
+    _lib.call("snerf_pose_compose_grad", _p(r), r.shape[0], cam_dev, cam_host, _p(g_o), _p(g_d), _p(g_v), _p(origins), _p(directions),
+              _p(viewdirs), n, _p(ws), ws.numel(), _p(grad_r), _p(grad_t), _stream())
+
+
 def _conf_args(maps, slot_of_image, lambdas, sky, img, coords):
     """checks and the leading arguments shared by snerf_conf_apply / snerf_conf_grad"""
     _f32c(maps); _f32c(lambdas)

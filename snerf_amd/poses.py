@@ -7,6 +7,13 @@ who keep their own training loop (sample_utils.apply_pose_transform + MipTrainer
 through `MipTrainer(pose_net=...)`: the table row is applied to the batch by `snerf_pose_apply` and the ray gradients are reduced to
 the row's gradient by `snerf_pose_grad`; `pose_grad_chain` below is that kernel's host model in float64.
 
+That is the training-time route (sample_utils.py:421-435, transform_only=True): finished rays are moved, o + t and R d.  The test-time
+route (s-nerf/eval.py:77-114, --test_refine_iter) fits the test cameras against the trained network, which is held fixed, and generates
+its rays from make_c2w(r, t) @ init_c2w[img]: the camera centre turns with the rotation, o' = R o + t, d' = R d -- the delta applied to
+the rays of the INITIAL pose, which is what `snerf_pose_compose_apply` does; `snerf_pose_compose_grad` adds the term sum g_o o^T to the
+rotation's gradient (`pose_sums(..., origins=o)`).  `MipTrainer(pose_net=..., freeze_model=True, pose_compose=True)` is that loop on the
+device: data gradients only, no weight gradient, no arena Adam; afterwards `pose_net(i)` is the refined pose of image i.
+
 Path C's pose refinement (cal_input_grad, s-nerfpp/zipnerf/train.py:187-224) parameterises the pose differently and is not covered."""
 import torch
 import torch.nn as nn
@@ -74,8 +81,11 @@ def pose_grad_chain(r, G):
     return out
 
 
-def pose_sums(g_o, g_d, g_v, directions, viewdirs):
-    """the twelve float64 sums snerf_pose_grad forms over a batch -> (G [3,3], g_t [3])"""
+def pose_sums(g_o, g_d, g_v, directions, viewdirs, origins=None):
+    """the twelve float64 sums snerf_pose_grad forms over a batch -> (G [3,3], g_t [3]); with `origins` (the untransformed ones) those of
+    snerf_pose_compose_grad: the rotation reaches the origins too, so G gains sum g_o o^T"""
     f = lambda x: torch.as_tensor(x).detach().cpu().to(torch.float64)
     G = f(g_d).T @ f(directions) + f(g_v).T @ f(viewdirs)
+    if origins is not None:
+        G = G + f(g_o).T @ f(origins)
     return G, f(g_o).sum(0)

@@ -383,7 +383,7 @@ class MipTrainer(_ArenaAdam):
                  nonfinite="zero", grad_max_val=0.0, grad_max_norm=0.0, exchange_when_single=False,
                  pose_net=None, pose_lr=1e-4, pose_betas=(0.9, 0.999), pose_eps=1e-8, semantic_lambda=0.1, loss_rules=None,
                  conf_net=None, conf_maps=None, conf_lr=1e-3, conf_betas=(0.9, 0.999), conf_eps=1e-8,
-                 smooth_patch_sz=None, smooth_lambda=0.1, smooth_skymask=True):
+                 smooth_patch_sz=None, smooth_lambda=0.1, smooth_skymask=True, freeze_model=False, pose_compose=False):
         """`nonfinite` / `grad_max_val` / `grad_max_norm`: gradient hygiene folded into the Adam launch (ops.adam_step).  The s-nerf
         reference has none (train.py:212-215 drops into pdb on a failing backward); the default "zero" keeps one NaN / Inf gradient
         (1/(depth + eps), a bf16 overflow) from poisoning m, v and the parameters of the whole arena on every rank.  "keep" = plain Adam.
@@ -399,7 +399,20 @@ class MipTrainer(_ArenaAdam):
         lr 1e-3, no schedule).
         `smooth_patch_sz` (configs: smooth_loss = True; arg_parser's patch_sz; None = off): the edge-aware smoothness of depth patches
         (train.py:154-177) joins the step -- see `step`'s `n_rgb`.  `smooth_lambda`: its weight (arg_parser's smooth_lambda);
-        `smooth_skymask`: edges whose left / top pixel is sky count twice (SmoothLoss's use_skymask), `step` then needs `smooth_sky`."""
+        `smooth_skymask`: edges whose left / top pixel is sky count twice (SmoothLoss's use_skymask), `step` then needs `smooth_sky`.
+        `freeze_model` (needs a `pose_net`; the reference's test-time pose refinement, eval.py:77-114, --test_refine_iter): the network is
+        held fixed and only the side tables are trained -- the step is pose apply, forward, loss tail, the backward's data path alone
+        (MipNerfModel._backward(ray_grads=True, weight_grads=False): no weight-gradient GEMM, no bias-gradient sums), the pose gradient and
+        the side tables' Adam; no gradient exchange of the arena, no arena Adam, `self.t` / `self.m` / `self.v` and the arena stay as
+        they are.  world > 1: the pose gradient is still summed over the ranks.
+        `pose_compose` (with a `pose_net`): the table row is COMPOSED with the initial pose as eval.py:88-89 does
+        (make_c2w(r, t) @ init_c2w[img]) -- on the rays of the initial pose o' = R o + t, d' = R d (ops.pose_compose_apply /
+        ops.pose_compose_grad) -- where the training-time route (sample_utils.py:421-435) shifts the origins without turning them."""
+        if freeze_model and pose_net is None:
+            raise ValueError("MipTrainer: freeze_model=True trains the pose table alone: it needs pose_net=")
+        if pose_compose and pose_net is None:
+            raise ValueError("MipTrainer: pose_compose=True needs pose_net= (the table whose rows are composed with the rays' initial pose)")
+        self.freeze_model, self.pose_compose = bool(freeze_model), bool(pose_compose)
         self._arena_buffers(model, lr, betas, eps, nonfinite, grad_max_val, grad_max_norm, process_group)
         self.depth_lambda, self.coarse_depth_mult = depth_lambda, coarse_depth_mult
         self.proposal_loss, self.proposal_lambda, self.disparity_depth = proposal_loss, proposal_lambda, disparity_depth
@@ -437,10 +450,16 @@ class MipTrainer(_ArenaAdam):
     def load_conf_state_dict(self, sd):
         self.conf.load_state_dict(sd)
 
+    def _trained(self):
+        """what the step's Adam launches train, in their order: the arena (unless the model is frozen), then the side tables"""
+        return ([] if self.freeze_model else [self]) + self.side
+
     def _update(self):
-        """the model's Adam, then the side tables'; graph mode: step counts and learning rates live on the device (capture / replay below)"""
-        self.t += 1
-        self._arena_adam(1.0 / self.world)
+        """the model's Adam (unless it is frozen), then the side tables'; graph mode: step counts and learning rates live on the device
+        (capture / replay below)"""
+        if not self.freeze_model:
+            self.t += 1
+            self._arena_adam(1.0 / self.world)
         for table in self.side:
             table.train(self.world, self.pg, self.nonfinite)
 
@@ -485,6 +504,8 @@ class MipTrainer(_ArenaAdam):
         which is never read on the host); the step applies row img_i of the pose table to them (ops.pose_apply: sample_rays' pose
         branch), runs forward, loss tail and backward with ray gradients (`last_ray_grads` as above), reduces those to the row's gradient
         (ops.pose_grad) and follows the model's Adam with the pose table's -- no torch op, autograd graph or host sync in between.
+        With `pose_compose` the row is composed with the rays' initial pose instead (ops.pose_compose_apply / ops.pose_compose_grad:
+        o' = R o + t); with `freeze_model` the backward forms no weight gradient and the model's Adam is left out (see __init__).
         `target_semantic` (a model with semantic=True): per-ray labels, int32 or fp32 holding exact integers (a batcher's extras row;
         other integer types are converted), -100 = ignored; the semantic cross-entropy times `semantic_lambda` joins the loss and
         trains the semantic head (train.py:185-191).  A label outside [0, C) other than -100 is ignored as well -- the reference
@@ -523,12 +544,14 @@ class MipTrainer(_ArenaAdam):
             if target_depth is None or sel_coords is None or img_i is None:
                 raise ValueError("MipTrainer with a conf_net: step() needs target_depth=, sel_coords= and img_i= (the confidence weighs the depth term "
                                  "of the batch's pixels with the weights of its image)")
-        ex = _GradExchange(self.model.arena, self.world, self.pg, self.single_rank_exchange)
         # every block of the gradient arena goes on the wire as soon as the backward pass has finished it (heads, then trunk layer by
-        # trunk layer, then the proposal network): the collectives run under the remaining backward kernels
+        # trunk layer, then the proposal network): the collectives run under the remaining backward kernels.  A frozen model has no
+        # arena gradient to exchange (the side tables' gradients are summed by _SideTable.train)
+        ex = None if self.freeze_model else _GradExchange(self.model.arena, self.world, self.pg, self.single_rank_exchange)
         loss, outs = self._forward_backward(rays, target_rgb, target_depth, conf, randomized, s_rand, u, ray_grads, ex, img_i,
                                             target_semantic, sel_coords, depth_keep, n_rgb, smooth_sky)
-        ex.finish()
+        if ex is not None:
+            ex.finish()
         self._update()
         return loss, outs
 
@@ -648,7 +671,8 @@ class MipTrainer(_ArenaAdam):
         if ps is not None:
             f32 = lambda x: x.detach().to(dev, torch.float32).contiguous()
             o, d, v = f32(rays.origins), f32(rays.directions), f32(rays.viewdirs)
-            rays = rays._replace(**dict(zip(("origins", "directions", "viewdirs"), ops.pose_apply(ps.net.r.data, ps.net.t.data, img, o, d, v))))
+            apply = ops.pose_compose_apply if self.pose_compose else ops.pose_apply
+            rays = rays._replace(**dict(zip(("origins", "directions", "viewdirs"), apply(ps.net.r.data, ps.net.t.data, img, o, d, v))))
             ray_grads = True
         ds_rand, du, noise0, noise1 = m._draws(n, randomized, dev)
         s_rand = ds_rand if s_rand is None else s_rand
@@ -661,10 +685,13 @@ class MipTrainer(_ArenaAdam):
             g = self._smooth_term(outs, target_rgb, n_rgb, n_patches, smooth_sky, loss, g)
         elif self.smooth_patch_sz is not None:
             self.last_smooth_loss = torch.zeros((), dtype=torch.float32, device=dev)
-        self.last_ray_grads = m._backward(ctx, *g, on_done=on_done, ray_grads=ray_grads)
+        self.last_ray_grads = m._backward(ctx, *g, on_done=on_done, ray_grads=ray_grads, weight_grads=not self.freeze_model)
         if ps is not None:
             g_o, g_d, g_v = self.last_ray_grads
-            ops.pose_grad(ps.net.r.data, img, g_o, g_d, g_v, d, v, ps.g.get("r"), ps.g.get("t"), ws=ps.workspace(n))
+            if self.pose_compose:                        # (the rotation reached the origins: the untransformed ones join the reduction)
+                ops.pose_compose_grad(ps.net.r.data, img, g_o, g_d, g_v, o, d, v, ps.g.get("r"), ps.g.get("t"), ws=ps.workspace(n))
+            else:
+                ops.pose_grad(ps.net.r.data, img, g_o, g_d, g_v, d, v, ps.g.get("r"), ps.g.get("t"), ws=ps.workspace(n))
         return loss, outs
 
     # ---- hipGraph capture of the whole step --------------------------------------------------------------------------------------
@@ -695,7 +722,9 @@ class MipTrainer(_ArenaAdam):
         With a `pose_net` the captured step is the draw, ops.pose_apply fed by the batch's `img` tensor (without a batcher: `img_i`, an
         int64 [1] device tensor the caller refreshes like the rays), forward, backward with ray gradients, ops.pose_grad and both Adams
         (world > 1: both Adams and the two all-reduces follow the graph); the pose table, its moments and step count are snapshotted and
-        restored around the warm-up like the model's.
+        restored around the warm-up like the model's.  `pose_compose` swaps in ops.pose_compose_apply / ops.pose_compose_grad;
+        `freeze_model`: the captured step ends with the side tables' Adam launches -- it holds no weight-gradient GEMM and no arena Adam
+        node, and neither capture nor replay touches the arena, its moments or `self.t`.
 
         With a `conf_net` (batcher only; `conf_extra` stays None) the captured step also holds ops.conf_apply and ops.conf_grad, fed by the
         batch's `sel_coords` and `img` buffers, and the confidence table's Adam (world > 1: that Adam and its all-reduce follow the
@@ -741,7 +770,7 @@ class MipTrainer(_ArenaAdam):
         if indexed and not (torch.is_tensor(img_i) and img_i.is_cuda):
             raise ValueError("capture() with a pose_net or loss_rules: img_i= must be an int64 [1] device tensor (a python int would be frozen into the graph)")
         self._set_viewc(viewc)                           # (fn = 0: the centre is a kernel argument, i.e. a constant of the captured graph)
-        trained = [self] + self.side
+        trained = self._trained()
         snaps = [x.snapshot() for x in trained]
         if self.world == 1:
             for x in trained:
@@ -766,7 +795,8 @@ class MipTrainer(_ArenaAdam):
             x.restore(snap)
         if batcher is not None:                          # capturing uses up no draws
             batcher.counter.copy_(b_snap[0])
-        a.bump()
+        if not self.freeze_model:                        # (the restored parameters are new values to the packed operands)
+            a.bump()
         self._graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self._graph):
             draw()
@@ -786,15 +816,17 @@ class MipTrainer(_ArenaAdam):
         if getattr(self, "_batcher", None) is not None:
             self._batcher.advance_host(1)                # the graph's first node drew the batch and advanced the device counter
         if self.world == 1:
-            for x in [self] + self.side:
+            for x in self._trained():
                 x.lr_dev.fill_(x.lr)                     # the graph reads the learning rates from the device
             for table in self.side:
                 table.t += 1
             self._graph.replay()
-            self.t += 1
+            if not self.freeze_model:
+                self.t += 1
         else:
             self._graph.replay()                         # forward + loss tail + backward of this rank's shard
-            _GradExchange(self.model.arena, self.world, self.pg).finish()       # one all-reduce of the flat gradient arena
+            if not self.freeze_model:
+                _GradExchange(self.model.arena, self.world, self.pg).finish()   # one all-reduce of the flat gradient arena
             self._update()
         return self._graph_loss, self._graph_outs
 
