@@ -878,6 +878,14 @@ int snerf_adam_step_ex(float* p, float* g, float* m, float* v, long n, float lr,
 int snerf_adam_step_cnt(float* p, float* g, float* m, float* v, long n, float lr, float b1, float b2, float eps, int step,
                         int* step_dev, const float* lr_dev, float grad_scale, int zero_grad, int nonfinite, float grad_max_val,
                         const float* clip_coef, void* dropped, void* stream);
+/* Plain SGD over a flat fp32 buffer (torch.optim.SGD without momentum or weight decay: the optimiser of the reference's learned camera
+ * poses, s-nerfpp/zipnerf/internal/train_utils.py:290, stepped after clip_gradients(posenet), train.py:343):
+ * p -= lr * hygiene(g * grad_scale), then g = 0.  The hygiene, its order and the `nonfinite` codes are snerf_adam_step_ex's (clip_coef:
+ * nullable device float; grad_max_val > 0: value clip; nonfinite 0 / 1 / 2); the product lr * g and the difference are separate fp32
+ * operations.  *dropped (device uint64, 8-byte aligned, nullable) += the NaN / +-Inf gradient elements met.  count = 0 is a no-op; a
+ * null p or g, count < 0, a pointer off 4-byte alignment or a nonfinite code outside 0..2 return 1 before any launch. */
+int snerf_sgd_step(float* p, float* g, long count, float lr, float grad_scale, float grad_max_val, const float* clip_coef, int nonfinite,
+                   void* dropped, void* stream);
 /* torch.nn.utils.clip_grad_norm_ coefficient over a flat gradient arena: out[0] = min(1, max_norm / (|grad_scale| * ||g||_2 + 1e-6)),
  * out[1] = the norm.  ws: >= 1024 doubles of device scratch.  Fixed reduction order (deterministic).  A NaN in g gives out[0] = out[1]
  * = NaN (torch's clamp(max=1) keeps the NaN too): snerf_adam_step_ex then sees NaN gradients everywhere and its `nonfinite` policy decides
@@ -929,6 +937,35 @@ int snerf_pose_compose_apply(const float* r, const float* t, int n_cams, const l
 int snerf_pose_compose_grad(const float* r, int n_cams, const long* cam_dev, int cam_host, const float* g_o, const float* g_d,
                             const float* g_v, const float* origins, const float* directions, const float* viewdirs, long n, double* ws,
                             long ws_doubles, float* grad_r, float* grad_t, void* stream);
+
+/* Per-ray learned poses (path C: s-nerfpp/zipnerf/train.py:177-213, internal/posenet_v2.py): a batch mixes cameras, every ray names its
+ * row of the table.  snerf_pose_table writes table_out [n_cams,3,4], one thread per camera: the rotation of row c formed in double from
+ * the fp32 r [n_cams,3] and rounded once (as snerf_pose_apply does; r = 0 gives I exactly), column 3 = fp32(t[c] * t_ratio)
+ * (posenet_v2.py:89,99; zeros when t is NULL).  table_out must not overlap r or t.  Bad arguments (a null r or table_out, n_cams < 1,
+ * overlap) return 1 before any launch. */
+int snerf_pose_table(const float* r, const float* t, int n_cams, float t_ratio, float* table_out, void* stream);
+/* The table of snerf_pose_table (16-byte aligned) applied ray by ray (train.py:186-196): cam [n] fp32 holds each ray's row, truncated
+ * toward zero like the reference's .int(); origins_out = o + t_eff (one fp32 add), and for x in (directions, viewdirs, base_x, base_y)
+ * x'_i = (R_i0 x_0 + R_i1 x_1) + R_i2 x_2 as separate fp32 operations, not contracted.  A ray whose index is outside [0, n_cams) (or
+ * NaN) is copied through unchanged.  The inputs are never written; an output that overlaps an input, the table, cam or another output
+ * is a bad argument, like a null pointer, n < 0 or n_cams < 1 (status 1 before any launch).  n = 0 is a no-op. */
+int snerf_pose_rays_apply(const float* table, int n_cams, const float* cam, const float* origins, const float* directions,
+                          const float* viewdirs, const float* base_x, const float* base_y, long n, float* origins_out,
+                          float* directions_out, float* viewdirs_out, float* base_x_out, float* base_y_out, void* stream);
+/* doubles of scratch snerf_pose_rays_grad needs for n rays spread over a table of n_cams rows (0 for n <= 0 or n_cams < 1) */
+long snerf_pose_rays_grad_ws(long n, int n_cams);
+/* The gradient of the table under snerf_pose_rays_apply, segmented by camera: g_o .. g_by [n,3] = d loss / d the TRANSFORMED origins,
+ * directions, viewdirs, base_x, base_y, and the UNtransformed directions, viewdirs, base_x, base_y [n,3].  For every camera c that owns
+ * at least one ray, G_c[i][j] = sum over its rays of (g_d[i] d[j] + g_v[i] v[j]) + (g_bx[i] bx[j] + g_by[i] by[j]) and g_t,c = t_ratio *
+ * sum g_o, summed in double in an order that depends on (n, n_cams) only -- no floating-point atomics, the same bits every call --
+ * chained through row c of r as snerf_pose_grad chains, rounded once to fp32 and ADDED into row c of grad_r / grad_t [n_cams,3] (either
+ * nullable, not both; g_o nullable without grad_t).  Rows of cameras without a ray in the batch are not stored to; rays with an index
+ * outside the table take no part.  ws: >= snerf_pose_rays_grad_ws(n, n_cams) doubles, ws_doubles = its length (short = bad argument).
+ * n = 0 is a no-op; a null required pointer, n < 0 or n_cams < 1 return 1 before any launch.  Linear in the rays: per-slice results
+ * add up. */
+int snerf_pose_rays_grad(const float* r, int n_cams, float t_ratio, const float* cam, const float* g_o, const float* g_d, const float* g_v,
+                         const float* g_bx, const float* g_by, const float* directions, const float* viewdirs, const float* base_x,
+                         const float* base_y, long n, double* ws, long ws_doubles, float* grad_r, float* grad_t, void* stream);
 
 /* Learned depth confidence (depth_conf = True, precompute_conf = True; s-nerf/model/confidence.py:65-73,193-206) on the rays of one
  * batch: conf[r] = sum_k w_k maps[k, slot, row_r, col_r] / sum_k w_k with w_k = sigmoid(lambdas[k, i]), i the image of the batch and

@@ -132,6 +132,39 @@ extern "C" int snerf_adam_step_cnt(float* p, float* g, float* m, float* v, long 
                                              (unsigned long long*)dropped}, stream, step_dev != nullptr);
 }
 
+// Plain SGD (torch.optim.SGD without momentum or weight decay: the reference's optimiser of its learned camera poses,
+// s-nerfpp/zipnerf/internal/train_utils.py:290, after clip_gradients(posenet), train.py:343): p -= lr * hygiene(g * grad_scale), g = 0.
+// The hygiene is adam_clean_grad itself (same order, same `nonfinite` codes); the product and the difference round on their own.
+// A scalar kernel: the tables it trains have a few thousand entries.
+__global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, float* __restrict__ g, long n, AdamArgs a) {
+#pragma clang fp contract(off)
+  const float coef = a.clip_coef != nullptr ? *a.clip_coef : 1.f;
+  unsigned bad = 0;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+    bad += (fabsf(g[i]) <= 3.402823466e+38f) ? 0u : 1u;
+    const float gk = adam_clean_grad(g[i], a, coef);
+    p[i] = p[i] - a.lr * gk;
+    g[i] = 0.f;
+  }
+  if (a.dropped != nullptr && __any(bad != 0)) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) bad += __shfl_xor(bad, o);
+    if ((threadIdx.x & 63) == 0) atomicAdd(a.dropped, (unsigned long long)bad);
+  }
+}
+
+extern "C" int snerf_sgd_step(float* p, float* g, long count, float lr, float grad_scale, float grad_max_val, const float* clip_coef,
+                              int nonfinite, void* dropped, void* stream) {
+  if (count == 0) return SNERF_OK;
+  if (count < 0 || p == nullptr || g == nullptr || (((uintptr_t)p | (uintptr_t)g) & 3) || nonfinite < 0 || nonfinite > 2) return SNERF_ERR_ARG;
+  if (dropped != nullptr && ((uintptr_t)dropped & 7)) return SNERF_ERR_ARG;
+  long blocks = (count + 255) / 256;
+  blocks = blocks > 2048 ? 2048 : blocks;
+  hipLaunchKernelGGL(sgd_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, g, count,
+                     AdamArgs{lr, 0.f, 0.f, 0.f, grad_scale, grad_max_val, 1, nonfinite, nullptr, nullptr, clip_coef, 0, (unsigned long long*)dropped});
+  return snerf_check_launch();
+}
+
 // Global-norm clip coefficient of torch.nn.utils.clip_grad_norm_ (accelerator.clip_grad_norm_, train_utils.py:236-237):
 // coef = min(1, max_norm / (||grad_scale * g||_2 + 1e-6)) over the flat gradient arena.  A NaN gradient makes the norm and the
 // coefficient NaN, as torch.clamp(max=1) keeps it (fminf would return 1, i.e. switch the clip off exactly then); an Inf gives 0.

@@ -315,3 +315,196 @@ extern "C" int snerf_pose_compose_grad(const float* r, int n_cams, const long* c
   hipLaunchKernelGGL(pose_grad_finish_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, a);
   return snerf_check_launch();
 }
+
+// ---------------------------------------------------------------------------
+// Per-ray learned poses (path C: s-nerfpp/zipnerf/train.py:177-213, internal/posenet_v2.py).  A batch mixes cameras: every ray carries
+// the row of the table that moves it (batch['glo_idx']), five ray tensors turn -- directions, viewdirs, base_x, base_y get R x, origins
+// get + t -- and the translation is t * t_ratio (posenet_v2.py:89,99).  snerf_pose_table forms the [R | t * t_ratio] rows once per
+// step, snerf_pose_rays_apply gathers a ray's row, snerf_pose_rays_grad reduces the step's ray gradients camera by camera.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void pose_table_kernel(const float* __restrict__ r, const float* __restrict__ t, int n_cams, float t_ratio,
+                                                         float* __restrict__ table) {
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= n_cams) return;
+  double R[9];
+  pose_rotation(r + 3 * (long)c, R);
+  float* row = table + 12 * (long)c;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+#pragma unroll
+    for (int j = 0; j < 3; ++j) row[4 * i + j] = (float)R[3 * i + j];
+    row[4 * i + 3] = t != nullptr ? t[3 * (long)c + i] * t_ratio : 0.f;
+  }
+}
+
+extern "C" int snerf_pose_table(const float* r, const float* t, int n_cams, float t_ratio, float* table_out, void* stream) {
+  if (n_cams < 1 || r == nullptr || table_out == nullptr) return SNERF_ERR_ARG;
+  const uintptr_t len = (uintptr_t)n_cams * 12;
+  if (pose_overlap(table_out, 4 * len, r, len) || pose_overlap(table_out, 4 * len, t, len)) return SNERF_ERR_ARG;
+  hipLaunchKernelGGL(pose_table_kernel, dim3((unsigned)((n_cams + 255) / 256)), dim3(256), 0, (hipStream_t)stream, r, t, n_cams, t_ratio,
+                     table_out);
+  return snerf_check_launch();
+}
+
+// the row of a ray: its fp32 index truncated toward zero (the reference's .int()); -1 = outside the table (NaN included)
+__device__ __forceinline__ int pose_ray_cam(float c, int n_cams) { return (c > -1.f && c < (float)n_cams) ? (int)c : -1; }
+
+struct PoseRays {
+  const float* table; int n_cams;   // [n_cams,3,4]
+  const float* cam;                 // [n]
+  const float* in[5];               // origins, directions, viewdirs, base_x, base_y [n,3]
+  float* out[5];
+  long n;
+};
+
+__global__ __launch_bounds__(256) void pose_rays_apply_kernel(PoseRays a) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= a.n) return;
+  const int c = pose_ray_cam(a.cam[i], a.n_cams);
+  if (c < 0) {                                          // copied through unchanged
+#pragma unroll
+    for (int k = 0; k < 5; ++k)
+#pragma unroll
+      for (int e = 0; e < 3; ++e) a.out[k][3 * i + e] = a.in[k][3 * i + e];
+    return;
+  }
+  float T[12];
+  const float4* row = (const float4*)(a.table + 12 * (long)c);     // (rows are 48 bytes: 16-byte aligned with the table)
+#pragma unroll
+  for (int q = 0; q < 3; ++q) { const float4 w = row[q]; T[4 * q] = w.x; T[4 * q + 1] = w.y; T[4 * q + 2] = w.z; T[4 * q + 3] = w.w; }
+#pragma unroll
+  for (int e = 0; e < 3; ++e) a.out[0][3 * i + e] = a.in[0][3 * i + e] + T[4 * e + 3];
+#pragma unroll
+  for (int k = 1; k < 5; ++k) {
+    const float x0 = a.in[k][3 * i], x1 = a.in[k][3 * i + 1], x2 = a.in[k][3 * i + 2];
+#pragma unroll
+    for (int e = 0; e < 3; ++e) a.out[k][3 * i + e] = (T[4 * e] * x0 + T[4 * e + 1] * x1) + T[4 * e + 2] * x2;
+  }
+}
+
+extern "C" int snerf_pose_rays_apply(const float* table, int n_cams, const float* cam, const float* origins, const float* directions,
+                                     const float* viewdirs, const float* base_x, const float* base_y, long n, float* origins_out,
+                                     float* directions_out, float* viewdirs_out, float* base_x_out, float* base_y_out, void* stream) {
+  if (n == 0) return SNERF_OK;
+  if (n < 0 || n_cams < 1 || table == nullptr || cam == nullptr || ((uintptr_t)table & 15)) return SNERF_ERR_ARG;
+  PoseRays a{table, n_cams, cam, {origins, directions, viewdirs, base_x, base_y},
+             {origins_out, directions_out, viewdirs_out, base_x_out, base_y_out}, n};
+  // the backward needs the untransformed rays: no output may share memory with an input, the table or the indices, nor with another output
+  const uintptr_t len = (uintptr_t)n * 12;
+  for (int i = 0; i < 5; ++i) {
+    if (a.in[i] == nullptr || a.out[i] == nullptr) return SNERF_ERR_ARG;
+    for (int j = 0; j < 5; ++j)
+      if (pose_overlap(a.out[i], len, a.in[j], len)) return SNERF_ERR_ARG;
+    for (int j = i + 1; j < 5; ++j)
+      if (pose_overlap(a.out[i], len, a.out[j], len)) return SNERF_ERR_ARG;
+    if (pose_overlap(a.out[i], len, table, (uintptr_t)n_cams * 48) || pose_overlap(a.out[i], len, cam, (uintptr_t)n * 4)) return SNERF_ERR_ARG;
+  }
+  hipLaunchKernelGGL(pose_rays_apply_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
+  return snerf_check_launch();
+}
+
+// ---------------------------------------------------------------------------
+// Gradient of the table under snerf_pose_rays_apply, segmented by camera.  For every camera c that owns a ray
+//   G_c[i][j] = sum over its rays of (g_d[i] d[j] + g_v[i] v[j]) + (g_bx[i] bx[j] + g_by[i] by[j]),    g_t,c = t_ratio * sum g_o
+// with the UNtransformed d, v, bx, by.  Grid (n_cams, S): workgroup (c, s) walks the rays s 256 + lane, + 256 S, ... in ascending order,
+// reads the index of each (coalesced) and loads the 27 floats of the rays of camera c only; 12 sums and the ray count fold in double,
+// lane -> wave -> workgroup as in pose_grad_partial_kernel, into ws[(c S + s) 13 + k].  The finish launch, one thread per camera, folds the
+// S slices in order, leaves a camera without a ray alone (no store), chains G_c to its row (pose_chain), rounds once and ADDS.  No
+// floating-point atomics; S depends on (n, n_cams) only: the same bits every run.  Cost: n_cams n index reads out of L2.
+// ---------------------------------------------------------------------------
+#define POSE_RAYS_WG 2048            // workgroups aimed at: S = ceil(POSE_RAYS_WG / n_cams), at most one per 256 rays
+static inline int pose_rays_slices(long n, int n_cams) {
+  const int want = (POSE_RAYS_WG + n_cams - 1) / n_cams, have = pose_grad_blocks(n);
+  return want < have ? want : have;
+}
+
+extern "C" long snerf_pose_rays_grad_ws(long n, int n_cams) { return (n <= 0 || n_cams < 1) ? 0 : 13L * n_cams * pose_rays_slices(n, n_cams); }
+
+struct PoseRaysGrad {
+  const float* r; int n_cams; float t_ratio;
+  const float* cam;                                     // [n]
+  const float *g_o, *g_d, *g_v, *g_bx, *g_by;           // [n,3]; g_o nullable (no translation gradient wanted)
+  const float *d, *v, *bx, *by;                         // [n,3], untransformed
+  long n;
+  double* ws;                                           // [n_cams, slices, 13]
+  int slices;
+  float *grad_r, *grad_t;                               // [n_cams,3], each nullable
+};
+
+__global__ __launch_bounds__(256) void pose_rays_grad_partial_kernel(PoseRaysGrad a) {
+  __shared__ double red[4][13];
+  const int c = blockIdx.x;
+  double acc[13];
+#pragma unroll
+  for (int k = 0; k < 13; ++k) acc[k] = 0.0;
+  for (long i = (long)blockIdx.y * 256 + threadIdx.x; i < a.n; i += (long)gridDim.y * 256) {
+    if (pose_ray_cam(a.cam[i], a.n_cams) != c) continue;
+    double d[3], v[3], bx[3], by[3];
+#pragma unroll
+    for (int e = 0; e < 3; ++e) {
+      d[e] = (double)a.d[3 * i + e]; v[e] = (double)a.v[3 * i + e]; bx[e] = (double)a.bx[3 * i + e]; by[e] = (double)a.by[3 * i + e];
+    }
+#pragma unroll
+    for (int e = 0; e < 3; ++e) {
+      const double gd = (double)a.g_d[3 * i + e], gv = (double)a.g_v[3 * i + e], gx = (double)a.g_bx[3 * i + e], gy = (double)a.g_by[3 * i + e];
+#pragma unroll
+      for (int j = 0; j < 3; ++j) acc[3 * e + j] += (gd * d[j] + gv * v[j]) + (gx * bx[j] + gy * by[j]);
+      if (a.g_o != nullptr) acc[9 + e] += (double)a.g_o[3 * i + e];
+    }
+    acc[12] += 1.0;
+  }
+#pragma unroll
+  for (int k = 0; k < 13; ++k) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) acc[k] += __shfl_xor(acc[k], o, 64);
+  }
+  if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+    for (int k = 0; k < 13; ++k) red[threadIdx.x >> 6][k] = acc[k];
+  }
+  __syncthreads();
+  if (threadIdx.x < 13)
+    a.ws[13 * ((long)c * a.slices + blockIdx.y) + threadIdx.x] = ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
+}
+
+__global__ __launch_bounds__(64) void pose_rays_grad_finish_kernel(PoseRaysGrad a) {
+  const int c = blockIdx.x * 64 + threadIdx.x;
+  if (c >= a.n_cams) return;
+  double s[13];
+#pragma unroll
+  for (int k = 0; k < 13; ++k) s[k] = 0.0;
+  for (int b = 0; b < a.slices; ++b) {
+    const double* w = a.ws + 13 * ((long)c * a.slices + b);
+#pragma unroll
+    for (int k = 0; k < 13; ++k) s[k] += w[k];
+  }
+  if (s[12] == 0.0) return;                             // no ray of this camera in the batch: its rows keep their bits
+  if (a.grad_t != nullptr) {
+#pragma unroll
+    for (int e = 0; e < 3; ++e) a.grad_t[3 * (long)c + e] += (float)((double)a.t_ratio * s[9 + e]);
+  }
+  if (a.grad_r == nullptr) return;
+  double g[3];
+  pose_chain(s, a.r + 3 * (long)c, g);
+#pragma unroll
+  for (int k = 0; k < 3; ++k) a.grad_r[3 * (long)c + k] += (float)g[k];
+}
+
+extern "C" int snerf_pose_rays_grad(const float* r, int n_cams, float t_ratio, const float* cam, const float* g_o, const float* g_d,
+                                    const float* g_v, const float* g_bx, const float* g_by, const float* directions, const float* viewdirs,
+                                    const float* base_x, const float* base_y, long n, double* ws, long ws_doubles, float* grad_r,
+                                    float* grad_t, void* stream) {
+  if (n == 0) return SNERF_OK;
+  if (n < 0 || n_cams < 1 || r == nullptr || cam == nullptr) return SNERF_ERR_ARG;
+  if (g_d == nullptr || g_v == nullptr || g_bx == nullptr || g_by == nullptr || directions == nullptr || viewdirs == nullptr ||
+      base_x == nullptr || base_y == nullptr)
+    return SNERF_ERR_ARG;
+  if ((grad_r == nullptr && grad_t == nullptr) || (grad_t != nullptr && g_o == nullptr)) return SNERF_ERR_ARG;
+  const int slices = pose_rays_slices(n, n_cams);
+  if (ws == nullptr || ws_doubles < 13L * n_cams * slices) return SNERF_ERR_ARG;
+  PoseRaysGrad a{r, n_cams, t_ratio, cam, grad_t != nullptr ? g_o : nullptr, g_d, g_v, g_bx, g_by, directions, viewdirs, base_x, base_y, n, ws,
+                 slices, grad_r, grad_t};
+  hipLaunchKernelGGL(pose_rays_grad_partial_kernel, dim3((unsigned)n_cams, (unsigned)slices), dim3(256), 0, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(pose_rays_grad_finish_kernel, dim3((unsigned)((n_cams + 63) / 64)), dim3(64), 0, (hipStream_t)stream, a);
+  return snerf_check_launch();
+}

@@ -784,6 +784,19 @@ def adam_step_dev(p, g, m, v, lr, b1, b2, eps, step_dev, grad_scale=1.0, zero_gr
     adam_step(p, g, m, v, lr, b1, b2, eps, 0, grad_scale, zero_grad, step_dev=step_dev, **kw)
 
 
+def sgd_step(p, g, lr, grad_scale=1.0, nonfinite="zero", grad_max_val=0.0, clip_coef=None, dropped=None):
+    """Plain SGD over a flat buffer (snerf_sgd_step; torch.optim.SGD without momentum or weight decay): p -= lr * hygiene(g * grad_scale),
+    g = 0.  The hygiene options are adam_step's, in the same order."""
+    _f32c(p), _f32c(g)
+    assert p.numel() == g.numel()
+    if clip_coef is not None:
+        assert clip_coef.dtype == torch.float32 and clip_coef.is_cuda
+    if dropped is not None:
+        assert dropped.dtype == torch.int64 and dropped.is_cuda and dropped.numel() == 1
+    _lib.call("snerf_sgd_step", _p(p), _p(g), p.numel(), float(lr), float(grad_scale), float(grad_max_val), _p(clip_coef), NONFINITE[nonfinite],
+              _p(dropped), _stream())
+
+
 def grad_clip_coef(g, grad_scale, max_norm):
     """-> fp32 [2] on the device = (min(1, max_norm / (|grad_scale| ||g|| + 1e-6)), the norm): clip_grad_norm_'s coefficient for adam_step.
     A NaN in g gives (NaN, NaN) as in torch -- adam_step's `nonfinite` policy then decides about the whole step; +-Inf gives (0, Inf)."""
@@ -1640,6 +1653,60 @@ def pose_compose_grad(r, cam, g_o, g_d, g_v, origins, directions, viewdirs, grad
     cam_dev, cam_host = _cam_args(cam)
     _lib.call("snerf_pose_compose_grad", _p(r), r.shape[0], cam_dev, cam_host, _p(g_o), _p(g_d), _p(g_v), _p(origins), _p(directions),
               _p(viewdirs), n, _p(ws), ws.numel(), _p(grad_r), _p(grad_t), _stream())
+
+
+def pose_table(r, t, t_ratio=1.0, out=None):
+    """snerf_pose_table: the LearnPoseV2 table r [n_cams,3] / t [n_cams,3] (None = no translation) -> fp32 [n_cams,3,4], row c =
+    [R(r_c) | t_c * t_ratio] (posenet_v2.py:89,99), the rotation formed in double and rounded once."""
+    for x in (r, t, out):
+        _f32c(x)
+    assert r.dim() == 2 and r.shape[1] == 3 and (t is None or t.shape == r.shape)
+    if out is None:
+        out = torch.empty(r.shape[0], 3, 4, dtype=torch.float32, device=r.device)
+    assert tuple(out.shape) == (r.shape[0], 3, 4)
+    _lib.call("snerf_pose_table", _p(r), _p(t), r.shape[0], float(t_ratio), _p(out), _stream())
+    return out
+
+
+def pose_rays_apply(table, cam, origins, directions, viewdirs, base_x, base_y):
+    """snerf_pose_rays_apply: every ray moved by its own row of `table` (pose_table's) -- zipnerf/train.py:186-196.  cam fp32 [n]: the
+    rays' rows, truncated toward zero like the reference's .int(); a ray whose row is outside the table passes through unchanged.
+    -> new (origins + t, R directions, R viewdirs, R base_x, R base_y); the inputs are left as they are (pose_rays_grad needs them)."""
+    rays = (origins, directions, viewdirs, base_x, base_y)
+    for x in (table, cam) + rays:
+        _f32c(x)
+    n = origins.shape[0]
+    assert table.dim() == 3 and tuple(table.shape[1:]) == (3, 4) and cam.numel() == n
+    assert all(tuple(x.shape) == (n, 3) for x in rays)
+    outs = tuple(torch.empty_like(x) for x in rays)
+    _lib.call("snerf_pose_rays_apply", _p(table), table.shape[0], _p(cam), *[_p(x) for x in rays], n, *[_p(x) for x in outs], _stream())
+    return outs
+
+
+def pose_rays_grad_ws(n, n_cams):
+    """doubles of scratch pose_rays_grad needs for n rays over n_cams table rows (snerf_pose_rays_grad_ws)"""
+    return int(_lib.query("snerf_pose_rays_grad_ws", int(n), int(n_cams)))
+
+
+def pose_rays_grad(r, t_ratio, cam, g_o, g_d, g_v, g_bx, g_by, directions, viewdirs, base_x, base_y, grad_r, grad_t=None, ws=None):
+    """snerf_pose_rays_grad: d loss / d (the moved origins, directions, viewdirs, base_x, base_y) [n,3] and the UNmoved directions /
+    viewdirs / base_x / base_y reduced camera by camera (cam fp32 [n], as pose_rays_apply) to the gradient of the table rows that own a
+    ray, ADDED into grad_r [n_cams,3] (and grad_t, which takes t_ratio * sum g_o; either may be None, g_o too without grad_t); rows without
+    a ray are not written.  Deterministic (double sums in a fixed order, no atomics).  ws: fp64 scratch of >= pose_rays_grad_ws(n,
+    n_cams) elements (allocated when None)."""
+    rays = (g_d, g_v, g_bx, g_by, directions, viewdirs, base_x, base_y)
+    for x in (r, cam, g_o, grad_r, grad_t) + rays:
+        _f32c(x)
+    n = g_d.shape[0]
+    assert r.dim() == 2 and r.shape[1] == 3 and cam.numel() == n
+    assert all(x is not None and tuple(x.shape) == (n, 3) for x in rays) and (g_o is None or tuple(g_o.shape) == (n, 3))
+    for g in (grad_r, grad_t):
+        assert g is None or g.shape == r.shape
+    if ws is None:
+        ws = torch.empty(pose_rays_grad_ws(n, r.shape[0]), dtype=torch.float64, device=r.device)
+    assert ws.is_cuda and ws.dtype == torch.float64 and ws.is_contiguous()
+    _lib.call("snerf_pose_rays_grad", _p(r), r.shape[0], float(t_ratio), _p(cam), _p(g_o), *[_p(x) for x in rays], n, _p(ws), ws.numel(),
+              _p(grad_r), _p(grad_t), _stream())
 
 
 def _conf_args(maps, slot_of_image, lambdas, sky, img, coords):

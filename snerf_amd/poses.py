@@ -14,7 +14,11 @@ the rays of the INITIAL pose, which is what `snerf_pose_compose_apply` does; `sn
 rotation's gradient (`pose_sums(..., origins=o)`).  `MipTrainer(pose_net=..., freeze_model=True, pose_compose=True)` is that loop on the
 device: data gradients only, no weight gradient, no arena Adam; afterwards `pose_net(i)` is the refined pose of image i.
 
-Path C's pose refinement (cal_input_grad, s-nerfpp/zipnerf/train.py:187-224) parameterises the pose differently and is not covered."""
+Path C's pose refinement (s-nerfpp/zipnerf/train.py:177-213, 338-344; internal/posenet_v2.py) moves every ray by the row of its own
+camera -- a batch mixes cameras -- turns base_x / base_y as well, scales the translation by `t_ratio` and trains the table with plain
+SGD.  `LearnPoseV2` is that module in torch ops (its `posenet_ckpt_*` state_dict loads); `zipnerf.apply_pose` applies its output to a
+batch; on the device `ZipTrainer(pose_net=...)` runs `snerf_pose_table`, `snerf_pose_rays_apply` and `snerf_pose_rays_grad`, whose
+float64 host model is `pose_rays_sums` + `pose_grad_chain`."""
 import torch
 import torch.nn as nn
 
@@ -53,6 +57,59 @@ class LearnPose(nn.Module):
         if not transform_only and self.init_c2w is not None:
             c2w = c2w @ self.init_c2w[cam_id]
         return c2w
+
+
+def rotations(r):
+    """`rotation` for a whole table: axis-angle [N,3] -> [N,3,3], posenet_v2.Exp as written"""
+    z = torch.zeros_like(r[:, 0])
+    K = torch.stack([torch.stack([z, -r[:, 2], r[:, 1]], 1), torch.stack([r[:, 2], z, -r[:, 0]], 1), torch.stack([-r[:, 1], r[:, 0], z], 1)], 1)
+    th = r.norm(dim=-1)[:, None, None] + 1e-15
+    return torch.eye(3, dtype=r.dtype, device=r.device)[None] + (torch.sin(th) / th) * K + ((1 - torch.cos(th)) / th ** 2) * (K @ K)
+
+
+class LearnPoseV2(nn.Module):
+    def __init__(self, num_cams, learn_R=True, learn_t=True, init_c2w=None, t_ratio=1):
+        """posenet_v2.LearnPose: num_cams rows of axis-angle `r` and translation `t` (zeros: the identity), the translation applied as
+        t * t_ratio (configs.py:145: 0.25); init_c2w [num_cams,4,4] (optional, never trained)"""
+        super().__init__()
+        self.num_cams, self.t_ratio = int(num_cams), t_ratio
+        self.init_c2w = None
+        if init_c2w is not None:
+            self.init_c2w = nn.Parameter(torch.as_tensor(init_c2w).detach().clone(), requires_grad=False)
+        self.r = nn.Parameter(torch.zeros(self.num_cams, 3, dtype=torch.float32), requires_grad=bool(learn_R))
+        self.t = nn.Parameter(torch.zeros(self.num_cams, 3, dtype=torch.float32), requires_grad=bool(learn_t))
+
+    def forward(self, cam_id, transform_only=False, one_img=False):
+        """cam_id [B] (integer) -> [B,4,4]: the learned transforms [R(r) | t * t_ratio] of those rows, or (transform_only=False, with
+        init_c2w) those times init_c2w[cam_id]; one_img: the bare transform of row cam_id[0] alone, [1,4,4]"""
+        cam_id = torch.as_tensor(cam_id, device=self.r.device).reshape(-1).long()
+        if one_img:
+            cam_id = cam_id[:1]
+        top = torch.cat([rotations(self.r), (self.t * self.t_ratio)[:, :, None]], dim=2)
+        c2w = torch.cat([top, torch.zeros_like(top[:, :1])], dim=1)
+        c2w[:, 3, 3] = 1.0
+        c2w = c2w[cam_id]
+        if not one_img and not transform_only and self.init_c2w is not None:
+            c2w = c2w @ self.init_c2w[cam_id]
+        return c2w
+
+
+def pose_rays_sums(cam, n_cams, g_o, g_d, g_v, g_bx, g_by, directions, viewdirs, base_x, base_y, t_ratio=1.0):
+    """Host model of snerf_pose_rays_grad's reduction, float64: cam [n] (each ray's table row, truncated toward zero; rows outside
+    [0, n_cams) take no part) -> (G [n_cams,3,3], g_t [n_cams,3], count [n_cams]) with G_c = sum over the rays of camera c of
+    g_d d^T + g_v v^T + g_bx bx^T + g_by by^T (the UNmoved rays) and g_t,c = t_ratio * sum g_o.  `pose_grad_chain(r[c], G[c])` is
+    then row c of the rotation's gradient."""
+    f = lambda x: torch.as_tensor(x).detach().cpu().to(torch.float64)
+    c = torch.trunc(f(cam).reshape(-1))
+    ok = (c >= 0) & (c < n_cams)                                                        # (a NaN index compares false)
+    idx = c[ok].long()
+    outer = sum(f(g)[ok][:, :, None] * f(x)[ok][:, None, :] for g, x in ((g_d, directions), (g_v, viewdirs), (g_bx, base_x), (g_by, base_y)))
+    G = torch.zeros(n_cams, 3, 3, dtype=torch.float64).index_add_(0, idx, outer)
+    g_t = torch.zeros(n_cams, 3, dtype=torch.float64)
+    if g_o is not None:
+        g_t.index_add_(0, idx, f(g_o)[ok] * float(t_ratio))
+    count = torch.zeros(n_cams, dtype=torch.float64).index_add_(0, idx, torch.ones(idx.shape[0], dtype=torch.float64))
+    return G, g_t, count
 
 
 def pose_grad_chain(r, G):

@@ -253,14 +253,13 @@ class _SideTable(_AdamState):
         self.adam(1.0 / world, nonfinite)
 
 
-class _PoseAdam(_SideTable):
-    """The learned camera poses of a trainer (poses.LearnPose) and their Adam (utils/model_utils.py:36-42: its own optimiser, lr 1e-4) on
-    the device: the trained parameters -- `r`, then `t` when it is trained -- are moved into one flat fp32 buffer (the module's
-    parameters become views of it, so `pose_net.state_dict()` / `load_state_dict()` keep working).  State in the layout of
-    torch.optim.Adam([{'params': [...], 'lr': 1e-4}]).state_dict(): the `optimizer` entry of the reference's pose/NNNNNN.tar."""
+class _PoseFlat:
+    """The flat pose table of a trainer: the trained parameters of a LearnPose / LearnPoseV2 -- `r`, then `t` when it is trained -- moved
+    into one flat fp32 buffer (the module's parameters become views of it, so `pose_net.state_dict()` / `load_state_dict()` keep
+    working).  `_flatten` allocates `flat`; `_adopt`, once the gradient buffer stands, moves the parameters in and cuts `g`."""
     what = "pose"
 
-    def __init__(self, pose_net, device, lr, betas, eps):
+    def _flatten(self, pose_net, device):
         self.net = pose_net
         pose_net.to(device)
         self.shape = (pose_net.num_cams, 3)         # of every trained parameter
@@ -273,10 +272,12 @@ class _PoseAdam(_SideTable):
                 raise ValueError(f"pose_net.{n}: fp32 [num_cams, 3] expected")
         k = 3 * pose_net.num_cams
         self.flat = torch.zeros(k * len(self.names), dtype=torch.float32, device=device)
-        self._table_buffers(lr, betas, eps)
+
+    def _adopt(self):
+        k = 3 * self.net.num_cams
         self.g = {}
         for i, n in enumerate(self.names):
-            p = getattr(pose_net, n)
+            p = getattr(self.net, n)
             view = self.flat[i * k:(i + 1) * k].view(-1, 3)
             view.copy_(p.data)
             p.data = view
@@ -286,12 +287,69 @@ class _PoseAdam(_SideTable):
         k = 3 * self.net.num_cams
         return [(n, i * k, k, self.shape) for i, n in enumerate(self.names)]
 
-    def ws_need(self, n):
-        return ops.pose_grad_ws(n)
-
     def broadcast_tensors(self):
         """the whole table: an untrained t (learn_t=False) is applied to the rays all the same"""
         return [self.net.r.data, self.net.t.data]
+
+
+class _PoseAdam(_PoseFlat, _SideTable):
+    """The learned camera poses of a trainer (poses.LearnPose) and their Adam (utils/model_utils.py:36-42: its own optimiser, lr 1e-4) on
+    the device, over the flat table of _PoseFlat.  State in the layout of
+    torch.optim.Adam([{'params': [...], 'lr': 1e-4}]).state_dict(): the `optimizer` entry of the reference's pose/NNNNNN.tar."""
+
+    def __init__(self, pose_net, device, lr, betas, eps):
+        self._flatten(pose_net, device)
+        self._table_buffers(lr, betas, eps)
+        self._adopt()
+
+    def ws_need(self, n):
+        return ops.pose_grad_ws(n)
+
+
+class _PoseSGD(_PoseFlat, _SideTable):
+    """The per-ray learned poses of ZipTrainer (poses.LearnPoseV2) and their optimiser, plain SGD (s-nerfpp/zipnerf/internal/
+    train_utils.py:290: torch.optim.SGD(posenet.parameters(), lr), stepped after clip_gradients(posenet), train.py:343) on the device:
+    the flat table, its gradient buffer, no moments.  `lr` is a plain attribute read at step time: the caller applies the schedule
+    (pn_lr_fn, train.py:181-183) by assigning it.  State in the layout of torch.optim.SGD([...], lr).state_dict()."""
+
+    def __init__(self, pose_net, device, lr):
+        self._flatten(pose_net, device)
+        self.grad, self.lr, self._ws = torch.zeros_like(self.flat), float(lr), None
+        self._adopt()
+
+    def ws_need(self, n):
+        return ops.pose_rays_grad_ws(n, self.net.num_cams)
+
+    def train(self, world, group, nonfinite, loss_scale=1.0, grad_max_val=0.0, grad_max_norm=0.0, dropped=None):
+        """the table's SGD step (after the model's update): the ranks' gradients are summed like the model's; the launch undoes the loss
+        scale, takes the data-parallel mean, applies the trainer's gradient hygiene (train.py:343 clips the posenet with the model's
+        config) and zeroes the gradient"""
+        if world > 1:
+            dist.all_reduce(self.grad, op=dist.ReduceOp.SUM, group=group)
+        scale = 1.0 / (world * loss_scale)
+        coef = ops.grad_clip_coef(self.grad, scale, grad_max_norm) if grad_max_norm > 0 else None
+        ops.sgd_step(self.flat, self.grad, self.lr, grad_scale=scale, nonfinite=nonfinite, grad_max_val=grad_max_val, clip_coef=coef, dropped=dropped)
+
+    def _torch_sgd(self):
+        return torch.optim.SGD([torch.nn.Parameter(torch.zeros(shape)) for *_, shape in self._layout()], lr=self.lr)
+
+    def state_dict(self):
+        return self._torch_sgd().state_dict()
+
+    def load_state_dict(self, sd):
+        """takes the learning rate; refuses, before it writes, a state for another number of parameters or an SGD this launch is not
+        (momentum, dampening, weight decay, nesterov, maximize)"""
+        groups = sd["param_groups"]
+        if sum(len(g["params"]) for g in groups) != len(self._layout()):
+            raise ValueError(f"pose optimizer state for {sum(len(g['params']) for g in groups)} parameters, {len(self._layout())} expected "
+                             f"({', '.join(self.names)})")
+        if any(float(g["lr"]) != float(groups[0]["lr"]) for g in groups[1:]):
+            raise ValueError("the SGD launch covers the pose parameters with one lr: the saved param_groups differ")
+        if any(float(g.get(k, 0) or 0) != 0 for g in groups for k in ("momentum", "dampening", "weight_decay")) or \
+                any(g.get(k, False) for g in groups for k in ("nesterov", "maximize")):
+            raise ValueError("the pose optimizer is plain SGD: no momentum / dampening / weight decay / nesterov / maximize")
+        self._torch_sgd().load_state_dict(sd)          # (torch's own checks of the layout)
+        self.lr = float(groups[0]["lr"])
 
 
 class _ConfAdam(_SideTable):
@@ -963,8 +1021,15 @@ class ZipTrainer(_ArenaAdam):
     leaf copies of every level's `weights`; its d(loss)/d(weights) is added to the fused tail's)."""
 
     def __init__(self, model, lr=1e-2, betas=(0.9, 0.99), eps=1e-15, charb_padding=0.001, process_group=None, loss_cfg=None,
-                 nonfinite="zero", grad_max_val=0.0, grad_max_norm=0.0, table_exchange="sharded", loss_scale=None):
-        """`loss_scale` (a number = static; default 4096 when the model computes in fp16, else 1): the gradients of the rendered outputs are
+                 nonfinite="zero", grad_max_val=0.0, grad_max_norm=0.0, table_exchange="sharded", loss_scale=None, pose_net=None, pose_lr=1e-2,
+                 pose_index="glo_idx"):
+        """`pose_net` (a poses.LearnPoseV2; config.pose_refine, zipnerf/train.py:177-213, 338-344): the per-ray learned camera poses,
+        trained by `step(pose="train")` and applied by `step(pose="apply")` on the device.  Its trained parameters move into a flat
+        table with plain SGD (`self.pose`, a _PoseSGD; `pose_lr` = `self.pose.lr`, a plain attribute read at step time: assign the
+        schedule's value, pn_lr_fn, before the step); `pose_index`: the batch key that holds each ray's table row (`cam_idx` stands in
+        when the batch has no `glo_idx`).  loss_cfg `pose_depth_lambda` (0.0, train.py:256) replaces depth_lambda in a "train" step.
+        `pose_state_dict()` / `load_pose_state_dict()`: the table's optimiser in torch.optim.SGD's layout.
+        `loss_scale` (a number = static; default 4096 when the model computes in fp16, else 1): the gradients of the rendered outputs are
         multiplied by it before the backward -- so that the fp16 gradient buffers of the networks stay in fp16's normal range -- and the
         factor is undone inside the Adam launch (grad_scale), before clipping.  Overflowed (non-finite) gradients are dropped by
         `nonfinite` and counted in `dropped_nonfinite` (device int64: watch it in fp16 runs -- GradScaler would have skipped those steps).
@@ -984,6 +1049,11 @@ class ZipTrainer(_ArenaAdam):
         # the patch terms (train.py:280-293; step(n_patch=...)): computed behind the fused tail, not arguments of it
         self.d_smo_mult, self.s_smo_mult = float(self.loss_cfg.pop("d_smo_mult", 0.001)), float(self.loss_cfg.pop("s_smo_mult", 0.001))
         self.last_smooth_losses, self._patch_own, self._patch_ws = None, {}, None
+        self.pose_depth_lambda = float(self.loss_cfg.pop("pose_depth_lambda", 0.0))
+        self.pose, self.pose_index, self.last_ray_grads = None, pose_index, None
+        if pose_net is not None:
+            self.pose = _PoseSGD(pose_net, model.arena.flat.device, pose_lr)
+            self.side = (self.pose,)
         a = model.arena
         self.last_losses = None
         # running count of NaN / +-Inf gradient elements the Adam launches met (device int64, no host sync; read it when logging): a
@@ -1090,8 +1160,15 @@ class ZipTrainer(_ArenaAdam):
         return out[0] + out[1]
 
     def step(self, batch, target_rgb, train_frac=1.0, rand=True, aux_loss_fn=None, draws=None, sample_n=7, sample_m=3, targets=None, zero_glo=False,
-             n_patch=None, patch_size=None, patch_mask=None):
-        """`targets` (all optional, per ray): lossmult [R] (the reference's mask_rgb as 0/1 floats), depth [R] + depth_mask [R]
+             n_patch=None, patch_size=None, patch_mask=None, pose=None, ray_grads=False):
+        """`pose` (with a `pose_net`): "train" = a step of the refinement window (train.py:180-197, 256, 340-344) -- the rays are moved by
+        the rows of their cameras (ops.pose_table, ops.pose_rays_apply), the loss tail runs with depth_lambda = `pose_depth_lambda` (0:
+        `depth` and `d_complete` vanish), the backward also returns the ray gradients, ops.pose_rays_grad reduces them camera by camera
+        and the table takes its SGD step after the model's update (skipped with it when a dynamic loss scale overflows); "apply" = a step
+        after the window or with a loaded table (train.py:201-213): the rays are moved, the rest is the plain step, the table is not
+        touched.  `ray_grads=True` leaves d loss / d (origins, directions, viewdirs, base_x, base_y) of the rays the model saw in
+        `last_ray_grads` (the loss scale divided out): for callers who keep a pose optimiser of their own (zipnerf.apply_pose).
+        `targets` (all optional, per ray): lossmult [R] (the reference's mask_rgb as 0/1 floats), depth [R] + depth_mask [R]
         (+ complete_mask [R]), semantic int32 labels [R] + semantic_mask [R].  `zero_glo` (models with GLO vectors): train with zero
         vectors instead of the rows batch['cam_idx'] selects (zipnerf/train.py:235 passes zero_glo=False).
         `n_patch` > 0 with `patch_size` = p (a batch of zipnerf.PatchRayBatcher: n_patch = its n_patch_local): rows [0, n_patch p^2) are
@@ -1106,14 +1183,62 @@ class ZipTrainer(_ArenaAdam):
         m._zero_glo = bool(zero_glo)
         dev = m.arena.flat.device
         R = batch['origins'].shape[0]
+        cam = self._pose_index(batch, pose, R, dev)
         n_patch, p, t = self._step_args(R, target_rgb, targets or {}, n_patch, patch_size, patch_mask, dev)
+        train = pose == "train"
+        if pose is not None:
+            batch, unmoved = self._pose_move(batch, cam, dev)
         if draws is None:
             draws = m._draws(R, rand, dev, sample_n)
         levels, ctx = m._run(batch, True, float(train_frac), draws, sample_n, sample_m)
-        loss, G, g_w = self._loss_and_grads(levels, target_rgb, t, n_patch, p, patch_mask, aux_loss_fn, dev)
-        mine = self._backward(ctx, G, g_w)
-        self._update(mine)
+        loss, G, g_w = self._loss_and_grads(levels, target_rgb, t, n_patch, p, patch_mask, aux_loss_fn, dev,
+                                            depth_lambda=self.pose_depth_lambda if train else None)
+        mine, rg = self._backward(ctx, G, g_w, ray_grads=ray_grads or train)
+        if train:
+            ps = self.pose
+            ops.pose_rays_grad(ps.net.r.data, ps.net.t_ratio, cam, *rg, *unmoved[1:], ps.g.get("r"), ps.g.get("t"), ws=ps.workspace(R))
+        ls = self.loss_scale
+        self.last_ray_grads = ([g if ls == 1.0 else g * (1.0 / ls) for g in rg] if ray_grads else None)
+        if self._update(mine):
+            if train:
+                self.pose.train(self.world, self.pg, self.nonfinite, loss_scale=ls, grad_max_val=self.grad_max_val,
+                                grad_max_norm=self.grad_max_norm, dropped=self.dropped_nonfinite)
+        elif train:
+            self.pose.grad.zero_()
         return loss, levels
+
+    def _pose_index(self, batch, pose, R, dev):
+        """checks of step's `pose` argument, before any launch -> the rays' table rows as fp32 [R] on the device (None without `pose`)"""
+        if pose is None:
+            return None
+        if pose not in ("train", "apply"):
+            raise ValueError(f"pose: None, 'train' or 'apply', not {pose!r}")
+        if self.pose is None:
+            raise ValueError(f"step(pose={pose!r}) needs a ZipTrainer built with pose_net=")
+        key = self.pose_index if self.pose_index in batch else "cam_idx"
+        if key not in batch:
+            raise ValueError(f"step(pose={pose!r}): the batch has neither {self.pose_index!r} nor 'cam_idx' (each ray's row of the pose table)")
+        if batch[key].numel() != R:
+            raise ValueError(f"batch[{key!r}]: one table row per ray ({R}), got {batch[key].numel()} values")
+        self.pose.check_views()
+        return batch[key].detach().to(dev, torch.float32).reshape(R).contiguous()
+
+    def _pose_move(self, batch, cam, dev):
+        """-> (a new batch with every ray moved by the table row of its camera, the five unmoved ray tensors as the kernels read them)"""
+        from .zipnerf import POSE_RAY_KEYS
+        net = self.pose.net
+        unmoved = [batch[k].detach().to(dev, torch.float32).reshape(-1, 3).contiguous() for k in POSE_RAY_KEYS]
+        table = ops.pose_table(net.r.data, net.t.data, net.t_ratio)
+        batch = dict(batch)
+        batch.update(zip(POSE_RAY_KEYS, ops.pose_rays_apply(table, cam, *unmoved)))
+        return batch, unmoved
+
+    def pose_state_dict(self):
+        """the pose optimiser's state in torch.optim.SGD's layout (the table itself is `pose_net.state_dict()`)"""
+        return self.pose.state_dict()
+
+    def load_pose_state_dict(self, sd):
+        self.pose.load_state_dict(sd)
 
     def _step_args(self, R, target_rgb, t, n_patch, patch_size, patch_mask, dev):
         """checks of step's patch arguments -> (n_patch, p, the targets the loss tail sees)"""
@@ -1136,18 +1261,19 @@ class ZipTrainer(_ArenaAdam):
             raise ValueError("target_rgb: one row per ray")
         return n_patch, p, self._patch_targets(t, R, n_patch * p * p, dev)
 
-    def _loss_and_grads(self, levels, target_rgb, t, n_patch, p, patch_mask, aux_loss_fn, dev):
+    def _loss_and_grads(self, levels, target_rgb, t, n_patch, p, patch_mask, aux_loss_fn, dev, depth_lambda=None):
         """the fused loss tail, hash decay, the patch terms and `aux_loss_fn` -> (loss, the tail's output gradients G with the loss scale
-        in them, the three levels' weight gradients)"""
+        in them, the three levels' weight gradients).  `depth_lambda`: this step's value in place of loss_cfg's (a pose-training step)"""
         m = self.model
         fin = levels[2]
+        cfg = self.loss_cfg if depth_lambda is None else dict(self.loss_cfg, depth_lambda=depth_lambda)
         with_depth = t.get("depth") is not None
         with_sem = t.get("semantic") is not None and fin.get("semantic") is not None
         out, G = ops.zip_loss_tail(fin["rgb"], target_rgb, t.get("lossmult"), depth=fin["depth"] if with_depth else None,
                                    tdepth=t.get("depth"), dmask=t.get("depth_mask"), cmask=t.get("complete_mask"),
                                    sem=fin["semantic"] if with_sem else None, labels=t.get("semantic") if with_sem else None,
                                    smask=t.get("semantic_mask"), hist=[(levels[l]["sdist"], levels[l]["weights"]) for l in range(3)],
-                                   **self.loss_cfg)
+                                   **cfg)
         decay = torch.zeros(1, dtype=torch.float32, device=dev)
         if self.scaler is not None:
             self.loss_scale = self.scaler.scale
@@ -1178,8 +1304,9 @@ class ZipTrainer(_ArenaAdam):
             loss = loss + aux.detach()
         return loss, G, g_w
 
-    def _backward(self, ctx, G, g_w):
-        """the backward pass with the gradient exchange under it -> this rank's reduced table slices (_TableShards.finish), or None"""
+    def _backward(self, ctx, G, g_w, ray_grads=False):
+        """the backward pass with the gradient exchange under it -> (this rank's reduced table slices (_TableShards.finish), or None;
+        with `ray_grads` d loss / d (origins, directions, viewdirs, base_x, base_y), the loss scale in them, else None)"""
         m = self.model
         ex = _GradExchange(m.arena, self.world, self.pg)
         sh = self.shards
@@ -1193,21 +1320,23 @@ class ZipTrainer(_ArenaAdam):
             if sh is not None and isinstance(prefix, str) and prefix + "encoder.embeddings" in sh.spans:
                 sh.reduce_scatter(prefix + "encoder.embeddings")
             ex(prefix)
-        m._backward(ctx, [(None, None, None, g_w[0]), (None, None, None, g_w[1]), (G["rgb"], G["depth"], None, g_w[2], G["semantic"])], on_done=level_done)
+        rg = m._backward(ctx, [(None, None, None, g_w[0]), (None, None, None, g_w[1]), (G["rgb"], G["depth"], None, g_w[2], G["semantic"])],
+                         on_done=level_done, ray_grads=ray_grads)
         ex.finish()
-        return sh.finish() if sh is not None else None
+        return (sh.finish() if sh is not None else None), rg
 
     def _update(self, mine):
         """the overflow test of a dynamic loss scale, then Adam with the loss scale and the data-parallel mean folded in: one launch over the
-        arena, or with sharded tables (`mine`) one per table slice of this rank and one per stretch between the table spans"""
+        arena, or with sharded tables (`mine`) one per table slice of this rank and one per stretch between the table spans
+        -> False when the step was skipped for an overflow"""
         a, sh = self.model.arena, self.shards
         if self.scaler is not None and self._overflowed(a, mine):
-            return
+            return False
         self.t += 1
         grad_scale = 1.0 / (self.world * self.loss_scale)
         if sh is None:
             self._arena_adam(grad_scale, dropped=self.dropped_nonfinite)
-            return
+            return True
         # tables: this rank's slice only, then the updated slices are gathered; everything between the table spans: the usual pass
         hygiene = dict(grad_max_val=self.grad_max_val, dropped=self.dropped_nonfinite)
         for name, lo, hi, gshard in mine:
@@ -1222,3 +1351,4 @@ class ZipTrainer(_ArenaAdam):
         for name in self.tables:
             sh.all_gather_params(name)
         a.bump()
+        return True

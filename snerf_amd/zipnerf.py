@@ -462,6 +462,28 @@ class Model(_ArenaModule):
 
 
 
+POSE_RAY_KEYS = ('origins', 'directions', 'viewdirs', 'base_x', 'base_y')
+
+
+def apply_pose(batch, refine_poses):
+    """zipnerf/train.py:186-196 in torch ops: `refine_poses` [B,4,4] = posenet(batch['glo_idx'].reshape(-1).int()), one transform per
+    ray -> a NEW batch dict with origins + t and R directions / viewdirs / base_x / base_y (the other entries are the caller's
+    tensors).  Differentiable: the caller's route to a pose optimiser of their own (Model.forward(cal_input_grad=True) or
+    ZipTrainer.step(ray_grads=True)), and under no_grad the steps after the refinement window (train.py:201-213).  On the device
+    the same is ops.pose_table + ops.pose_rays_apply (ZipTrainer.step(pose=...)).
+    The reference writes the product as (x.reshape(-1, 1, 3) * R).sum(-1), which leaves the order of the two additions to torch's
+    reduction; here it is x'_i = (R_i0 x_0 + R_i1 x_1) + R_i2 x_2, the kernel's order, on every device: hash-grid gradients jump
+    where a sample crosses a cell face, so rays that differ in their last bit train measurably different poses."""
+    out = dict(batch)
+    R, t = refine_poses[:, :3, :3], refine_poses[:, :3, 3]
+    shape = batch['origins'].shape
+    out['origins'] = batch['origins'] + t.reshape(shape)
+    for k in POSE_RAY_KEYS[1:]:
+        x = batch[k].reshape(-1, 1, 3)
+        out[k] = ((R[:, :, 0] * x[:, :, 0] + R[:, :, 1] * x[:, :, 1]) + R[:, :, 2] * x[:, :, 2]).reshape(shape)
+    return out
+
+
 def _dist_info(accelerator):
     """(rank, world, gather) from an accelerate.Accelerator-like object or, when None, from torch.distributed."""
     import torch.distributed as dist
