@@ -400,6 +400,22 @@ int snerf_mip_loss_tail(const float* rgb, const float* tgt, const float* dist1, 
                         const float* conf, const float* s_f, const float* w_f, const float* s_c, const float* w_c, long N, int Pf,
                         int Sc, int disparity, float depth_lambda, float coarse_mult, float prop_lambda, float* out, float* g_rgb,
                         float* g_dist1, float* g_dist0, float* g_wc, void* stream);
+/* Loss tail of the classic path (path B): the stock training loop around render_rays with img2mse / mse2psnr
+ * (s-nerf/model/run_nerf_helpers.py:16-17).  rgb (the fine colour map, or the only one), rgb0 (the coarse map of a two-level render;
+ * nullable), tgt, g_rgb, g_rgb0 (nullable iff rgb0 is): fp32 [N,3] contiguous.
+ *   img_loss = mean((rgb - tgt)^2), img_loss0 = mean((rgb0 - tgt)^2) (0 without rgb0), loss = img_loss + img_loss0,
+ *   psnr = -10 ln(img_loss) / ln 10;  out[4] = {loss, img_loss, img_loss0, psnr}
+ *   g_rgb[i] = inv * (2 * (rgb[i] - tgt[i])) with inv = 1.0f / (float)(3 N), an fp32 division: the expression torch's pow / mean
+ *   backward evaluates; g_rgb0 alike from rgb0.  Gradients of the LOCAL mean: a data-parallel mean belongs into Adam's grad_scale.
+ * The sums are taken in double in an order that depends on N only (a partial launch into ws, a finish launch that adds the partials
+ * in block order and rounds each scalar to fp32 once): no floating-point atomics, bit-reproducible, graph-safe.  ws: device scratch of
+ * >= snerf_classic_loss_tail_ws(N) BYTES, 8-byte aligned; nothing past that is written.  Bad arguments (N <= 0, a null rgb / tgt / ws /
+ * out / g_rgb, rgb0 and g_rgb0 not both null or both given, a pointer off 4-byte alignment, ws off 8-byte alignment) return 1 before
+ * any launch. */
+int snerf_classic_loss_tail(const float* rgb, const float* rgb0, const float* tgt, long N, void* ws, float* out, float* g_rgb,
+                            float* g_rgb0, void* stream);
+/* bytes of scratch snerf_classic_loss_tail needs for N rays (0 for N <= 0) */
+long snerf_classic_loss_tail_ws(long N);
 /* The same tail with the per-image rules of s-nerf/train.py:131-209; the arguments of snerf_mip_loss_tail keep their meaning and,
  * with every new pointer NULL, their results (gradients bit for bit).  New, each nullable = term or mask absent:
  *   sem [N,C] fp32 composited logits, labels [N] (int32, or fp32 holding exact integers when labels_f32 = 1), g_sem [N,C]: all three
@@ -497,6 +513,20 @@ int snerf_mip_image_patch_batch(const void* images, int images_u8, const float* 
                                 float* origins, float* directions, float* viewdirs, float* radii, float* lossmult, float* near_out,
                                 float* far_out, float* app_out, float* rgb, float* depth, float* extras_out, long* sel_coords,
                                 long* img_out, int n_patch, int patch_sz, int k0, int k1, void* stream);
+/* Path B (the stock `use_batching` loader of the classic training loop: every ray of the training images, shuffled, N_rand per step):
+ * T = n_train H W rays.  Row r of step s has global position p = s n + r, epoch e = p / T, and is ray q = perm(4, e, T)(p mod T) (the
+ * keyed permutation of csrc/callers.hip with tag 4, keyed by the epoch) -> image i_train[q / (H W)], pixel row (q mod (H W)) / W, column
+ * (q mod (H W)) mod W: every ray exactly once per epoch, a new order every epoch; batches have constant size n and may straddle an
+ * epoch boundary.  images [n_images,H,W,3] fp32 or uint8, c2w fp32 [n_images,3,4], intrinsics DOUBLE [n_images,3] = (focal, cx, cy)
+ * (snerf_classic_get_rays takes doubles; each is rounded to fp32 as there), i_train int32 [n_train] with entries in [0, n_images).
+ * Outputs, rows [i0, i1) of the global batch: rows [i1 - i0, ld] = [o3, d3, near, far, (viewdir3)] (ld >= 8, or 11 with use_viewdirs),
+ * bit for bit what snerf_classic_ray_batch writes for the same pixel of the same camera (ndc as there, near = 1 in the warp); rgb
+ * [i1 - i0, 3] the pixel's colour.  counter as above.  A launch with i0 = i1 still advances the counter.  Bad arguments (n <= 0,
+ * n_images / n_train / H / W < 1, 0 <= i0 <= i1 <= n not holding, seed < 0, a null pointer, images_u8 outside {0, 1}, a short ld, a
+ * misaligned pointer) return 1 before any launch. */
+int snerf_classic_train_batch(const void* images, int images_u8, const float* c2w, const double* intrinsics, const int* i_train,
+                              int n_train, int n_images, int H, int W, long seed, long* counter, long n, long i0, long i1, int ndc,
+                              float near, float far, int use_viewdirs, float* rows, int ld, float* rgb, void* stream);
 /* Path C(s-nerfpp/zipnerf/internal/datasets.py:442-566 Dataset._next_train + _make_ray_batch, patch_size 1; anything else is a
  * bad argument): per ray a camera in [0, N) and x in [border, W - border), y in [border, H - border), uniform WITH replacement like
  * np.random.randint (single_image = 1: one camera per step, batching 'single_image').  images [N,H,W,3] fp32 or uint8, depths

@@ -651,6 +651,130 @@ def create_nerf(args, compute: str = "bf16", device="cuda"):
     return render_kwargs_train, render_kwargs_test, start, grad_vars, optimizer, model_confidence
 
 
+def lrate_decay(lrate, lrate_decay, global_step):
+    """The stock exponential learning-rate schedule of the classic training loop: lrate * 0.1 ** (global_step / (lrate_decay * 1000)),
+    `lrate_decay` in units of 1000 steps.  Assign it to `ClassicTrainer.lr` before a step (or a replay)."""
+    return lrate * 0.1 ** (global_step / (lrate_decay * 1000))
+
+
+class RayBatcher:
+    """Device-resident form of the stock `use_batching` loader of the classic training loop: the rays of ALL training images are visited
+    in a shuffled order, `N_rand` per step.  Images, camera-to-world matrices, the per-image (focal, cx, cy) table and i_train live on
+    the device; `next()` / `next_into(buf)` draws, casts and gathers one batch in ONE launch (`snerf_classic_train_batch`) with no host
+    work, no upload and no sync -- the stock loader builds every ray of every image up front and shuffles that array on the host.
+
+    Schedule (`sample_utils.classic_rays_of_step`): with T = len(i_train) H W, row r of step s sits at position p = s N_rand + r of the
+    ray stream, in epoch e = p // T, and is ray q = keyed_perm(p % T, T, tag, e, seed) -> image i_train[q // (H W)], pixel row
+    (q % (H W)) // W, column (q % (H W)) % W.  Every ray appears exactly once per epoch; batches have constant size and may straddle an
+    epoch boundary.  Only the order differs from the reference (a counter-based generator instead of numpy's shuffle): given the pixel,
+    the ray row [o3, d3, near, far, (viewdir3)] is what `render` builds for that pixel of that camera (ops.classic_ray_batch), bit for
+    bit, and the target is the pixel's colour (uint8 storage decodes to float32(k / 255.0)).
+
+    images [n,H,W,3] uint8 or float; poses [n,3,4] (or [n,4,4]); `focal`: one number or one per image; `ori_points`: None (the image
+    centre) or per-image (cx, cy); near / far: scalars (per-image bounds and precrop are not offered); ndc / use_viewdirs as `render`.
+    Rank r of `world` computes rows shard_bounds(N_rand, r, world) of the one global batch."""
+
+    def __init__(self, images, poses, focal, i_train, N_rand, near=0., far=1., ndc=True, use_viewdirs=False, ori_points=None, seed=0,
+                 rank=0, world=1, device=None):
+        from .sample_utils import _stack
+        from .trainer import shard_bounds
+        if not 0 <= int(seed) < (1 << 63):
+            raise ValueError("seed must be in [0, 2^63)")
+        device = torch.device(device if device is not None else "cuda")
+        img = _stack(images)
+        if img.dim() != 4 or img.shape[-1] != 3 or img.shape[0] == 0 or img.shape[1] == 0 or img.shape[2] == 0:
+            raise ValueError("images: [n, H, W, 3] with n, H, W >= 1")
+        n, H, W = (int(v) for v in img.shape[:3])
+        it = np.asarray(i_train.cpu() if torch.is_tensor(i_train) else i_train, dtype=np.int64).reshape(-1)
+        if it.size == 0:
+            raise ValueError("i_train is empty")
+        if it.min() < 0 or it.max() >= n:
+            raise ValueError("i_train indexes past the images")
+        P = _stack(poses).to(torch.float32)
+        if P.dim() != 3 or P.shape[0] != n or P.shape[1] < 3 or P.shape[2] != 4:
+            raise ValueError("poses: one [3, 4] (or [4, 4]) camera-to-world matrix per image")
+        f = np.asarray(focal.cpu() if torch.is_tensor(focal) else focal, dtype=np.float64).reshape(-1)
+        if f.size not in (1, n):
+            raise ValueError("focal: one number, or one per image")
+        K = np.empty((n, 3), dtype=np.float64)
+        K[:, 0] = f
+        if ori_points is None:
+            K[:, 1], K[:, 2] = W * 0.5, H * 0.5
+        else:
+            op = np.asarray(ori_points, dtype=np.float64).reshape(-1, 2)
+            if op.shape[0] != n:
+                raise ValueError("ori_points: one (cx, cy) per image")
+            K[:, 1:] = op
+        world, rank, N_rand = int(world), int(rank), int(N_rand)
+        if world < 1 or not 0 <= rank < world:
+            raise ValueError("rank in [0, world)")
+        if N_rand < world:
+            raise ValueError(f"N_rand = {N_rand}: at least one ray per rank ({world})")
+        self.images = img.to(device, torch.uint8 if img.dtype == torch.uint8 else torch.float32).contiguous()
+        self.c2w = P[:, :3, :4].to(device).contiguous()
+        self.intrinsics = torch.as_tensor(K).to(device)
+        self.i_train_host = it
+        self.i_train = torch.as_tensor(it, dtype=torch.int32).to(device)
+        self.n_images, self.H, self.W, self.N_rand = n, H, W, N_rand
+        self.T = int(it.size) * H * W
+        self.near, self.far, self.ndc, self.use_viewdirs = float(near), float(far), bool(ndc), bool(use_viewdirs)
+        self.rank, self.world = rank, world
+        self.i0, self.i1 = shard_bounds(N_rand, rank, world)
+        self.seed, self.device = int(seed), device
+        self.counter = torch.zeros(2, dtype=torch.int64, device=device)        # {step, workgroup ticket}: advanced by the launch
+        self._step = 0
+
+    @property
+    def step(self):
+        """the step of the next draw (host mirror of the device counter; `advance_host` after graph replays of `next_into`)"""
+        return self._step
+
+    @property
+    def n_rows(self):
+        """rows of this rank's batch"""
+        return self.i1 - self.i0
+
+    def rays_of_step(self, s):
+        """ray indices in [0, T) of this rank's rows of step s -- on the host, no sync"""
+        from .sample_utils import classic_rays_of_step
+        return classic_rays_of_step(s, self.N_rand, self.T, self.seed, self.rank, self.world)
+
+    def pixels_of_step(self, s):
+        """-> int64 [n_rows, 3] of (image, row, col) of this rank's rows of step s -- on the host, no sync"""
+        q = self.rays_of_step(s)
+        hw = self.H * self.W
+        return np.stack([self.i_train_host[q // hw], (q % hw) // self.W, (q % hw) % self.W], -1).astype(np.int64)
+
+    def state_dict(self):
+        return {"seed": self.seed, "step": self._step}
+
+    def load_state_dict(self, sd):
+        self.seed, self._step = int(sd["seed"]), int(sd["step"])
+        self.counter.copy_(torch.tensor([self._step, 0], dtype=torch.int64))
+
+    def advance_host(self, k=1):
+        """tell the host mirror that k draws ran inside graph replays"""
+        self._step += int(k)
+
+    def buffers(self):
+        """fresh output tensors of one batch (this rank's rows)"""
+        m = self.n_rows
+        return dict(rays=torch.empty(m, 11 if self.use_viewdirs else 8, dtype=torch.float32, device=self.device),
+                    rgb=torch.empty(m, 3, dtype=torch.float32, device=self.device))
+
+    def next_into(self, buf):
+        """draw the next batch into `buf` (from `buffers()`) on the current stream; graph-capturable (every replay draws the next step)
+        -> (ray_batch, target_rgb), the tensors of `buf`"""
+        ops.classic_train_batch(self.images, self.c2w, self.intrinsics, self.i_train, self.seed, self.counter, self.N_rand, self.i0, self.i1,
+                                self.ndc, self.near, self.far, self.use_viewdirs, buf["rays"], buf["rgb"])
+        self._step += 1
+        return buf["rays"], buf["rgb"]
+
+    def next(self):
+        """-> (ray_batch, target_rgb) of the next step in new tensors (they stay valid)"""
+        return self.next_into(self.buffers())
+
+
 def strip_module_prefix(state_dict):
     """Checkpoints saved from an nn.DataParallel / DistributedDataParallel wrapper carry a ``module.`` prefix on every key
     (s-nerf/utils/device_utils.py:33,38; s-nerf/eval.py:72-74 loads them into a wrapped model).  One process drives one GPU here, so

@@ -112,14 +112,32 @@ __device__ __forceinline__ void classic_pinhole(const float* c2w, int row, int c
   }
 }
 
-__device__ __forceinline__ void classic_ndc(const ClassicRays& a, float* o, float* d) {
-  const float t = -(a.ndc_near + o[2]) / d[2];
+// (ndc_cw, ndc_ch) = (-1/(W/(2 focal)), -1/(H/(2 focal))), computed in double like the python scalars and rounded once
+__device__ __forceinline__ void classic_ndc(float ndc_near, float ndc_cw, float ndc_ch, float* o, float* d) {
+  const float t = -(ndc_near + o[2]) / d[2];
 #pragma unroll
   for (int c = 0; c < 3; ++c) o[c] = o[c] + t * d[c];
-  const float o0 = a.ndc_cw * o[0] / o[2], o1 = a.ndc_ch * o[1] / o[2], o2 = 1.f + (2.f * a.ndc_near) / o[2];
-  const float d0 = a.ndc_cw * (d[0] / d[2] - o[0] / o[2]), d1 = a.ndc_ch * (d[1] / d[2] - o[1] / o[2]), d2 = (-2.f * a.ndc_near) / o[2];
+  const float o0 = ndc_cw * o[0] / o[2], o1 = ndc_ch * o[1] / o[2], o2 = 1.f + (2.f * ndc_near) / o[2];
+  const float d0 = ndc_cw * (d[0] / d[2] - o[0] / o[2]), d1 = ndc_ch * (d[1] / d[2] - o[1] / o[2]), d2 = (-2.f * ndc_near) / o[2];
   o[0] = o0; o[1] = o1; o[2] = o2;
   d[0] = d0; d[1] = d1; d[2] = d2;
+}
+
+// viewdirs = rays_d / norm(rays_d) (render.py:52-53), from the PRE-NDC directions
+__device__ __forceinline__ void classic_unit(const float* d, float* v) {
+  const float nrm = sqrtf((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
+#pragma unroll
+  for (int c = 0; c < 3; ++c) v[c] = d[c] / nrm;
+}
+
+// one row [o3, d3, near, far, (depth), (viewdir3)] of the ray batch (render.py:70-77)
+__device__ __forceinline__ void classic_store_row(float* q, const float* o, const float* d, float near, float far, const float* depth,
+                                                  int use_viewdirs, const float* v) {
+  q[0] = o[0]; q[1] = o[1]; q[2] = o[2]; q[3] = d[0]; q[4] = d[1]; q[5] = d[2];
+  q[6] = near; q[7] = far;                             // near * ones_like(d[..., :1]): exact
+  int k = 8;
+  if (depth != nullptr) q[k++] = *depth;
+  if (use_viewdirs) { q[k] = v[0]; q[k + 1] = v[1]; q[k + 2] = v[2]; }
 }
 
 __global__ __launch_bounds__(256) void classic_rays_kernel(ClassicRays a) {
@@ -133,26 +151,18 @@ __global__ __launch_bounds__(256) void classic_rays_kernel(ClassicRays a) {
     for (int c = 0; c < 3; ++c) { o[c] = a.rays_o[3 * r + c]; d[c] = a.rays_d[3 * r + c]; }
   }
   if (a.use_viewdirs) {
-    const float nrm = sqrtf((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
-#pragma unroll
-    for (int c = 0; c < 3; ++c) v[c] = d[c] / nrm;
+    classic_unit(d, v);
     // c2w_staticcam: the rays come from the static camera (principal point at the image centre: render.py:59 passes no
     // ori_points), the view directions stay those of c2w
     if (a.has_static) classic_pinhole(a.c2w_static, row, col, a.focal, (float)(a.W * 0.5), (float)(a.H * 0.5), o, d);
   }
-  if (a.ndc) classic_ndc(a, o, d);
+  if (a.ndc) classic_ndc(a.ndc_near, a.ndc_cw, a.ndc_ch, o, d);
   if (a.o_out != nullptr) {
 #pragma unroll
     for (int c = 0; c < 3; ++c) { a.o_out[3 * r + c] = o[c]; a.d_out[3 * r + c] = d[c]; }
   }
-  if (a.rows != nullptr) {
-    float* q = a.rows + r * a.ld;
-    q[0] = o[0]; q[1] = o[1]; q[2] = o[2]; q[3] = d[0]; q[4] = d[1]; q[5] = d[2];
-    q[6] = a.near; q[7] = a.far;                       // near * ones_like(d[..., :1]): exact
-    int k = 8;
-    if (a.depths != nullptr) q[k++] = a.depths[r];
-    if (a.use_viewdirs) { q[k] = v[0]; q[k + 1] = v[1]; q[k + 2] = v[2]; }
-  }
+  if (a.rows != nullptr)
+    classic_store_row(a.rows + r * a.ld, o, d, a.near, a.far, a.depths != nullptr ? a.depths + r : nullptr, a.use_viewdirs, v);
 }
 
 static int classic_rays_launch(ClassicRays& a, void* stream) {
@@ -334,6 +344,83 @@ extern "C" int snerf_mip_loss_tail(const float* rgb, const float* tgt, const flo
   LossTail a{rgb, tgt, dist1, dist0, tdepth, conf, s_f, w_f, s_c, w_c, N, Pf, Sc, disparity, depth_lambda, coarse_mult, prop_lambda, out,
              g_rgb, g_dist1, g_dist0, g_wc};
   hipLaunchKernelGGL(loss_tail_kernel, dim3((unsigned)((N + 63) / 64)), dim3(64), 0, (hipStream_t)stream, a);
+  return snerf_check_launch();
+}
+
+// ---------------------------------------------------------------------------
+// Loss tail of the classic path: the stock training loop around render_rays, img2mse / mse2psnr (s-nerf/model/run_nerf_helpers.py:16-17)
+// on the fine and the coarse colour map, value and gradients in two launches.
+//   img_loss = mean((rgb - tgt)^2), img_loss0 = mean((rgb0 - tgt)^2) (rgb0 null: 0), loss = img_loss + img_loss0,
+//   psnr = -10 ln(img_loss) / ln 10;  out[4] = {loss, img_loss, img_loss0, psnr}
+//   g_rgb[i] = inv (2 (rgb[i] - tgt[i])), inv = 1.f / (float)(3 N): what torch's mean / pow backward evaluate, in fp32
+// The sums are taken in double (the differences too: the squares are exact to double rounding) in an order that depends on N only:
+// ray r belongs to thread r mod (256 blocks(N)) and is taken in ascending order, the 64 lanes of a wave fold with shuffles, the 4
+// waves of a workgroup through LDS in wave order, the workgroups' partials (ws[2 b + k]) in block order by the finish launch, which
+// forms the four scalars in double and rounds each once.  No floating-point atomics: the same bits every run, graph-safe.
+// ---------------------------------------------------------------------------
+#define CLASSIC_TAIL_MAX_BLOCKS 256
+static inline int classic_tail_blocks(long N) {
+  const long b = (N + 255) / 256;
+  return b < 1 ? 1 : (b > CLASSIC_TAIL_MAX_BLOCKS ? CLASSIC_TAIL_MAX_BLOCKS : (int)b);
+}
+
+struct ClassicTail {
+  const float *rgb, *rgb0, *tgt;
+  long N;
+  double* ws; int blocks;
+  float *out, *g_rgb, *g_rgb0;
+};
+
+__global__ __launch_bounds__(256) void classic_tail_partial_kernel(ClassicTail a) {
+  __shared__ double red[4][2];
+  const float inv = 1.0f / (float)(3 * a.N);
+  double s1 = 0.0, s0 = 0.0;
+  for (long r = (long)blockIdx.x * 256 + threadIdx.x; r < a.N; r += (long)gridDim.x * 256) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const float t = a.tgt[3 * r + c], x = a.rgb[3 * r + c];
+      const double e = (double)x - (double)t;
+      s1 += e * e;
+      a.g_rgb[3 * r + c] = inv * (2.f * (x - t));
+      if (a.rgb0 != nullptr) {
+        const float y = a.rgb0[3 * r + c];
+        const double e0 = (double)y - (double)t;
+        s0 += e0 * e0;
+        a.g_rgb0[3 * r + c] = inv * (2.f * (y - t));
+      }
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) { s1 += __shfl_xor(s1, o, 64); s0 += __shfl_xor(s0, o, 64); }
+  if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6][0] = s1; red[threadIdx.x >> 6][1] = s0; }
+  __syncthreads();
+  if (threadIdx.x < 2) a.ws[2 * (long)blockIdx.x + threadIdx.x] = ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
+}
+
+__global__ __launch_bounds__(64) void classic_tail_finish_kernel(ClassicTail a) {
+  if (threadIdx.x != 0) return;
+  double s1 = 0.0, s0 = 0.0;
+  for (int b = 0; b < a.blocks; ++b) { s1 += a.ws[2 * (long)b]; s0 += a.ws[2 * (long)b + 1]; }
+  const double cnt = 3.0 * (double)a.N;
+  const double l1 = s1 / cnt, l0 = a.rgb0 != nullptr ? s0 / cnt : 0.0;
+  a.out[0] = (float)(l1 + l0);
+  a.out[1] = (float)l1;
+  a.out[2] = (float)l0;
+  a.out[3] = (float)(-10.0 * log(l1) / log(10.0));
+}
+
+extern "C" long snerf_classic_loss_tail_ws(long N) { return N <= 0 ? 0 : 16L * classic_tail_blocks(N); }
+
+extern "C" int snerf_classic_loss_tail(const float* rgb, const float* rgb0, const float* tgt, long N, void* ws, float* out, float* g_rgb,
+                                       float* g_rgb0, void* stream) {
+  if (N <= 0 || rgb == nullptr || tgt == nullptr || ws == nullptr || out == nullptr || g_rgb == nullptr) return SNERF_ERR_ARG;
+  if ((rgb0 == nullptr) != (g_rgb0 == nullptr)) return SNERF_ERR_ARG;
+  if ((((uintptr_t)rgb | (uintptr_t)rgb0 | (uintptr_t)tgt | (uintptr_t)out | (uintptr_t)g_rgb | (uintptr_t)g_rgb0) & 3) != 0 ||
+      ((uintptr_t)ws & 7) != 0)
+    return SNERF_ERR_ARG;
+  ClassicTail a{rgb, rgb0, tgt, N, (double*)ws, classic_tail_blocks(N), out, g_rgb, g_rgb0};
+  hipLaunchKernelGGL(classic_tail_partial_kernel, dim3((unsigned)a.blocks), dim3(256), 0, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(classic_tail_finish_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, a);
   return snerf_check_launch();
 }
 
@@ -1169,6 +1256,68 @@ extern "C" int snerf_mip_image_batch(const void* images, int images_u8, const fl
   return snerf_mip_image_patch_batch(images, images_u8, depths, poses, intrinsics, near, far, app, extras, n_extra, i_train, n_train, N, H, W, seed,
                                      counter, n, i0, i1, origins, directions, viewdirs, radii, lossmult, near_out, far_out, app_out, rgb, depth,
                                      extras_out, sel_coords, img_out, 0, 0, 0, 0, stream);
+}
+
+// ---------------------------------------------------------------------------
+// Training batch of the classic path: the device-resident form of the stock `use_batching` loader (every ray of the training images,
+// shuffled, N_rand at a time).  T = n_train H W rays; row r of step s sits at global position p = s N_rand + r, in epoch e = p / T, and
+// is ray q = perm(4, e, T)(p mod T) -> image i_train[q / (H W)], pixel (q mod (H W)) / W, (q mod (H W)) mod W: every ray exactly once
+// per epoch, a new order every epoch, batches of constant size that may straddle an epoch boundary.  Given the pixel, the row is what
+// classic_rays_kernel writes for that pixel of that camera (the same device functions, the same fp32 roundings of focal / cx / cy and
+// of the NDC constants), the target the pixel's colour (texel).  One lane per row; rows [i0, i1) of the global batch: a rank's slice.
+// ---------------------------------------------------------------------------
+struct ClassicBatch {
+  const void* images; int u8;                     // [n_img,H,W,3]
+  const float* c2w;                               // [n_img,3,4]
+  const double* intr;                             // [n_img,3] = (focal, cx, cy)
+  const int* i_train; int n_train, n_img, H, W;
+  unsigned k0, k1;
+  long* ctr;
+  long n, i0, i1;
+  int ndc, use_viewdirs;
+  float near, far;
+  float* rows; int ld;
+  float* rgb;
+};
+
+__global__ __launch_bounds__(256) void classic_train_batch_kernel(ClassicBatch a) {
+  const long s = batch_step(a.ctr);
+  const long r = (long)blockIdx.x * 256 + threadIdx.x;
+  if (r >= a.i1 - a.i0) return;
+  const unsigned long long HW = (unsigned long long)a.H * a.W, T = HW * (unsigned long long)a.n_train;
+  const unsigned long long p = (unsigned long long)s * (unsigned long long)a.n + (unsigned long long)(a.i0 + r);
+  const unsigned long long e = p / T;
+  const unsigned long long q = keyed_perm(p - e * T, T, 4u, (long)e, a.k0, a.k1);
+  const unsigned long long slot = q / HW, pixel = q - slot * HW;
+  const int img = a.i_train[slot];
+  if (img < 0 || img >= a.n_img) return;          // (RayBatcher checks i_train on the host; never read past the tables)
+  const int row = (int)(pixel / (unsigned)a.W), col = (int)(pixel - (unsigned long long)row * a.W);
+  const double* k = a.intr + 3 * (long)img;
+  float o[3], d[3], v[3] = {0.f, 0.f, 0.f};
+  classic_pinhole(a.c2w + 12 * (long)img, row, col, (float)k[0], (float)k[1], (float)k[2], o, d);
+  if (a.use_viewdirs) classic_unit(d, v);
+  if (a.ndc) classic_ndc(1.f, (float)(-1.0 / ((double)a.W / (2.0 * k[0]))), (float)(-1.0 / ((double)a.H / (2.0 * k[0]))), o, d);
+  classic_store_row(a.rows + r * a.ld, o, d, a.near, a.far, nullptr, a.use_viewdirs, v);
+  const long pix = (long)img * (long)HW + (long)pixel;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) a.rgb[3 * r + c] = texel(a.images, a.u8, 3 * pix + c);
+}
+
+extern "C" int snerf_classic_train_batch(const void* images, int images_u8, const float* c2w, const double* intrinsics, const int* i_train,
+                                         int n_train, int n_images, int H, int W, long seed, long* counter, long n, long i0, long i1,
+                                         int ndc, float near, float far, int use_viewdirs, float* rows, int ld, float* rgb, void* stream) {
+  if (n <= 0 || n_images < 1 || n_train < 1 || H < 1 || W < 1 || i0 < 0 || i1 < i0 || i1 > n || seed < 0) return SNERF_ERR_ARG;
+  if (images == nullptr || c2w == nullptr || intrinsics == nullptr || i_train == nullptr || counter == nullptr || rows == nullptr ||
+      rgb == nullptr || (images_u8 != 0 && images_u8 != 1) || ld < (use_viewdirs ? 11 : 8))
+    return SNERF_ERR_ARG;
+  if ((((uintptr_t)c2w | (uintptr_t)i_train | (uintptr_t)rows | (uintptr_t)rgb) & 3) != 0 || (((uintptr_t)intrinsics | (uintptr_t)counter) & 7) != 0 ||
+      (images_u8 == 0 && ((uintptr_t)images & 3) != 0))
+    return SNERF_ERR_ARG;
+  ClassicBatch a{images, images_u8, c2w, intrinsics, i_train, n_train, n_images, H, W, (unsigned)(unsigned long)seed,
+                 (unsigned)((unsigned long)seed >> 32), counter, n, i0, i1, ndc ? 1 : 0, use_viewdirs ? 1 : 0, near, far, rows, ld, rgb};
+  const long m = i1 - i0;
+  hipLaunchKernelGGL(classic_train_batch_kernel, dim3((unsigned)(m > 0 ? (m + 255) / 256 : 1)), dim3(256), 0, (hipStream_t)stream, a);
+  return snerf_check_launch();
 }
 
 struct ZipBatch {

@@ -1423,6 +1423,35 @@ def mip_loss_tail(rgb, tgt, dist1, dist0, tdepth, conf, s_f, w_f, s_c, w_c, disp
     return out, g_rgb, g1, g0, gw
 
 
+def classic_loss_tail_ws(n):
+    """bytes of scratch classic_loss_tail needs for n rays (snerf_classic_loss_tail_ws)"""
+    return int(_lib.query("snerf_classic_loss_tail_ws", int(n)))
+
+
+def classic_loss_tail(rgb, rgb0, tgt, ws=None, out=None, g_rgb=None, g_rgb0=None):
+    """snerf_classic_loss_tail: the stock loss of the classic training loop, img2mse(rgb, tgt) + img2mse(rgb0, tgt) (rgb0 None: the
+    one-level render) and mse2psnr, with d loss / d rgb and d loss / d rgb0 -> (out[4] = {loss, img_loss, img_loss0, psnr}, g_rgb,
+    g_rgb0 or None).  fp32 [n,3] contiguous; double sums in a fixed order, no atomics.  ws: uint8 / fp64 scratch of >=
+    classic_loss_tail_ws(n) bytes (allocated when None); out / g_rgb / g_rgb0: preallocated results (allocated when None)."""
+    _f32c(rgb); _f32c(rgb0); _f32c(tgt)
+    assert rgb.dim() == 2 and rgb.shape[1] == 3 and rgb.shape[0] > 0 and tgt.shape == rgb.shape and (rgb0 is None or rgb0.shape == rgb.shape), \
+        "rgb / rgb0 / tgt: fp32 [n, 3] with n >= 1"
+    n, dev = rgb.shape[0], rgb.device
+    need = classic_loss_tail_ws(n)
+    if ws is None:
+        ws = torch.empty(need // 8, dtype=torch.float64, device=dev)
+    assert ws.is_cuda and ws.is_contiguous() and ws.numel() * ws.element_size() >= need, "ws: >= classic_loss_tail_ws(n) bytes of device scratch"
+    out = torch.empty(4, dtype=torch.float32, device=dev) if out is None else _f32c(out)
+    g_rgb = torch.empty_like(rgb) if g_rgb is None else _f32c(g_rgb)
+    if rgb0 is None:
+        assert g_rgb0 is None, "g_rgb0 goes with rgb0"
+    else:
+        g_rgb0 = torch.empty_like(rgb0) if g_rgb0 is None else _f32c(g_rgb0)
+    assert out.numel() == 4 and g_rgb.shape == rgb.shape and (g_rgb0 is None or g_rgb0.shape == rgb.shape)
+    _lib.call("snerf_classic_loss_tail", _p(rgb), _p(rgb0), _p(tgt), n, _p(ws), _p(out), _p(g_rgb), _p(g_rgb0), _stream())
+    return out, g_rgb, g_rgb0
+
+
 def mip_loss_tail_masked(rgb, tgt, dist1, dist0, tdepth, conf, s_f, w_f, s_c, w_c, disparity, depth_lambda, coarse_mult, prop_lambda,
                          sem=None, labels=None, semantic_lambda=0.1, rows=None, img_i=None, rgb_row_limit=None, depth_row_limit=None,
                          sem_valid=None, depth_keep=None, want_g_conf=False):
@@ -1536,6 +1565,27 @@ def mip_image_patch_batch(images, depths, poses, intrinsics, near, far, app, ext
               _p(out["app"]), _p(out["rgb"]), _p(out.get("depth")), _p(out.get("extras")), _p(out["sel_coords"]), _p(out["img"]),
               int(n_patch), int(patch_sz), int(k0), int(k1), _stream())
     return out
+
+
+def classic_train_batch(images, c2w, intrinsics, i_train, seed, counter, n, i0, i1, ndc, near, far, use_viewdirs, rows, rgb):
+    """snerf_classic_train_batch: rows [i0, i1) of step counter[0]'s global batch of n rays of the classic training loop (every ray of
+    the training images in a shuffled order, n per step) into the preallocated `rows` [i1 - i0, 8 | 11] = [o3, d3, near, far, (viewdir3)]
+    and `rgb` [i1 - i0, 3]; one launch, advances counter[0].  images [N,H,W,3] uint8 / fp32, c2w fp32 [N,3,4], intrinsics fp64 [N,3] =
+    (focal, cx, cy), i_train int32 with entries in [0, N)."""
+    u8 = _u8_or_f32(images)
+    assert images.dim() == 4 and images.shape[3] == 3, "images: [N, H, W, 3]"
+    N, H, W = images.shape[:3]
+    _f32c(c2w); _f32c(rows); _f32c(rgb)
+    assert tuple(c2w.shape) == (N, 3, 4), "c2w: fp32 [N, 3, 4]"
+    assert intrinsics.is_cuda and intrinsics.dtype == torch.float64 and intrinsics.is_contiguous() and tuple(intrinsics.shape) == (N, 3), \
+        "intrinsics: fp64 [N, 3] = (focal, cx, cy)"
+    assert i_train.is_cuda and i_train.dtype == torch.int32 and i_train.is_contiguous() and i_train.numel() >= 1
+    assert counter.is_cuda and counter.dtype == torch.int64 and counter.numel() == 2
+    m, ld = int(i1) - int(i0), 11 if use_viewdirs else 8
+    assert 0 <= int(i0) <= int(i1) <= int(n) and tuple(rows.shape) == (m, ld) and tuple(rgb.shape) == (m, 3), "rows [i1 - i0, 8 | 11], rgb [i1 - i0, 3]"
+    _lib.call("snerf_classic_train_batch", _p(images), u8, _p(c2w), _p(intrinsics), _p(i_train), i_train.numel(), N, H, W, int(seed), _p(counter),
+              int(n), int(i0), int(i1), 1 if ndc else 0, float(near), float(far), 1 if use_viewdirs else 0, _p(rows), ld, _p(rgb), _stream())
+    return rows, rgb
 
 
 def smooth_loss_ws(P):

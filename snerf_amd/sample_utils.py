@@ -148,6 +148,23 @@ def keyed_perm(v, M, tag, t, seed):
             return v
 
 
+CLASSIC_BATCH_TAG = 4                                # keyed_perm tag of classic.RayBatcher (1 / 2: ImageRayBatcher's image and pixel orders, 3: the bounded draws)
+
+
+def classic_rays_of_step(s, n_rand, T, seed, rank=0, world=1):
+    """classic.RayBatcher's schedule (host form of snerf_classic_train_batch): the ray indices in [0, T) of rank's rows of step s.  Row r of
+    the global batch sits at position p = s n_rand + r of the endless ray stream, in epoch e = p // T, and is ray
+    keyed_perm(p % T, T, CLASSIC_BATCH_TAG, e, seed): every epoch visits each of the T rays once, in an order of its own; a batch may
+    straddle an epoch boundary.  -> int64 [rows of shard_bounds(n_rand, rank, world)]"""
+    from .trainer import shard_bounds
+    i0, i1 = shard_bounds(int(n_rand), int(rank), int(world))
+    out = np.empty(i1 - i0, dtype=np.int64)
+    for k, r in enumerate(range(i0, i1)):
+        e, pos = divmod(int(s) * int(n_rand) + r, int(T))
+        out[k] = keyed_perm(pos, int(T), CLASSIC_BATCH_TAG, e, int(seed))
+    return out
+
+
 def image_of_step(i_train, seed, s):
     """ImageRayBatcher's image schedule: step s of epoch e = s // len(i_train) trains on i_train[keyed_perm(s % len(i_train))] (each
     training image once per epoch, a new order every epoch)."""

@@ -1352,3 +1352,299 @@ class ZipTrainer(_ArenaAdam):
             sh.all_gather_params(name)
         a.bump()
         return True
+
+
+class _NetAdam(_AdamState):
+    """_AdamState over the arena of ONE network of a ClassicTrainer: its fused Adam launch, its device step / lr words and its part of
+    the warm-up snapshot.  The moments are the network's slices of the trainer's moment buffers; step count and hyper-parameters are
+    the trainer's (one optimiser over both networks, like torch.optim.Adam(grad_vars))."""
+    what = "network"
+    lr, betas, eps = (property(lambda self, k=k: getattr(self.owner, k)) for k in ("lr", "betas", "eps"))
+    t = property(lambda self: self.owner.t, lambda self, v: setattr(self.owner, "t", v))
+
+    def __init__(self, owner, net, m, v):
+        self.owner, self.net, self.m, self.v = owner, net, m, v
+
+    def _buffers(self):
+        return self.net.arena.flat, self.net.arena.grad
+
+
+class ClassicTrainer(_AdamState):
+    """Train step of the classic render_rays path (path B; the stock loop around s-nerf/model/render.py:281-409: render_rays,
+    img2mse on the fine and the coarse colour map, loss.backward(), optimizer.step()) without the autograd round trip: the operators
+    of classic.render_rays called directly, ONE loss-tail pair of launches (ops.classic_loss_tail: loss, psnr and d loss / d rgb), the
+    compositing and network backward passes into the flat gradient arenas, the all-reduce of each arena, and one fused Adam launch per
+    arena with the 1 / world mean (and the loss scale) folded in.  No autograd graph, no per-parameter gradient clones, no host read.
+
+    Arguments as render_rays' (`ClassicTrainer(**render_kwargs_train)` works: create_nerf's `use_viewdirs` / `ndc` entries belong to
+    render() and are accepted and ignored; `network_query_fn` is kept for that signature only: the networks embed inside their first
+    kernel).  `network_fine=None` with N_importance > 0 runs both passes through `network_fn`, whose arena then collects both passes'
+    gradients; N_importance = 0 is the one-level render.  NeRF_RGB networks (a frozen alpha model) and `ert` are not offered.
+    `lr` is a plain attribute read at step time: assign the schedule's value (classic.lrate_decay) before a step or a replay.
+    `nonfinite`: ops.adam_step's policy.  `loss_scale`: the tail's gradients are multiplied by it before the backward passes and the
+    factor is undone inside the Adam launches.
+    `state_dict()` / `load_state_dict()`: torch.optim.Adam's layout over create_nerf's grad_vars order -- the coarse network's
+    parameters, then the fine one's -- with one step count: the `optimizer_state_dict` of the reference's checkpoints
+    (render.py:165-278; classic.create_nerf)."""
+    what = "classic"
+
+    def __init__(self, network_fn, network_query_fn=None, N_samples=64, N_importance=0, network_fine=None, lr=5e-4, betas=(0.9, 0.999), eps=1e-8,
+                 perturb=1., lindisp=False, white_bkgd=False, raw_noise_std=0., nonfinite="zero", loss_scale=1.0, process_group=None,
+                 exchange_when_single=False, use_viewdirs=None, ndc=None):
+        from . import classic
+        nets = [network_fn] + ([network_fine] if network_fine is not None else [])
+        for net in nets:
+            if not isinstance(net, classic.NeRF):
+                raise ValueError("ClassicTrainer: network_fn / network_fine must be snerf_amd.classic.NeRF modules (network_fn is needed: the "
+                                 "no_coarse route belongs to NeRF_RGB)")
+            if not net._alpha_head:
+                raise ValueError("ClassicTrainer: NeRF_RGB (the colour network over a frozen alpha model) is not offered")
+        if network_fine is not None and int(N_importance) <= 0:
+            raise ValueError("ClassicTrainer: network_fine is evaluated on the importance samples only: it needs N_importance > 0")
+        if network_fine is network_fn:
+            raise ValueError("ClassicTrainer: pass network_fine=None to run both passes through network_fn")
+        if network_fine is not None and network_fine.arena.flat.device != network_fn.arena.flat.device:
+            raise ValueError("ClassicTrainer: both networks on one device")
+        if int(N_samples) < 2 or int(N_importance) < 0 or not float(loss_scale) > 0:
+            raise ValueError("ClassicTrainer: N_samples >= 2, N_importance >= 0, loss_scale > 0")
+        self.network_fn, self.network_fine, self.network_query_fn = network_fn, network_fine, network_query_fn
+        self.N_samples, self.N_importance = int(N_samples), int(N_importance)
+        self.lr, self.betas, self.eps, self.t = lr, tuple(betas), eps, 0
+        self.perturb, self.lindisp, self.white_bkgd, self.raw_noise_std = float(perturb), bool(lindisp), bool(white_bkgd), float(raw_noise_std)
+        self.nonfinite, self.loss_scale = nonfinite, float(loss_scale)
+        self.pg = process_group
+        live = dist.is_available() and dist.is_initialized()
+        self.world = dist.get_world_size(process_group) if live else 1
+        self.single_rank_exchange = bool(exchange_when_single) and live
+        dev = network_fn.arena.flat.device
+        sizes = [net.arena.numel for net in nets]
+        self.m, self.v = torch.zeros(sum(sizes), dtype=torch.float32, device=dev), torch.zeros(sum(sizes), dtype=torch.float32, device=dev)
+        self._base = [0]
+        for k in sizes:
+            self._base.append(self._base[-1] + k)
+        self.nets = [_NetAdam(self, net, self.m[a:a + k], self.v[a:a + k]) for net, a, k in zip(nets, self._base, sizes)]
+        for net in nets:
+            net.arena.grad.zero_()
+        self._const, self._ws = {}, None
+        self._batcher = None
+
+    # ---- the optimiser state ------------------------------------------------------------------------------------------------------
+    def _layout(self):
+        """create_nerf's grad_vars order: list(model.parameters()) + list(model_fine.parameters()), offsets into the moment buffers"""
+        out = []
+        for tag, x, base in zip(("network_fn.", "network_fine."), self.nets, self._base):
+            a = x.net.arena
+            out += [(tag + n, base + a._offs[n][0], a._offs[n][1], a.shapes[n]) for n, _ in x.net.named_parameters()]
+        return out
+
+    def state_dict(self):
+        sd = super().state_dict()
+        sd["param_names"] = [n for n, *_ in self._layout()]
+        return sd
+
+    def load_state_dict(self, sd):
+        if "param_names" in sd and list(sd["param_names"]) != [n for n, *_ in self._layout()]:
+            raise ValueError("optimizer state was saved for other parameter names")
+        super().load_state_dict(sd)
+        for x in self.nets:
+            if x.step_dev is not None:
+                x.step_dev.fill_(self.t)
+
+    def broadcast_parameters(self, src=0):
+        if self.world > 1:
+            for x in self.nets:
+                dist.broadcast(x.net.arena.flat, src=src, group=self.pg)
+                x.net.arena.bump()
+
+    # ---- the step ------------------------------------------------------------------------------------------------------------------
+    def _constant(self, key, make):
+        """a device constant built once (render_rays uploads its linspace every call)"""
+        hit = self._const.get(key)
+        if hit is None:
+            hit = self._const[key] = make()
+        return hit
+
+    def _network(self, net, pts, viewdirs, S):
+        """run_network's preparation of (inputs, viewdirs) and the network's training forward -> (raw [n S, C], saved)"""
+        if net.use_viewdirs != (viewdirs is not None):       # (as run_network)
+            raise TypeError("ClassicTrainer: ray rows with view directions ([N, 11]) go with networks built with use_viewdirs=True, and only "
+                            "with them")
+        net._check_arena()
+        vd = None
+        if net.use_viewdirs:
+            vd = viewdirs if viewdirs.stride(-1) == 1 else viewdirs.contiguous()
+        return net.net.forward(pts.reshape(-1, 3), vd, S, True)
+
+    def _forward_backward(self, ray_batch, target_rgb, t_rand=None, u=None, noise=None, on_done=None):
+        """draws, both passes forward, the loss tail, both passes backward into the gradient arenas (no exchange, no optimiser).
+        `on_done(i)`: network i's gradients are final"""
+        from . import classic
+        S, Ni = self.N_samples, self.N_importance
+        coarse = self.network_fn
+        fine = self.network_fine if self.network_fine is not None else coarse
+        if ray_batch.dim() != 2 or ray_batch.shape[0] == 0 or ray_batch.shape[1] not in (8, 11):
+            raise ValueError("ClassicTrainer: ray_batch is render_rays' [N, 8 | 11] = [o3, d3, near, far, (viewdir3)] with N >= 1")
+        dev = coarse.arena.flat.device
+        rb = ray_batch.detach().to(dev, torch.float32)
+        if rb.stride(-1) != 1:
+            rb = rb.contiguous()
+        N = rb.shape[0]
+        tgt = target_rgb.detach().to(dev, torch.float32).contiguous()
+        if tuple(tgt.shape) != (N, 3):
+            raise ValueError("ClassicTrainer: target_rgb is [N, 3]")
+        rays_d = rb[:, 3:6]
+        viewdirs = rb[:, -3:] if rb.shape[-1] > 9 else None
+        base = self._constant(("base", S), lambda: torch.linspace(0., 1., steps=S).to(dev))
+        if self.perturb > 0. and t_rand is None:
+            t_rand = torch.rand(N, S, device=dev)
+        z_vals = ops.stratified(base, None if t_rand is None else t_rand.contiguous().float(), rb[:, 6], rb[:, 7], N, 0, self.lindisp)
+        noises = list(noise) if isinstance(noise, (tuple, list)) else [noise, None]
+        std = self.raw_noise_std
+
+        def level(net, z, given):
+            """one pass: points, network, compositing -> (raw, saved, noise, (rgb, disp, acc, weights, depth))"""
+            raw, saved = self._network(net, ops.classic_points(rb, z), viewdirs, z.shape[1])
+            if given is None and std > 0.:             # raw2outputs' draw (run_nerf_helpers.py:399-401)
+                given = torch.randn(N, z.shape[1], device=dev) * std
+            if given is not None:
+                given = given.to(dev, torch.float32).contiguous()
+            return raw, saved, given, ops.classic_composite_fwd(raw, given, z, rays_d, self.white_bkgd)
+        raw0, saved0, noise0, (rgb0, disp0, acc0, w0, depth0) = level(coarse, z_vals, noises[0])
+        ret = {"rgb_map": rgb0, "disp_map": disp0, "acc_map": acc0, "depth_map": depth0, "z_vals_map": z_vals, "weights": w0}
+        if Ni > 0:
+            if u is None and self.perturb == 0.:
+                u = self._constant(("u", Ni), lambda: torch.linspace(0., 1., steps=Ni).to(dev))
+            u = classic._draw_u(N, Ni, False, False, u, dev)
+            z_samples, _, z_std = ops.classic_sample_pdf(z_vals, w0, u, True, False, True)      # (no gradient: render.py:381 detaches)
+            z_all = ops.classic_merge_sort(z_vals, z_samples)
+            raw1, saved1, noise1, (rgb1, disp1, acc1, w1, depth1) = level(fine, z_all, noises[1])
+            ret.update(rgb_map=rgb1, disp_map=disp1, acc_map=acc1, depth_map=depth1, rgb0=rgb0, disp0=disp0, acc0=acc0, z_std=z_std)
+        # ---- the loss tail: loss, psnr and the gradients of both colour maps
+        need = ops.classic_loss_tail_ws(N)
+        if self._ws is None or self._ws.numel() * 8 < need:
+            self._ws = torch.empty(need // 8, dtype=torch.float64, device=dev)
+        if Ni > 0:
+            out, g_rgb, g_rgb0 = ops.classic_loss_tail(rgb1, rgb0, tgt, ws=self._ws)
+        else:                                            # (the one-level render: its only colour map is the coarse pass's)
+            out, g_rgb0, g_rgb = ops.classic_loss_tail(rgb0, None, tgt, ws=self._ws)
+        if self.loss_scale != 1.0:
+            for g in (g_rgb, g_rgb0):
+                if g is not None:
+                    g.mul_(self.loss_scale)
+        self.last_grads = (g_rgb, g_rgb0)
+        ret["losses"] = out                              # {loss, img_loss, img_loss0, psnr}: stays on the device
+        # ---- backward: the fine pass, then the coarse one (autograd's order), each from its colour map's gradient alone
+
+        def level_bwd(net, raw, saved, nz, z, maps, g):
+            _, _, acc, w, depth = maps
+            d_raw = torch.zeros_like(raw)
+            ops.classic_composite_bwd(raw, nz, z, rays_d, self.white_bkgd, w, acc, depth, g, None, None, None, None, d_raw)
+            net.net.backward(d_raw, saved)
+        if Ni > 0:
+            level_bwd(fine, raw1, saved1, noise1, z_all, (rgb1, disp1, acc1, w1, depth1), g_rgb)
+            if on_done is not None and fine is not coarse:
+                on_done(1)
+        level_bwd(coarse, raw0, saved0, noise0, z_vals, (rgb0, disp0, acc0, w0, depth0), g_rgb0)
+        if on_done is not None:
+            on_done(0)
+        return out[0], ret
+
+    def loss_and_grads(self, ray_batch, target_rgb, t_rand=None, u=None, noise=None):
+        """forward, loss tail and backward: the gradients of the LOCAL mean are ADDED into every network's `arena.grad` (times
+        `loss_scale`); no exchange, no Adam.  -> (loss, out) as `step`"""
+        return self._forward_backward(ray_batch, target_rgb, t_rand, u, noise)
+
+    def _exchanges(self):
+        return [_GradExchange(x.net.arena, self.world, self.pg, self.single_rank_exchange) for x in self.nets]
+
+    def _update(self):
+        """one fused Adam launch per arena: folds the data-parallel mean, the loss scale, the non-finite policy and zero_grad"""
+        self.t += 1
+        scale = 1.0 / (self.world * self.loss_scale)
+        for x in self.nets:
+            x.adam(scale, self.nonfinite)
+            x.net.arena.bump()
+
+    def step(self, ray_batch, target_rgb, t_rand=None, u=None, noise=None):
+        """One training step on `ray_batch` [N, 8 | 11] (render_rays' rows; a classic.RayBatcher's) and `target_rgb` [N, 3]; neither is
+        written.  `t_rand` [N, N_samples] / `u` [N, N_importance] replace the torch.rand draws of render_rays; `noise` (one tensor
+        [N, N_samples], or a pair with the fine pass's [N, N_samples + N_importance]) replaces raw2outputs' randn * raw_noise_std and is
+        used as it is.  -> (loss, out): the loss as a device scalar, out = render_rays' maps (rgb_map, disp_map, acc_map, depth_map,
+        z_vals_map, weights, and with N_importance > 0 rgb0, disp0, acc0, z_std) plus `losses` = the device vector
+        {loss, img_loss, img_loss0, psnr}.  world > 1: every rank steps on its own shard and forms its own mean; the arenas' gradients are
+        summed over the ranks (the fine network's under the coarse backward pass) and Adam takes 1 / world of the sum."""
+        ex = self._exchanges()
+        loss, out = self._forward_backward(ray_batch, target_rgb, t_rand, u, noise, on_done=lambda i: ex[i](""))
+        for e in ex:
+            e.finish()
+        self._update()
+        return loss, out
+
+    # ---- hipGraph capture of the whole step --------------------------------------------------------------------------------------
+    def capture(self, ray_batch=None, target_rgb=None, warmup=3, batcher=None):
+        """Capture one full step (the torch RNG draws, forward, loss tail, backward, and for world 1 the Adam launches, with step count
+        and learning rate in device memory) in a hipGraph on one stream; `replay()` then runs a step with one graph launch.  Without a
+        batcher the graph reads the GIVEN tensors: refresh the batch by copying into them.  `batcher` (classic.RayBatcher): its draw
+        (`next_into`, one launch) is the first node, every replay trains on a fresh batch -- the k-th on the batch an eager batcher
+        draws at step s0 + k -- and `self.batch` = (ray_batch, target_rgb) are its buffers.  The `warmup` steps are real steps on the
+        capture batch: parameters, moments, step count and the batcher's counter are snapshotted before and restored after them
+        (the torch RNG does advance).  world > 1 (every rank calls capture / replay together): the graph ends with the backward, and
+        `replay()` follows it with the all-reduces and the Adam launches."""
+        if batcher is None and (ray_batch is None or target_rgb is None):
+            raise ValueError("ClassicTrainer.capture: give ray_batch= and target_rgb=, or batcher=")
+        dev = self.network_fn.arena.flat.device
+        buf = None
+        if batcher is not None:
+            buf = batcher.buffers()
+            ray_batch, target_rgb = buf["rays"], buf["rgb"]
+        snaps = [x.snapshot() for x in self.nets]
+        if self.world == 1:
+            for x in self.nets:
+                x.arm()
+        self._batcher, self.batch = batcher, (ray_batch, target_rgb)
+        if batcher is not None:
+            b_snap = (batcher.counter.clone(), batcher.step)
+
+        def draw():
+            if batcher is not None:
+                batcher.next_into(buf)
+        side = torch.cuda.Stream(device=dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side):                    # warm-up on a side stream
+            for _ in range(warmup):
+                draw()
+                self.step(ray_batch, target_rgb)
+        torch.cuda.current_stream(dev).wait_stream(side)
+        for x, snap in zip(self.nets, snaps):
+            x.restore(snap)
+            x.net.arena.bump()                           # (the restored parameters are new values to the packed operands)
+        if batcher is not None:                          # capturing uses up no draws
+            batcher.counter.copy_(b_snap[0])
+        self._graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self._graph):
+            draw()
+            if self.world == 1:
+                self._graph_loss, self._graph_outs = self.step(ray_batch, target_rgb)
+            else:
+                self._graph_loss, self._graph_outs = self._forward_backward(ray_batch, target_rgb)
+        if batcher is not None:
+            batcher._step = b_snap[1]
+        if self.world == 1:
+            self.t -= 1                                  # capturing records the step, it does not run it
+        return self._graph_loss
+
+    def replay(self):
+        """One captured step.  -> (loss, out): the same device tensors every time, overwritten by each replay."""
+        if self._batcher is not None:
+            self._batcher.advance_host(1)                # the graph's first node drew the batch and advanced the device counter
+        if self.world == 1:
+            for x in self.nets:
+                x.lr_dev.fill_(self.lr)                  # the graph reads the learning rate from the device
+            self._graph.replay()
+            self.t += 1
+        else:
+            self._graph.replay()                         # forward + loss tail + backward of this rank's shard
+            for e in self._exchanges():
+                e.finish()                               # one all-reduce per gradient arena
+            self._update()
+        return self._graph_loss, self._graph_outs
