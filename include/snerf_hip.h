@@ -1049,6 +1049,26 @@ int snerf_reproj_conf(const void* images, int images_u8, const float* depths, co
 /* bytes of scratch snerf_reproj_conf needs for H x W images (0 for H or W < 1) */
 long snerf_reproj_conf_ws(int H, int W);
 
+/* Frame metrics on the device: what image.MetricHarness (s-nerfpp/zipnerf/internal/image.py:110-125: skimage's PSNR of the uint8 RGB
+ * images, its SSIM of their 8-bit grey images) and eval.py's mse_to_psnr (s-nerf/eval.py:152) compute per rendered frame, F frames per
+ * call.  pred [F,H,W,3] fp32; gt [F,H,W,3] fp32 or uint8 (gt_u8 = 1); out [F,5] DOUBLE: mse_f, psnr_f, mse_u8, psnr_u8, ssim.
+ * Quantisation q(x) = trunc(x * 255.f) (one fp32 product, truncated toward zero; below 0 -> 0, above 255 -> 255, NaN -> 0: numpy's
+ * cast is undefined outside (-1, 256)); a uint8 gt is used as it is.  mse_f: d = pred - g and d * d as separate fp32 ops, g = gt or
+ * float32(k / 255.0) for a uint8 gt, the squares summed in double, over 3 H W; psnr_f = -10 / ln 10 * ln(mse_f).  mse_u8: the squared
+ * differences of the quantised samples summed as an integer, over 3 H W; psnr_u8 = 10 log10(255^2 / mse_u8) (+inf for equal images).
+ * Grey = (r wr + g wg + b wb + (1 << (shift - 1))) >> shift on the quantised channels, gray_w = {wr, wg, wb, shift} (a HOST array) or
+ * NULL for {9798, 19235, 3735, 15}, OpenCV 4's 8-bit RGB2GRAY ({4899, 9617, 1868, 14}: OpenCV 3's).  ssim: skimage's
+ * structural_similarity(data_range = 255) defaults on the grey images: 7 x 7 uniform window, K1 = 0.01, K2 = 0.03, sample covariance
+ * (49 / 48), a border of 3 cropped; window sums exact in int32, the rest in double, the mean over the (H - 6)(W - 6) cropped pixels.
+ * ws: >= snerf_frame_metrics_ws(F, H, W) bytes of device scratch, 8-byte aligned.  No host read, no sync, no atomics: every sum runs in
+ * an order that depends on the shape only (bit-reproducible), and the call can be captured in a graph.  Bad arguments (a null pred /
+ * gt / ws / out, F < 1 or > 65535, H or W < 7: the window does not fit, where skimage raises; a short or misaligned workspace; a shift
+ * outside 1..20, a negative weight or weights whose sum exceeds 1 << shift) return 1 before any launch. */
+int snerf_frame_metrics(const float* pred, const void* gt, int gt_u8, int F, int H, int W, const int* gray_w, void* ws, long ws_bytes,
+                        double* out, void* stream);
+/* bytes of scratch snerf_frame_metrics needs (0 for F < 1 or > 65535, H < 7 or W < 7) */
+long snerf_frame_metrics_ws(int F, int H, int W);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1840,6 +1840,40 @@ def reproj_conf(images, depths, poses, intrinsics, base, neighbours, modes, tau,
     return out
 
 
+FRAME_METRIC_NAMES = ("mse_f", "psnr_f", "mse_u8", "psnr_u8", "ssim")      # the columns of snerf_frame_metrics' out
+
+
+def frame_metrics_ws(F, H, W):
+    """bytes of scratch frame_metrics needs for F frames of H x W (snerf_frame_metrics_ws; 0 where the call would be refused)"""
+    return int(_lib.query("snerf_frame_metrics_ws", int(F), int(H), int(W)))
+
+
+def frame_metrics(pred, gt, gray_w=None, out=None, ws=None):
+    """snerf_frame_metrics: pred [H,W,3] or [F,H,W,3] fp32 against gt of the same shape, fp32 or uint8 -> float64 [F,5] on the device in
+    the order of FRAME_METRIC_NAMES (float MSE / PSNR of eval.py, uint8 MSE / PSNR and grey SSIM of image.MetricHarness).  gray_w:
+    (wr, wg, wb, shift) python ints, None = the library's default (OpenCV 4's RGB2GRAY).  No host read or sync; graph-capturable when
+    `out` (float64 [F,5]) and `ws` (uint8, >= frame_metrics_ws(F, H, W) elements) are preallocated."""
+    _f32c(pred)
+    u8 = _u8_or_f32(gt)
+    assert pred.dim() in (3, 4) and pred.shape[-1] == 3 and gt.shape == pred.shape, "pred [H,W,3] or [F,H,W,3] fp32, gt of the same shape"
+    F = 1 if pred.dim() == 3 else pred.shape[0]
+    H, W = pred.shape[-3], pred.shape[-2]
+    need = frame_metrics_ws(F, H, W)
+    assert need > 0, "frame_metrics: 1 <= F <= 65535 frames of at least 7 x 7 pixels (the 7 x 7 SSIM window must fit)"
+    if out is None:
+        out = torch.empty(F, 5, dtype=torch.float64, device=pred.device)
+    assert out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and tuple(out.shape) == (F, 5)
+    if ws is None:
+        ws = torch.empty(need, dtype=torch.uint8, device=pred.device)
+    assert ws.is_cuda and ws.dtype == torch.uint8 and ws.is_contiguous() and ws.numel() >= need
+    gw = None
+    if gray_w is not None:
+        assert len(gray_w) == 4, "gray_w: (wr, wg, wb, shift)"
+        gw = (ctypes.c_int * 4)(*[int(v) for v in gray_w])
+    _lib.call("snerf_frame_metrics", _p(pred), _p(gt), u8, F, H, W, gw, _p(ws), ws.numel(), _p(out), _stream())
+    return out
+
+
 def zip_ray_batch(images, depths, semantics, masks, pixtocams, camtoworlds, local2global, near, far, border, patch_size, single_image, seed,
                   counter, n, i0, i1, out):
     """snerf_zip_ray_batch: rows [i0, i1) of step counter[0]'s global batch of n rays into the preallocated `out` (dict: origins,
