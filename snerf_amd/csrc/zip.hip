@@ -3194,7 +3194,9 @@ __global__ __launch_bounds__(256) void zip_composite_fwd_kernel(ZipComp a) {
     }
     const float incl = wave_incl_scan_add(inf_last ? 0.f : dd, lane);
     const float excl = carry + (incl - (inf_last ? 0.f : dd));
-    const float alpha = inf_last ? 1.f : 1.f - expf(-dd);
+    // expm1f, not 1 - expf: for dd << 1 the difference keeps only the rounding of expf near 1, and that error has the same sign for
+    // every thin interval of a ray, so it adds up in acc / rgb / depth instead of averaging out (tests/test_zip_composite_f64.py)
+    const float alpha = inf_last ? 1.f : -expm1f(-dd);
     const float w = ok ? alpha * expf(-excl) : 0.f;
     if (ok) a.weights[ray * S + i] = w;
     s_acc += w;

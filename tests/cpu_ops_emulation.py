@@ -580,12 +580,18 @@ def mip_loss_tail(rgb, tgt, dist1, dist0, tdepth, conf, s_f, w_f, s_c, w_c, disp
     return out.to(dev), g_rgb, gd1, gd0, gw
 
 
+def _sem_float(t):
+    """fp32 arithmetic on 16-bit and fp32 logits, as the kernel; float64 logits stay float64 (the high-precision reference of
+    tests/test_zip_composite_f64.py)."""
+    return t if t.dtype == torch.float64 else t.float()
+
+
 def semantic_composite_fwd(weights, logits, C, softmax, row_index=None):
     if row_index is not None:
         ri = row_index.reshape(-1).long()
-        logits = torch.where((ri >= 0)[:, None], logits[ri.clamp(min=0), :C].float(), torch.zeros(1, C))
+        logits = _sem_float(logits[ri.clamp(min=0), :C]) * (ri >= 0)[:, None]
         weights = weights * (ri >= 0).reshape(weights.shape)
-    v = logits[:, :C].float().reshape(weights.shape[0], weights.shape[1], C)
+    v = _sem_float(logits[:, :C]).reshape(weights.shape[0], weights.shape[1], C)
     if softmax:
         v = torch.softmax(v, -1)
     return (weights[..., None] * v).sum(-2)
@@ -593,7 +599,7 @@ def semantic_composite_fwd(weights, logits, C, softmax, row_index=None):
 
 def semantic_composite_bwd(weights, logits, g_sem, C, softmax, d_logits, want_g_w=False):
     R, S = weights.shape
-    v = logits[:, :C].float().reshape(R, S, C)
+    v = _sem_float(logits[:, :C]).reshape(R, S, C)
     if softmax:
         p = torch.softmax(v, -1)
         dot = (p * g_sem[:, None, :]).sum(-1, keepdim=True)
