@@ -1069,6 +1069,45 @@ int snerf_frame_metrics(const float* pred, const void* gt, int gt_u8, int F, int
 /* bytes of scratch snerf_frame_metrics needs (0 for F < 1 or > 65535, H < 7 or W < 7) */
 long snerf_frame_metrics_ws(int F, int H, int W);
 
+/* First-hit ray / triangle-mesh tracer (csrc/meshtrace.hip): what `raytracing.RayTracer(vertices, faces).trace(ray_o, ray_d)` gives
+ * s-nerfpp/stage1_code/utils_render.py:839-868 (the mesh depth behind fg_depth of snerf_fg_paste) and stage0_code/utils_render.py:755-776
+ * (the instance mask).  That library is not in the reference tree: its behaviour at edges, its normals' orientation and whether it
+ * accepts hits beyond its max depth of 100 are NOT pinned.  Defined here: a hit needs 0 < t < t_max with t the ray parameter of the
+ * un-normalised direction; the nearest hit wins; a miss has face id -1 and zero position and normal.  The test is watertight (Woop's
+ * sheared edge functions, exactly antisymmetric per edge: a ray through a shared edge or a vertex of a closed surface hits).
+ *
+ * The mesh is handed over ORDERED: faces [F,3] int32 sorted by the caller so that neighbours in the array are neighbours in space (the
+ * Morton code of the object-space centroids; any order is correct, a bad one is slow), face_ids [F] int32 = the caller's own id of
+ * each ordered face (NULL: the ordered index).  snerf_mesh_prepare applies transform (12 floats in DEVICE memory, a row-major 3 x 4
+ * affine map; NULL: none) to vertices [V,3] fp32 and fills ws (>= snerf_mesh_ws_bytes(F) bytes of device memory, 16-byte aligned)
+ * with the triangle records and the boxes of the 64-triangle chunks and of the groups of 64 chunks; it is F triangles of work and is
+ * repeated for every new transform.  A face with an index outside [0, V), a non-finite transformed vertex or a zero cross product is
+ * dropped there (never hit); no vertex is read through an unchecked index.  F = 0 is valid (ws is not touched and may be NULL, here
+ * and in the trace entries: everything misses).  Bad arguments (F or V < 0, a null faces / ws, null vertices with V > 0, a short or
+ * misaligned ws) return 1 before any launch. */
+long snerf_mesh_ws_bytes(int F);
+int snerf_mesh_prepare(const float* vertices, int V, const int* faces, const int* face_ids, int F, const float* transform, void* ws,
+                       long ws_bytes, void* stream);
+/* General rays: rays_o, rays_d [R,3] fp32 -> depth [R] = t of the nearest hit or t_max, and, each optional (NULL), face_id [R] int32,
+ * positions [R,3] = o + t d, normals [R,3] = the unit normal (b - a) x (c - a) of the hit face, not turned towards the ray.  64
+ * consecutive rays share a wave.  A ray with a non-finite component or a zero direction misses.  flags: bit 0 = no box culling (every
+ * chunk is entered: the all-pairs flavour, for measurements), bit 1 = chunks read through wave-uniform loads instead of staged in LDS
+ * (same results, slower with culling).  No host read, no atomics; what a ray returns does not depend on the other rays of the call.  R = 0 is valid.  Bad
+ * arguments (F or R < 0, t_max not a positive finite number, unknown flag bits, a null rays_o / rays_d / depth, a null or misaligned
+ * ws with F > 0) return 1 before any launch. */
+int snerf_mesh_trace(const void* ws, int F, const float* rays_o, const float* rays_d, long R, float t_max, int flags, float* depth,
+                     int* face_id, float* positions, float* normals, void* stream);
+/* Camera rays generated in the kernel, one 8 x 8 pixel tile per wave: pixel (x, y) sends d = (((x + c) - cx) / fx, -(((y + c) - cy) / fy), -1)
+ * from the origin, c = 0.5 with pixel_center (stage 0's get_ray_directions) and 0 without (stage 1's get_ray_d_from_xy), in fp32
+ * operation by operation as written, so t is the z-depth; the intersection routine is snerf_mesh_trace's (the same bits for the same
+ * rays).  mask [H,W,3] uint8 or NULL: only pixels with channel 0 > 0 are traced, the others get depth 0 and hit 0.  depth [H,W] = t of a
+ * hit, miss_value on a traced miss (stage 1: t_max = 99, miss_value = 0.1 is `depth[depth >= 99.] = .1`); hit [H,W,3] uint8 (optional)
+ * = 255 on a hit (stage 0's mask with t_max = 100).  flags as above.  H = 0 or W = 0 is valid.  Bad arguments (F, H or W < 0, H W >=
+ * 2^31, fx or fy zero or not finite, cx or cy not finite, t_max not a positive finite number, unknown flag bits, a null depth, a null
+ * or misaligned ws with F > 0) return 1 before any launch. */
+int snerf_mesh_trace_pinhole(const void* ws, int F, float fx, float fy, float cx, float cy, int pixel_center, int H, int W,
+                             const void* mask, float t_max, float miss_value, int flags, float* depth, void* hit, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,8 +5,14 @@ utils_render.py:826-1005 handle_occlusion_paste, :306-324 get_bound_im, :327-361
 ip_utils.py:10-19 set_diff.  There every step round-trips PIL images and numpy index lists on the host; here the frame (background
 rgb, depth, semantic) stays resident in HBM as uint8 / float tensors and every step is one launch.
 
-Not here (they stay with the caller): mesh placement and the ray-traced mesh depth (`raytracing.RayTracer`, nvdiffrast, trimesh --
-`fg_depth` is an input), the bounding-box export, and `handle_lighting` (cv2's 8-bit HSV round trip)."""
+The mesh depth behind `fg_depth` and the stage-0 instance masks come from `snerf_amd.meshtrace.RayTracer` (`mesh_depth`,
+`mask_from_mesh`: snerf_mesh_prepare + snerf_mesh_trace_pinhole, scratch snerf_mesh_ws_bytes; general rays: snerf_mesh_trace), so
+`render_image` -> mesh depth -> paste -> boundary algebra -> `FrameWriter` never leaves the device.  The `raytracing` library the
+reference calls is not in its tree: see the meshtrace module docstring for what is and is not pinned.
+
+Not here (they stay with the caller): mesh loading and placement (trimesh), the vehicle image (nvdiffrast), the bounding-box export,
+and `handle_lighting` (cv2's 8-bit HSV round trip)."""
+import numpy as np
 import torch
 
 from . import _lib
@@ -35,6 +41,42 @@ def handle_occlusion_paste(bg_im, vehicle_im, mask_im, depth_mat, semantic_mat, 
               SEMANTIC_ID[category], int(person), _p(cnt), _stream())
     c = cnt.double()
     return 1 - c[1] / (c[0] + 1)
+
+
+def _intrinsic(intrinsic):
+    """(fx, fy, cx, cy) as python floats from a 3 x 3 (or larger) intrinsic matrix held on the HOST (numpy, nested lists, a CPU tensor)"""
+    assert not (torch.is_tensor(intrinsic) and intrinsic.is_cuda), "intrinsic: host values (a device matrix would cost a sync per call)"
+    K = np.asarray(intrinsic, dtype=np.float64)
+    return float(K[0, 0]), float(K[1, 1]), float(K[0, 2]), float(K[1, 2])
+
+
+_FLIP = ((1., 0., 0., 0.), (0., -1., 0., 0.), (0., 0., -1., 0.), (0., 0., 0., 1.))      # utils_render.py:857-862
+_FLIP_ON = {}                                                                            # device -> the flip as a [4,4] tensor there (uploaded once)
+
+
+def mesh_depth(tracer, intrinsic, H, W, mask_im, transform=None):
+    """utils_render.py:839-868,887-906: fg_depth [H,W] fp32 for handle_occlusion_paste -- the z-depth of `tracer`'s mesh along the ray
+    of every pixel with mask_im[..., 0] > 0, from integer pixel coordinates (get_ray_d_from_xy ignores use_pixel_centers); 0.1 where
+    the ray misses or the depth is >= 99 (`depth[depth >= 99.] = .1`), 0 outside the mask.  `transform` (3 x 4 or 4 x 4, host or device)
+    is what places the tracer's mesh into `mesh_in_cam_coord`; the reference's diag(1, -1, -1) flip is composed in here.  No host sync."""
+    from . import meshtrace
+    _u8(mask_im, (H, W, 3))
+    fx, fy, cx, cy = _intrinsic(intrinsic)
+    flip = _FLIP_ON.get(tracer.device)
+    if flip is None:
+        flip = _FLIP_ON[tracer.device] = torch.tensor(_FLIP, dtype=torch.float32, device=tracer.device)
+    t = meshtrace._as_transform(transform, tracer.device)
+    if t is not None:
+        flip = flip[:3, :3] @ t                        # the flip has no translation: [3,3] @ [3,4]
+    return tracer.trace_pinhole(fx, fy, cx, cy, H, W, False, mask=mask_im, transform=flip, t_max=99., miss_value=.1)[0]
+
+
+def mask_from_mesh(tracer, resolution, intrinsic, transform=None):
+    """stage0_code/utils_render.py:755-776 get_mask_from_mesh_use_inv: [H,W,3] uint8, 255 where the pixel-centre ray of resolution =
+    (W, H) hits the mesh (`depth < 100`).  The mesh is used as given (camera coordinates, no flip), after `transform` if there is one."""
+    W, H = resolution
+    fx, fy, cx, cy = _intrinsic(intrinsic)
+    return tracer.trace_pinhole(fx, fy, cx, cy, int(H), int(W), True, transform=transform, t_max=100., want_hit=True)[1]
 
 
 def bound_radius(mask_im, category="vehicle"):
@@ -75,7 +117,9 @@ def fuse_bound_and_im(fuse_im, bound_im):
 
 def composite_frame(bg_im, depth_mat, semantic_mat, instances):
     """The instance loop of generate_images.py:80-166 for one frame.  `instances`: iterable (already in the reference's occlusion
-    order) of dict(image [H,W,3] u8, mask [H,W,3] u8, fg_depth [H,W] f32 or None, category, r (optional band width)).
+    order) of dict(image [H,W,3] u8, mask [H,W,3] u8, fg_depth [H,W] f32 or None, category, r (optional band width)); instead of
+    fg_depth an instance may carry mesh = (meshtrace.RayTracer, transform or None) and intrinsic (3 x 3, host): its depth is then
+    mesh_depth(tracer, intrinsic, H, W, mask, transform), traced here.
     In place on bg_im / depth_mat / semantic_mat; returns dict(fuse, mask, bound, occluded_mask, depth, semantic, occlusion [per
     instance], instance_masks, instance_bounds) = the images the reference saves per frame (:153-154,186-196)."""
     total_mask, total_bound, total_occluded = torch.zeros_like(bg_im), torch.zeros_like(bg_im), torch.zeros_like(bg_im)
@@ -88,7 +132,11 @@ def composite_frame(bg_im, depth_mat, semantic_mat, instances):
         # the depth test works on a copy of the mask (utils_render.py:280: np.array(mask_im)); the band and the frame's mask come from
         # the instance's full mask, the depth-tested one only feeds the `occluded_mask` image of vehicles (generate_images.py:162-166)
         tested = inst["mask"].clone()
-        occ.append(handle_occlusion_paste(bg_im, inst["image"], tested, depth_mat, semantic_mat, inst.get("fg_depth"), cat))
+        fg_depth = inst.get("fg_depth")
+        if fg_depth is None and inst.get("mesh") is not None and cat != "person":
+            tracer, transform = inst["mesh"]
+            fg_depth = mesh_depth(tracer, inst["intrinsic"], depth_mat.shape[0], depth_mat.shape[1], inst["mask"], transform)
+        occ.append(handle_occlusion_paste(bg_im, inst["image"], tested, depth_mat, semantic_mat, fg_depth, cat))
         bound, mask_d = get_bound_im(inst["mask"], r, return_mask_diff=True)
         accumulate(total_mask, total_bound, bound, mask_d)
         if cat == "vehicle":

@@ -2081,3 +2081,68 @@ def semantic_composite_bwd(weights, logits, g_sem, C, softmax, d_logits, want_g_
     _lib.call("snerf_semantic_composite_bwd", _p(weights), _p(logits), logits.stride(0), _zip_dt(logits), _p(g_sem), R, S, C, int(bool(softmax)),
               _p(d_logits), d_logits.stride(0), _p(g_w), _stream())
     return g_w
+
+
+MESH_NO_CULL, MESH_UNIFORM = 1, 2       # flags of the trace entries: every chunk entered / chunks read by wave-uniform loads, not staged in LDS (both: measurements)
+
+
+def mesh_ws_bytes(F):
+    """bytes of device memory mesh_prepare fills for F faces (snerf_mesh_ws_bytes; 0 for F <= 0)"""
+    return int(_lib.query("snerf_mesh_ws_bytes", int(F)))
+
+
+def _mesh_ws(ws, F):
+    assert F == 0 or (ws is not None and ws.is_cuda and ws.dtype == torch.uint8 and ws.is_contiguous() and ws.numel() >= mesh_ws_bytes(F)), \
+        "ws: uint8 CUDA tensor of >= mesh_ws_bytes(F) elements, filled by mesh_prepare"
+    return ws
+
+
+def mesh_prepare(vertices, faces, face_ids=None, transform=None, ws=None):
+    """snerf_mesh_prepare: vertices [V,3] fp32, faces [F,3] int32 in the order the tracer walks them (meshtrace.RayTracer sorts them by
+    Morton code once), face_ids [F] int32 = the caller's id of each ordered face (None: its position), transform = a [3,4] fp32 DEVICE
+    tensor or None -> ws (uint8, mesh_ws_bytes(F) elements; allocated when None) holding the transformed triangles and the chunk and
+    group boxes.  Faces with an index outside [0, V), a non-finite vertex or no area are dropped by the kernel.  No host read."""
+    _f32c(vertices)
+    assert vertices.dim() == 2 and vertices.shape[1] == 3, "vertices [V,3] fp32"
+    assert faces.is_cuda and faces.dtype == torch.int32 and faces.is_contiguous() and faces.dim() == 2 and faces.shape[1] == 3, "faces [F,3] int32"
+    V, F = vertices.shape[0], faces.shape[0]
+    if face_ids is not None:
+        assert face_ids.is_cuda and face_ids.dtype == torch.int32 and face_ids.is_contiguous() and face_ids.numel() == F, "face_ids [F] int32"
+    if transform is not None:
+        _f32c(transform)
+        assert tuple(transform.shape) == (3, 4), "transform [3,4] fp32 on the device"
+    if ws is None:
+        ws = torch.empty(mesh_ws_bytes(F), dtype=torch.uint8, device=vertices.device)
+    _mesh_ws(ws, F)
+    _lib.call("snerf_mesh_prepare", _p(vertices), V, _p(faces), _p(face_ids), F, _p(transform), _p(ws), ws.numel(), _stream())
+    return ws
+
+
+def mesh_trace(ws, F, rays_o, rays_d, t_max=100., positions=True, normals=True, flags=0):
+    """snerf_mesh_trace: rays_o, rays_d [R,3] fp32 against the prepared mesh -> (depth [R] = t of the nearest hit with 0 < t < t_max, else
+    t_max; face_id [R] int32 in the caller's numbering, -1 on a miss; positions [R,3] or None; normals [R,3] or None).  No host read."""
+    _f32c(rays_o); _f32c(rays_d)
+    assert rays_o.dim() == 2 and rays_o.shape[1] == 3 and rays_d.shape == rays_o.shape, "rays_o, rays_d [R,3] fp32"
+    R, dev = rays_o.shape[0], rays_o.device
+    depth = torch.empty(R, dtype=torch.float32, device=dev)
+    face_id = torch.empty(R, dtype=torch.int32, device=dev)
+    pos = torch.empty(R, 3, dtype=torch.float32, device=dev) if positions else None
+    nrm = torch.empty(R, 3, dtype=torch.float32, device=dev) if normals else None
+    _lib.call("snerf_mesh_trace", _p(_mesh_ws(ws, F)), int(F), _p(rays_o), _p(rays_d), R, float(t_max), int(flags), _p(depth), _p(face_id), _p(pos),
+              _p(nrm), _stream())
+    return depth, face_id, pos, nrm
+
+
+def mesh_trace_pinhole(ws, F, fx, fy, cx, cy, pixel_center, H, W, mask=None, t_max=100., miss_value=100., want_hit=False, flags=0, device=None):
+    """snerf_mesh_trace_pinhole: the rays d = ((x + c - cx) / fx, -(y + c - cy) / fy, -1) of an H x W camera at the origin (c = 0.5 with
+    pixel_center), generated in the kernel -> (depth [H,W] fp32: t = z-depth of a hit, miss_value on a traced miss, 0 outside `mask`
+    ([H,W,3] uint8, channel 0 > 0 = traced; None: every pixel); hit [H,W,3] uint8 = 255 on a hit, or None).  No host read."""
+    H, W = int(H), int(W)
+    dev = ws.device if ws is not None else (mask.device if mask is not None else torch.device("cuda", torch.cuda.current_device()) if device is None else device)
+    if mask is not None:
+        assert mask.is_cuda and mask.dtype == torch.uint8 and mask.is_contiguous() and tuple(mask.shape) == (H, W, 3), "mask [H,W,3] uint8"
+    depth = torch.empty(H, W, dtype=torch.float32, device=dev)
+    hit = torch.empty(H, W, 3, dtype=torch.uint8, device=dev) if want_hit else None
+    _lib.call("snerf_mesh_trace_pinhole", _p(_mesh_ws(ws, F)), int(F), float(fx), float(fy), float(cx), float(cy), int(bool(pixel_center)), H, W,
+              _p(mask), float(t_max), float(miss_value), int(flags), _p(depth), _p(hit), _stream())
+    return depth, hit
