@@ -1107,6 +1107,41 @@ int snerf_mesh_trace(const void* ws, int F, const float* rays_o, const float* ra
  * or misaligned ws with F > 0) return 1 before any launch. */
 int snerf_mesh_trace_pinhole(const void* ws, int F, float fx, float fy, float cx, float cy, int pixel_center, int H, int W,
                              const void* mask, float t_max, float miss_value, int flags, float* depth, void* hit, void* stream);
+/* The instance image and mask of s-nerfpp/api_code/mesh_renderer.py:36-88 render(cam) from the prepared mesh: the pixel-centre rays of
+ * snerf_mesh_trace_pinhole (pixel_center = 1, no mask; row 0 on top, so the reference's vertical flip has no counterpart) and the same
+ * walk, so hit / miss / face are that entry's bits for the same ws, camera and t_max.  nvdiffrast and kaolin are not in the reference
+ * tree: their fill rule at an edge and their near plane are NOT pinned.  The winning triangle is intersected once more with the same
+ * sheared edge functions; (u, v, w) / ((u + v) + w) are the barycentrics of its vertices (a, b, c), perspective-correct by construction.
+ * The attribute source is exactly one of
+ *   vertex colours: vertex_color [V,3] fp32 through faces [F,3] int32 (the ORDERED faces snerf_mesh_prepare got);
+ *   textures: uvs [U,2] fp32 through face_uvs_idx [F,3] int32 and face_material_idx [F] int32, both in the tracer's order; a uv index
+ *     outside [0, U) means uv = (0, 0) (the reference's appended zero row), a material index outside [0, M) leaves the colour 0 with the
+ *     mask at 255.  texels: n_texels x (r, g, b, 0) fp32, 16-byte aligned, all materials back to back; materials [M,4] int32, 16-byte
+ *     aligned = (texel offset, Hm, Wm, 0) per material, row-major maps, a 1 x 1 map being a constant Kd; an entry that does not lie
+ *     inside [0, n_texels) gives colour 0.  The fetch is grid_sample(map, (2u - 1, -(2v - 1)), 'bilinear', align_corners = False,
+ *     padding_mode = 'border') in fp32 operation by operation: ix = ((gx + 1) Wm - 1) / 2 clipped to [0, Wm - 1], iy likewise, four
+ *     taps accumulated nw, ne, sw, se, a tap outside the map contributing nothing.
+ * No attribute is read through an unchecked index.  Outputs, each optional (NULL) but image: image [H,W,3] uint8 = floor(255 clamp(c, 0,
+ * 1) + 0.5) (torchvision's save_image; NaN -> 0), image_f [H,W,3] fp32 = the clamped colour (0 on a miss), mask [H,W,3] uint8 = 255 / 0,
+ * depth [H,W] fp32 = t (the z-depth) or miss_value, face_id [H,W] int32 in the caller's numbering or -1.
+ * validate != 0 applies mesh_renderer.py:44-53: a frame whose mask touches both the first and the last row, or both the first and the
+ * last column, or covers more than half of the pixels (as the integer 2 count > H W, where the reference divides twice in fp32) is
+ * cleared: image, image_f and mask to 0, depth to miss_value, face_id to -1.  Every wave stores one record (hit count, border bits)
+ * with plain stores into scratch (>= snerf_mesh_render_scratch_bytes(H, W) bytes of device memory, 8-byte aligned), a one-block launch
+ * reduces them in a fixed order and a finishing launch clears: no host read, no atomics, independent of launch order.  validate = 0
+ * skips both launches and does not touch scratch.  flags as for snerf_mesh_trace.  H = 0 or W = 0 is valid; F = 0 is valid (everything
+ * misses, the frame is valid, the attribute arguments are not looked at).  Bad arguments (F, H, W, V, U or n_texels < 0, H W >= 2^31,
+ * fx or fy zero or not finite, cx or cy not finite, t_max not a positive finite number, unknown flag bits, a null image, with F > 0:
+ * both or neither of vertex_color and face_uvs_idx, null faces in colour mode, M < 1 or a null / misaligned table or texel buffer or a
+ * null face_material_idx in texture mode, a null or misaligned ws; with validate a null, misaligned or short scratch) return 1 before
+ * any launch. */
+int snerf_mesh_render_pinhole(const void* ws, int F, float fx, float fy, float cx, float cy, int H, int W, float t_max, float miss_value,
+                              int flags, const int* faces, const float* vertex_color, int V, const float* uvs, int U,
+                              const int* face_uvs_idx, const int* face_material_idx, const void* texels, long n_texels,
+                              const int* materials, int M, int validate, void* scratch, long scratch_bytes, void* image, float* image_f,
+                              void* mask, float* depth, int* face_id, void* stream);
+/* bytes of scratch the validity rule of snerf_mesh_render_pinhole needs (0 for H or W <= 0) */
+long snerf_mesh_render_scratch_bytes(int H, int W);
 
 #ifdef __cplusplus
 }

@@ -27,6 +27,9 @@
 // t, far more than the shear's rounding.  Degenerate faces (an index outside [0, V), a non-finite vertex, a zero cross product) are
 // stored as zero records that no ray hits and are left out of the boxes; a ray with a non-finite component or a zero direction hits
 // nothing.
+//
+// The renderer at the end of the file (snerf_mesh_render_pinhole: the instance image and mask of api_code/mesh_renderer.py) shades the
+// pinhole entry's first hit; it shares the walk and the intersection routine, so its visibility is the tracer's bit for bit.
 #include "common.h"
 #include <float.h>
 #include <math.h>
@@ -362,5 +365,207 @@ extern "C" int snerf_mesh_trace_pinhole(const void* ws, int F, float fx, float f
   hipStream_t st = (hipStream_t)stream;
   if (flags & MT_UNIFORM) hipLaunchKernelGGL(mesh_trace_pinhole_kernel<false>, dim3(gx, gy), dim3(64), 0, st, m, a);
   else                    hipLaunchKernelGGL(mesh_trace_pinhole_kernel<true>, dim3(gx, gy), dim3(64), 0, st, m, a);
+  return snerf_check_launch();
+}
+
+// ---- the renderer: instance image and mask of mesh_renderer.py:render ------------------------------------------------------------------------
+// Reference counterpart: s-nerfpp/api_code/mesh_renderer.py:36-88 (nvdiffrast rasterize + interpolate, kaolin camera; neither library is in
+// the reference tree, so their fill rule at an edge and their near plane are not pinned).  Visibility is mesh_trace_pinhole_kernel's with
+// pixel centres: the same ray arithmetic and the same walk, so hit / miss / face are its bits.  The winning record is then intersected
+// once more with mt_hit's sheared edge functions; (u, v, w) / ((u + v) + w) are the barycentrics of (a, b, c) at the hit point in 3-D,
+// i.e. perspective-correct.  Attributes: vertex colours through the ordered faces, or uvs through face_uvs_idx and one bilinear fetch
+// that follows grid_sample(mode = 'bilinear', align_corners = False, padding_mode = 'border') operation by operation.  Every index is
+// checked before it is used.  Frame validity (mesh_renderer.py:44-53): one record per wave with plain stores, a one-block reduction in
+// a fixed order, a finishing launch that clears an invalid frame: no atomics, no host read.
+#define MT_REC_TOP 1
+#define MT_REC_BOTTOM 2
+#define MT_REC_LEFT 4
+#define MT_REC_RIGHT 8
+#define MT_SCRATCH_HEAD 16      // bytes in front of the tile records: the verdict (int; 1 = the frame is cleared)
+
+struct MtRenderArgs {
+  float fx, fy, cx, cy; int H, W; float t_max, miss_value; int flags;
+  const int* faces; const float* vcolor; int V;                               // vertex-colour mode (vcolor != nullptr)
+  const float* uvs; int U; const int* face_uvs; const int* face_mat;          // texture mode
+  const float4* texels; long n_texels; const int4* mats; int M;               // texels (r, g, b, 0); mats[i] = (texel offset, Hm, Wm, 0)
+  int2* records;                                                              // per tile (hit count, border bits), or nullptr
+  unsigned char* image; float* image_f; unsigned char* mask; float* depth; int* face_id;
+};
+
+// the barycentrics of (a, b, c) for a record the ray has hit: mt_hit's arithmetic, runtime axis
+__device__ __forceinline__ void mt_bary(const float4 a, const float4 b, const float4 c, const MtRay& r, float& b0, float& b1, float& b2) {
+  float ax, ay, az, bx, by, bz, cx, cy, cz;
+  mt_perm<-1>(r.kz, a.x - r.ox, a.y - r.oy, a.z - r.oz, ax, ay, az);
+  mt_perm<-1>(r.kz, b.x - r.ox, b.y - r.oy, b.z - r.oz, bx, by, bz);
+  mt_perm<-1>(r.kz, c.x - r.ox, c.y - r.oy, c.z - r.oz, cx, cy, cz);
+  ax = ax - r.sx * az; ay = ay - r.sy * az;
+  bx = bx - r.sx * bz; by = by - r.sy * bz;
+  cx = cx - r.sx * cz; cy = cy - r.sy * cz;
+  const float u = cx * by - cy * bx, v = ax * cy - ay * cx, w = bx * ay - by * ax;
+  const float det = (u + v) + w;                                                // != 0: the record was accepted
+  b0 = u / det; b1 = v / det; b2 = w / det;
+}
+
+// grid_sample's bilinear fetch with border padding at (u, v) in [0, 1]^2 coordinates: gx = 2u - 1, gy = -(2v - 1)
+__device__ __forceinline__ void mt_texture(const float4* __restrict__ tex, int Hm, int Wm, float u, float v, float& cr, float& cg, float& cb) {
+  const float gx = u * 2.f - 1.f, gy = -(v * 2.f - 1.f);
+  float ix = ((gx + 1.f) * (float)Wm - 1.f) / 2.f, iy = ((gy + 1.f) * (float)Hm - 1.f) / 2.f;
+  ix = fminf(fmaxf(ix, 0.f), (float)(Wm - 1)); iy = fminf(fmaxf(iy, 0.f), (float)(Hm - 1));       // (a NaN becomes 0)
+  const float fx0 = floorf(ix), fy0 = floorf(iy);
+  const int x0 = (int)fx0, y0 = (int)fy0, x1 = x0 + 1, y1 = y0 + 1;
+  const float wx1 = ix - fx0, wx0 = (fx0 + 1.f) - ix, wy1 = iy - fy0, wy0 = (fy0 + 1.f) - iy;
+  const float wgt[4] = {wx0 * wy0, wx1 * wy0, wx0 * wy1, wx1 * wy1};           // nw, ne, sw, se: grid_sample's order of accumulation
+  const int tx[4] = {x0, x1, x0, x1}, ty[4] = {y0, y0, y1, y1};
+  cr = 0.f; cg = 0.f; cb = 0.f;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    if (tx[j] >= 0 && tx[j] < Wm && ty[j] >= 0 && ty[j] < Hm) {               // a tap outside the map contributes nothing
+      const float4 s = tex[(long)ty[j] * Wm + tx[j]];
+      cr = cr + s.x * wgt[j]; cg = cg + s.y * wgt[j]; cb = cb + s.z * wgt[j];
+    }
+  }
+}
+
+__device__ __forceinline__ unsigned char mt_u8(float c) { return (unsigned char)floorf(255.f * c + 0.5f); }   // c in [0, 1]
+
+// one 8 x 8 pixel tile per wave, pixel centres: the rays and the walk of mesh_trace_pinhole_kernel with off = 0.5 and no mask
+template <bool LDS> __global__ __launch_bounds__(64) void mesh_render_pinhole_kernel(MtMesh m, MtRenderArgs a) {
+  __shared__ float4 s_tri[LDS ? 3 * MT_CHUNK : 1];
+  const int x = blockIdx.x * 8 + (threadIdx.x & 7), y = blockIdx.y * 8 + (threadIdx.x >> 3);
+  const bool in = x < a.W && y < a.H;
+  const long p = (long)y * a.W + x;
+  const float dx = (((float)x + 0.5f) - a.cx) / a.fx, dy = -((((float)y + 0.5f) - a.cy) / a.fy);
+  const MtRay r = mt_ray(0.f, 0.f, 0.f, dx, dy, -1.f, in);
+  float t = a.t_max;
+  int k = -1;
+  mt_walk<LDS>(m, r, a.flags, s_tri, t, k);                                     // (every tile has a pixel inside the frame)
+  const bool hit = in && k >= 0;
+  if (a.records != nullptr) {
+    const unsigned long long all = __ballot(hit);
+    const int bits = (__ballot(hit && y == 0) != 0ull ? MT_REC_TOP : 0) | (__ballot(hit && y == a.H - 1) != 0ull ? MT_REC_BOTTOM : 0)
+                     | (__ballot(hit && x == 0) != 0ull ? MT_REC_LEFT : 0) | (__ballot(hit && x == a.W - 1) != 0ull ? MT_REC_RIGHT : 0);
+    if (threadIdx.x == 0) a.records[(long)blockIdx.y * gridDim.x + blockIdx.x] = make_int2(__popcll(all), bits);
+  }
+  if (!in) return;
+  float c[3] = {0.f, 0.f, 0.f};
+  int id = -1;
+  if (hit) {
+    const float4 va = m.tri[3l * k], vb = m.tri[3l * k + 1], vc = m.tri[3l * k + 2];
+    id = __float_as_int(va.w);
+    float b0, b1, b2;
+    mt_bary(va, vb, vc, r, b0, b1, b2);
+    if (a.vcolor != nullptr) {
+      const int i0 = a.faces[3l * k], i1 = a.faces[3l * k + 1], i2 = a.faces[3l * k + 2];
+      if (i0 >= 0 && i0 < a.V && i1 >= 0 && i1 < a.V && i2 >= 0 && i2 < a.V) {  // (a hit record passed this check in mesh_prepare_kernel already)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) c[j] = (b0 * a.vcolor[3l * i0 + j] + b1 * a.vcolor[3l * i1 + j]) + b2 * a.vcolor[3l * i2 + j];
+      }
+    } else {
+      float uv[3][2];
+#pragma unroll
+      for (int j = 0; j < 3; ++j) {
+        const int iu = a.face_uvs[3l * k + j];
+        const bool ok = iu >= 0 && iu < a.U;                                    // outside: the reference's appended zero row
+        uv[j][0] = ok ? a.uvs[2l * iu] : 0.f; uv[j][1] = ok ? a.uvs[2l * iu + 1] : 0.f;
+      }
+      const float tu = (b0 * uv[0][0] + b1 * uv[1][0]) + b2 * uv[2][0], tv = (b0 * uv[0][1] + b1 * uv[1][1]) + b2 * uv[2][1];
+      const int mi = a.face_mat[k];
+      if (mi >= 0 && mi < a.M) {                                                // outside: no material matches, the colour stays 0
+        const int4 mt = a.mats[mi];
+        if (mt.x >= 0 && mt.y >= 1 && mt.z >= 1 && (long)mt.x + (long)mt.y * mt.z <= a.n_texels)
+          mt_texture(a.texels + mt.x, mt.y, mt.z, tu, tv, c[0], c[1], c[2]);
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < 3; ++j) c[j] = fminf(fmaxf(c[j], 0.f), 1.f);            // clamp(img, 0, 1); a NaN becomes 0
+  }
+  const unsigned char mk = hit ? 255 : 0;
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    a.image[3 * p + j] = mt_u8(c[j]);
+    if (a.image_f != nullptr) a.image_f[3 * p + j] = c[j];
+    if (a.mask != nullptr) a.mask[3 * p + j] = mk;
+  }
+  if (a.depth != nullptr) a.depth[p] = hit ? t : a.miss_value;
+  if (a.face_id != nullptr) a.face_id[p] = id;
+}
+
+// one block: the tile records in a fixed order -> verdict (mesh_renderer.py:44-53; the area rule as the integer 2 count > H W)
+__global__ __launch_bounds__(256) void mesh_render_verdict_kernel(const int2* __restrict__ records, long n_tiles, long HW, int* verdict) {
+  __shared__ int s_count[256], s_bits[256];
+  int count = 0, bits = 0;                                                      // count <= H W < 2^31
+  for (long i = threadIdx.x; i < n_tiles; i += 256) { const int2 rec = records[i]; count += rec.x; bits |= rec.y; }
+  s_count[threadIdx.x] = count; s_bits[threadIdx.x] = bits;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (threadIdx.x < o) { s_count[threadIdx.x] += s_count[threadIdx.x + o]; s_bits[threadIdx.x] |= s_bits[threadIdx.x + o]; }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    const int b = s_bits[0];
+    const bool bad = ((b & MT_REC_TOP) && (b & MT_REC_BOTTOM)) || ((b & MT_REC_LEFT) && (b & MT_REC_RIGHT)) || 2l * s_count[0] > HW;
+    *verdict = bad ? 1 : 0;
+  }
+}
+
+// an invalid frame: every output as if nothing had been hit
+__global__ __launch_bounds__(256) void mesh_render_finish_kernel(const int* __restrict__ verdict, long HW, float miss_value, unsigned char* image,
+                                                                 float* image_f, unsigned char* mask, float* depth, int* face_id) {
+  if (*verdict == 0) return;
+  const long p = (long)blockIdx.x * 256 + threadIdx.x;
+  if (p >= HW) return;
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    image[3 * p + j] = 0;
+    if (image_f != nullptr) image_f[3 * p + j] = 0.f;
+    if (mask != nullptr) mask[3 * p + j] = 0;
+  }
+  if (depth != nullptr) depth[p] = miss_value;
+  if (face_id != nullptr) face_id[p] = -1;
+}
+
+extern "C" long snerf_mesh_render_scratch_bytes(int H, int W) {
+  if (H <= 0 || W <= 0) return 0;
+  return MT_SCRATCH_HEAD + (long)((H + 7) / 8) * ((W + 7) / 8) * (long)sizeof(int2);
+}
+
+extern "C" int snerf_mesh_render_pinhole(const void* ws, int F, float fx, float fy, float cx, float cy, int H, int W, float t_max, float miss_value,
+                                         int flags, const int* faces, const float* vertex_color, int V, const float* uvs, int U,
+                                         const int* face_uvs_idx, const int* face_material_idx, const void* texels, long n_texels,
+                                         const int* materials, int M, int validate, void* scratch, long scratch_bytes, void* image,
+                                         float* image_f, void* mask, float* depth, int* face_id, void* stream) {
+  if (F < 0 || H < 0 || W < 0 || V < 0 || U < 0 || n_texels < 0 || !(t_max > 0.f) || !isfinite(t_max) || (flags & ~(MT_NO_CULL | MT_UNIFORM)) != 0)
+    return SNERF_ERR_ARG;
+  if ((long)H * W > 0x7fffffffl) return SNERF_ERR_ARG;
+  if (!isfinite(fx) || !isfinite(fy) || fx == 0.f || fy == 0.f || !isfinite(cx) || !isfinite(cy)) return SNERF_ERR_ARG;
+  if (F > 0) {                                                                  // the attribute source: exactly one mode, complete
+    const bool colours = vertex_color != nullptr, textures = face_uvs_idx != nullptr;
+    if (colours == textures) return SNERF_ERR_ARG;
+    if (colours && faces == nullptr) return SNERF_ERR_ARG;
+    if (textures && (M < 1 || materials == nullptr || face_material_idx == nullptr || (uvs == nullptr && U > 0) || (texels == nullptr && n_texels > 0)
+                     || ((uintptr_t)texels & 15) != 0 || ((uintptr_t)materials & 15) != 0))
+      return SNERF_ERR_ARG;
+  }
+  if (H == 0 || W == 0) return SNERF_OK;
+  if (image == nullptr || !mt_ws_ok(ws, F)) return SNERF_ERR_ARG;
+  if (validate && (scratch == nullptr || ((uintptr_t)scratch & 7) != 0 || scratch_bytes < snerf_mesh_render_scratch_bytes(H, W))) return SNERF_ERR_ARG;
+  const unsigned gx = (unsigned)((W + 7) / 8), gy = (unsigned)((H + 7) / 8);
+  if (gy > 65535u) return SNERF_ERR_ARG;
+  const MtMesh m = mt_views((void*)ws, F);
+  MtRenderArgs a;
+  a.fx = fx; a.fy = fy; a.cx = cx; a.cy = cy; a.H = H; a.W = W; a.t_max = t_max; a.miss_value = miss_value; a.flags = flags;
+  a.faces = faces; a.vcolor = vertex_color; a.V = V; a.uvs = uvs; a.U = U; a.face_uvs = face_uvs_idx; a.face_mat = face_material_idx;
+  a.texels = (const float4*)texels; a.n_texels = n_texels; a.mats = (const int4*)materials; a.M = M;
+  a.records = validate ? (int2*)((char*)scratch + MT_SCRATCH_HEAD) : nullptr;
+  a.image = (unsigned char*)image; a.image_f = image_f; a.mask = (unsigned char*)mask; a.depth = depth; a.face_id = face_id;
+  hipStream_t st = (hipStream_t)stream;
+  if (flags & MT_UNIFORM) hipLaunchKernelGGL(mesh_render_pinhole_kernel<false>, dim3(gx, gy), dim3(64), 0, st, m, a);
+  else                    hipLaunchKernelGGL(mesh_render_pinhole_kernel<true>, dim3(gx, gy), dim3(64), 0, st, m, a);
+  if (validate) {
+    const long HW = (long)H * W;
+    hipLaunchKernelGGL(mesh_render_verdict_kernel, dim3(1), dim3(256), 0, st, a.records, (long)gx * gy, HW, (int*)scratch);
+    hipLaunchKernelGGL(mesh_render_finish_kernel, dim3((unsigned)((HW + 255) / 256)), dim3(256), 0, st, (const int*)scratch, HW, miss_value, a.image,
+                       image_f, a.mask, depth, face_id);
+  }
   return snerf_check_launch();
 }

@@ -10,8 +10,14 @@ The mesh depth behind `fg_depth` and the stage-0 instance masks come from `snerf
 `render_image` -> mesh depth -> paste -> boundary algebra -> `FrameWriter` never leaves the device.  The `raytracing` library the
 reference calls is not in its tree: see the meshtrace module docstring for what is and is not pinned.
 
-Not here (they stay with the caller): mesh loading and placement (trimesh), the vehicle image (nvdiffrast), the bounding-box export,
-and `handle_lighting` (cv2's 8-bit HSV round trip)."""
+The instance's own `image` and `mask` (api_code/mesh_renderer.py:36-88, nvdiffrast + kaolin in the reference) come from
+`snerf_amd.meshrender.MeshRenderer` (snerf_mesh_render_pinhole, scratch snerf_mesh_render_scratch_bytes): an instance of
+`composite_frame` may carry `render = (MeshRenderer, transform)` instead of `image` / `mask`, so mesh -> image + mask -> paste needs
+no host round trip either.  The placement of :14-34 is `meshrender.center_mesh_bottom`.
+
+Not here (they stay with the caller): mesh loading (trimesh, kaolin's .obj import), the kaolin camera algebra of
+mesh_renderer.py:187-221 (INTEGRATION.md gives the correspondence), the bounding-box export, and `handle_lighting` (cv2's 8-bit HSV
+round trip)."""
 import numpy as np
 import torch
 
@@ -119,25 +125,33 @@ def composite_frame(bg_im, depth_mat, semantic_mat, instances):
     """The instance loop of generate_images.py:80-166 for one frame.  `instances`: iterable (already in the reference's occlusion
     order) of dict(image [H,W,3] u8, mask [H,W,3] u8, fg_depth [H,W] f32 or None, category, r (optional band width)); instead of
     fg_depth an instance may carry mesh = (meshtrace.RayTracer, transform or None) and intrinsic (3 x 3, host): its depth is then
-    mesh_depth(tracer, intrinsic, H, W, mask, transform), traced here.
+    mesh_depth(tracer, intrinsic, H, W, mask, transform), traced here.  Instead of image and mask an instance may carry render =
+    (meshrender.MeshRenderer, transform or None) and intrinsic: both are then rendered here, at the frame's size, with the reference's
+    frame-validity rule.
     In place on bg_im / depth_mat / semantic_mat; returns dict(fuse, mask, bound, occluded_mask, depth, semantic, occlusion [per
     instance], instance_masks, instance_bounds) = the images the reference saves per frame (:153-154,186-196)."""
     total_mask, total_bound, total_occluded = torch.zeros_like(bg_im), torch.zeros_like(bg_im), torch.zeros_like(bg_im)
     occ, masks, bounds = [], [], []
     for inst in instances:
         cat = inst.get("category", "vehicle")
+        if inst.get("render") is not None:
+            renderer, transform = inst["render"]
+            fx, fy, cx, cy = _intrinsic(inst["intrinsic"])
+            image, mask = renderer.render(fx, fy, cx, cy, depth_mat.shape[0], depth_mat.shape[1], transform=transform)[:2]
+        else:
+            image, mask = inst["image"], inst["mask"]
         r = inst.get("r")
         if r is None:
-            r = bound_radius(inst["mask"], cat)
+            r = bound_radius(mask, cat)
         # the depth test works on a copy of the mask (utils_render.py:280: np.array(mask_im)); the band and the frame's mask come from
         # the instance's full mask, the depth-tested one only feeds the `occluded_mask` image of vehicles (generate_images.py:162-166)
-        tested = inst["mask"].clone()
+        tested = mask.clone()
         fg_depth = inst.get("fg_depth")
         if fg_depth is None and inst.get("mesh") is not None and cat != "person":
             tracer, transform = inst["mesh"]
-            fg_depth = mesh_depth(tracer, inst["intrinsic"], depth_mat.shape[0], depth_mat.shape[1], inst["mask"], transform)
-        occ.append(handle_occlusion_paste(bg_im, inst["image"], tested, depth_mat, semantic_mat, fg_depth, cat))
-        bound, mask_d = get_bound_im(inst["mask"], r, return_mask_diff=True)
+            fg_depth = mesh_depth(tracer, inst["intrinsic"], depth_mat.shape[0], depth_mat.shape[1], mask, transform)
+        occ.append(handle_occlusion_paste(bg_im, image, tested, depth_mat, semantic_mat, fg_depth, cat))
+        bound, mask_d = get_bound_im(mask, r, return_mask_diff=True)
         accumulate(total_mask, total_bound, bound, mask_d)
         if cat == "vehicle":
             total_occluded = torch.where((tested > 0) | (total_occluded > 0), 255, 0).to(torch.uint8)

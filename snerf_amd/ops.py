@@ -2146,3 +2146,53 @@ def mesh_trace_pinhole(ws, F, fx, fy, cx, cy, pixel_center, H, W, mask=None, t_m
     _lib.call("snerf_mesh_trace_pinhole", _p(_mesh_ws(ws, F)), int(F), float(fx), float(fy), float(cx), float(cy), int(bool(pixel_center)), H, W,
               _p(mask), float(t_max), float(miss_value), int(flags), _p(depth), _p(hit), _stream())
     return depth, hit
+
+
+def mesh_render_scratch_bytes(H, W):
+    """bytes of device scratch the validity rule of mesh_render_pinhole needs (snerf_mesh_render_scratch_bytes; 0 for H or W <= 0)"""
+    return int(_lib.query("snerf_mesh_render_scratch_bytes", int(H), int(W)))
+
+
+def _i32c(t, what, shape):
+    assert t is not None and t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and tuple(t.shape) == tuple(shape), f"{what}: int32 CUDA tensor {shape}"
+    return t
+
+
+def mesh_render_pinhole(ws, F, fx, fy, cx, cy, H, W, faces=None, vertex_color=None, uvs=None, face_uvs_idx=None, face_material_idx=None, texels=None,
+                        materials=None, t_max=100., miss_value=100., validate=True, flags=0, want_image_f=False, want_mask=True, want_depth=False,
+                        want_face_id=False, device=None):
+    """snerf_mesh_render_pinhole: the pixel-centre rays of mesh_trace_pinhole against the prepared mesh, shaded from exactly one attribute
+    source -- vertex_color [V,3] fp32 through the ORDERED faces [F,3] int32, or uvs [U,2] fp32 through face_uvs_idx [F,3] int32,
+    face_material_idx [F] int32 (both in the tracer's order), texels [T,4] fp32 (r, g, b, 0) and materials [M,4] int32 = (texel offset,
+    Hm, Wm, 0) -> (image [H,W,3] uint8, image_f [H,W,3] fp32 or None, mask [H,W,3] uint8 or None, depth [H,W] fp32 or None, face_id [H,W]
+    int32 or None).  `validate`: mesh_renderer.py's frame-validity rule, decided and applied on the device.  No host read."""
+    H, W, F = int(H), int(W), int(F)
+    dev = ws.device if ws is not None else (torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device))
+    V = U = M = T = 0
+    if F > 0:
+        assert (vertex_color is None) != (face_uvs_idx is None), "exactly one of vertex_color and face_uvs_idx"
+    if vertex_color is not None:
+        _f32c(vertex_color)
+        assert vertex_color.dim() == 2 and vertex_color.shape[1] == 3, "vertex_color [V,3] fp32"
+        V = vertex_color.shape[0]
+        _i32c(faces, "faces", (F, 3))
+    if face_uvs_idx is not None:
+        _f32c(uvs); _f32c(texels)
+        assert uvs is not None and uvs.dim() == 2 and uvs.shape[1] == 2, "uvs [U,2] fp32"
+        assert texels is not None and texels.dim() == 2 and texels.shape[1] == 4, "texels [T,4] fp32"
+        U, T = uvs.shape[0], texels.shape[0]
+        _i32c(face_uvs_idx, "face_uvs_idx", (F, 3)); _i32c(face_material_idx, "face_material_idx", (F,))
+        assert materials is not None and materials.dim() == 2
+        M = materials.shape[0]
+        _i32c(materials, "materials", (M, 4))
+    image = torch.empty(H, W, 3, dtype=torch.uint8, device=dev)
+    image_f = torch.empty(H, W, 3, dtype=torch.float32, device=dev) if want_image_f else None
+    mask = torch.empty(H, W, 3, dtype=torch.uint8, device=dev) if want_mask else None
+    depth = torch.empty(H, W, dtype=torch.float32, device=dev) if want_depth else None
+    face_id = torch.empty(H, W, dtype=torch.int32, device=dev) if want_face_id else None
+    scratch = torch.empty(mesh_render_scratch_bytes(H, W), dtype=torch.uint8, device=dev) if validate else None
+    _lib.call("snerf_mesh_render_pinhole", _p(_mesh_ws(ws, F)), F, float(fx), float(fy), float(cx), float(cy), H, W, float(t_max), float(miss_value),
+              int(flags), _p(faces), _p(vertex_color), V, _p(uvs), U, _p(face_uvs_idx), _p(face_material_idx), _p(texels), T, _p(materials), M,
+              int(bool(validate)), _p(scratch), 0 if scratch is None else scratch.numel(), _p(image), _p(image_f), _p(mask), _p(depth), _p(face_id),
+              _stream())
+    return image, image_f, mask, depth, face_id
