@@ -86,7 +86,7 @@ def raw2outputs(raw: torch.Tensor, z_vals: torch.Tensor, rays_d: torch.Tensor,
     disp = 1 / max(1e-10, depth / sum w), acc = sum w; optional white background.
     Returns (rgb_map, disp_map, acc_map, weights, depth_map)."""
     dists = z_vals[..., 1:] - z_vals[..., :-1]
-    dists = torch.cat([dists, torch.full_like(dists[..., :1], 1e10)], -1)
+    dists = torch.cat([dists, torch.full_like(z_vals[..., :1], 1e10)], -1)     # (z_vals, not dists: a single sample has no difference)
     dists = dists * torch.norm(rays_d[..., None, :], dim=-1)
     rgb = torch.sigmoid(raw[..., :3])
     sigma = raw[..., 3] if noise is None else raw[..., 3] + noise

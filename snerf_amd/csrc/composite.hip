@@ -7,10 +7,13 @@
 //                                     (real_volumetric_rendering)
 //   snerf_classic_composite_fwd/bwd : run_nerf_helpers.py:381-424 (raw2outputs)
 //
+// The two forward entries take any S >= 1.  The two backward entries take S <= 64 * MAXSEG = 512 and return
+// SNERF_ERR_ARG beyond that, without a launch.
+//
 // raw network outputs are fp32 [M, ld] (the MLP heads store fp32).
 #include "common.h"
 
-#define MAXSEG 8   // backward kernels keep per-64-sample-segment partial sums in registers: S <= 512
+#define MAXSEG 8   // backward kernels keep per-64-sample-segment partial sums in registers
 
 __device__ __forceinline__ float transform_s(float s, float near, float far, int idx) {
   if (idx == 0) return near * expf(s * logf(far / near));
@@ -19,6 +22,12 @@ __device__ __forceinline__ float transform_s(float s, float near, float far, int
 }
 __device__ __forceinline__ float softplus_f(float x) { return x > 20.f ? x : log1pf(expf(x)); }
 __device__ __forceinline__ float sigmoid_f(float x) { return 1.f / (1.f + expf(-x)); }
+// exclusive suffix sum: lane i gets the sum over lanes > i.  Taken from the neighbour's inclusive sum and not as inclusive - v,
+// which would leave an error of eps * |v| on the small sum behind a dense sample.
+__device__ __forceinline__ float wave_excl_rscan_add(float v, int lane) {
+  const float t = __shfl_down(wave_incl_rscan_add(v, lane), 1, 64);
+  return lane == 63 ? 0.f : t;
+}
 
 struct MipComp {
   const float* raw_rgb; long ld_rgb;       // [M,3] or null (proposal level)
@@ -65,8 +74,9 @@ __global__ __launch_bounds__(256) void mip_composite_fwd_kernel(MipComp a) {
       }
     }
     const float incl = wave_incl_scan_add(dd, lane);
-    const float excl = carry + (incl - dd);
-    const float alpha = 1.f - expf(-dd);
+    float excl = __shfl_up(incl, 1, 64);   // the neighbour's inclusive sum, not incl - dd: that loses the sum in front of a dense sample
+    excl = carry + (lane == 0 ? 0.f : excl);
+    const float alpha = -expm1f(-dd);   // not 1 - expf: its rounding near 1 has one sign over a ray's thin intervals and adds up in acc
     const float w = ok ? alpha * expf(-excl) : 0.f;
     if (ok) a.weights[ray * S + i] = w;
     s_acc += w;
@@ -184,7 +194,7 @@ __global__ __launch_bounds__(256) void mip_composite_bwd_kernel(MipComp a) {
     const float gw = g * w;
     const float incl_dd = wave_incl_scan_add(dd, lane);
     const float t_next = expf(-(carry_dd + incl_dd));              // T_{i+1}
-    const float suffix = later + (wave_incl_rscan_add(gw, lane) - gw);   // sum_{k>i} g_k w_k
+    const float suffix = later + wave_excl_rscan_add(gw, lane);     // sum_{k>i} g_k w_k
     const float g_dd = g * t_next - suffix;                         // d loss / d (density * delta)
     if (ok) a.d_raw_density[(ray * S + i) * a.ld_dden] = g_dd * delta * sp_grad;
     if (ok) g_norm += g_dd * dd;                                    // d(dd)/d|d| = dd / |d|
@@ -254,6 +264,13 @@ struct ClassicComp {
   float* d_raw; long ld_draw;
 };
 
+// log q of the reference's factor q = 1 - alpha + 1e-10 = exp(-x) + 1e-10, x = relu(sigma) dist.  The transmittance is exp of the
+// running sum of these, not a running product of q: each rounding of a q just under 1 is 3e-8 of the product, and 512 thin
+// intervals gave an opaque last sample a weight that was off by 5e-6.
+__device__ __forceinline__ float classic_log_q(float x) {
+  return x < 16.f ? log1pf(1e-10f * expf(x)) - x : logf(expf(-x) + 1e-10f);
+}
+
 __global__ __launch_bounds__(256) void classic_composite_fwd_kernel(ClassicComp a) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const long ray = (long)blockIdx.x * 4 + wave;
@@ -262,24 +279,25 @@ __global__ __launch_bounds__(256) void classic_composite_fwd_kernel(ClassicComp 
   const float* d = a.rays_d + ray * a.rd_stride;
   const float dnorm = sqrtf(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
   const float* z = a.z_vals + ray * S;
-  float carry = 1.f;   // product of (1 - alpha + 1e-10) over previous segments
+  float carry = 0.f;   // sum of log(1 - alpha + 1e-10) over previous segments
   float s_rgb[3] = {0.f, 0.f, 0.f}, s_acc = 0.f, s_depth = 0.f;
   for (int base = 0; base < S; base += 64) {
     const int i = base + lane;
     const bool ok = i < S;
-    float q = 1.f, alpha = 0.f, zi = 0.f;
+    float lq = 0.f, alpha = 0.f, zi = 0.f;
     if (ok) {
       zi = z[i];
       const float dist = (i + 1 < S ? z[i + 1] - zi : 1e10f) * dnorm;
       float sg = a.raw[(ray * S + i) * a.ld + 3];
       if (a.noise != nullptr) sg += a.noise[ray * S + i];
-      alpha = 1.f - expf(-fmaxf(sg, 0.f) * dist);
-      q = 1.f - alpha + 1e-10f;
+      const float x = fmaxf(sg, 0.f) * dist;
+      alpha = -expm1f(-x);               // not 1 - expf(-x): thin intervals (x ~ 1e-5) would keep two digits of alpha
+      lq = classic_log_q(x);
     }
-    const float incl = wave_incl_scan_mul(q, lane);
+    const float incl = wave_incl_scan_add(lq, lane);
     float excl = __shfl_up(incl, 1, 64);
-    if (lane == 0) excl = 1.f;
-    const float w = ok ? alpha * (carry * excl) : 0.f;
+    if (lane == 0) excl = 0.f;
+    const float w = ok ? alpha * expf(carry + excl) : 0.f;
     if (ok) {
       a.weights[ray * S + i] = w;
       const float* rr = a.raw + (ray * S + i) * a.ld;
@@ -288,7 +306,7 @@ __global__ __launch_bounds__(256) void classic_composite_fwd_kernel(ClassicComp 
     }
     s_acc += w;
     s_depth += w * zi;
-    carry *= __shfl(incl, 63, 64);
+    carry += __shfl(incl, 63, 64);
   }
   s_acc = wave_sum(s_acc);
   s_depth = wave_sum(s_depth);
@@ -324,7 +342,7 @@ __global__ __launch_bounds__(256) void classic_composite_bwd_kernel(ClassicComp 
     // disp = 1 / max(1e-10, depth/acc): d disp/d depth = -disp^2 / acc, d disp/d acc = disp^2 depth / acc^2 (if not clamped)
     const float acc = a.acc_map[ray], depth = a.depth_map[ray];
     const float r = depth / acc;
-    if (r > 1e-10f) {
+    if (r > 1e-10f) {   // false for the NaN of an empty ray (acc == 0) as well: deliberate, its samples get zeros and the trainer no NaN
       const float disp = 1.f / r, gd = a.g_disp[ray];
       gdepth += gd * (-disp * disp / acc);
       gacc += gd * (disp * disp * depth / (acc * acc));
@@ -346,7 +364,7 @@ __global__ __launch_bounds__(256) void classic_composite_bwd_kernel(ClassicComp 
     }
     segG[seg] = seg < nseg ? wave_sum(pg) : 0.f;
   }
-  float carry_p = 1.f;
+  float carry_p = 0.f;                                              // sum of log q over previous segments
 #pragma unroll
   for (int seg = 0; seg < MAXSEG; ++seg) {
     if (seg >= nseg) break;
@@ -355,15 +373,16 @@ __global__ __launch_bounds__(256) void classic_composite_bwd_kernel(ClassicComp 
     for (int s2 = 0; s2 < MAXSEG; ++s2) later += s2 > seg ? segG[s2] : 0.f;
     const int i = seg * 64 + lane;
     const bool ok = i < S;
-    float q = 1.f, g = 0.f, w = 0.f, dist = 0.f, sg = 0.f;
+    float q = 1.f, lq = 0.f, g = 0.f, w = 0.f, dist = 0.f, sg = 0.f;
     if (ok) {
       const float zi = z[i];
       dist = (i + 1 < S ? z[i + 1] - zi : 1e10f) * dnorm;
       const float* rr = a.raw + (ray * S + i) * a.ld;
       sg = rr[3];
       if (a.noise != nullptr) sg += a.noise[ray * S + i];
-      const float alpha = 1.f - expf(-fmaxf(sg, 0.f) * dist);
-      q = 1.f - alpha + 1e-10f;
+      const float x = fmaxf(sg, 0.f) * dist;
+      q = expf(-x) + 1e-10f;                                        // 1 - alpha + 1e-10
+      lq = classic_log_q(x);
       w = a.weights[ray * S + i];
       g = gacc + gdepth * zi;
       if (a.g_w != nullptr) g += a.g_w[ray * S + i];
@@ -376,17 +395,17 @@ __global__ __launch_bounds__(256) void classic_composite_bwd_kernel(ClassicComp 
       }
     }
     const float gw = g * w;
-    const float incl_q = wave_incl_scan_mul(q, lane);
+    const float incl_q = wave_incl_scan_add(lq, lane);
     float excl_q = __shfl_up(incl_q, 1, 64);
-    if (lane == 0) excl_q = 1.f;
-    const float P = carry_p * excl_q;
-    const float suffix = later + (wave_incl_rscan_add(gw, lane) - gw);
+    if (lane == 0) excl_q = 0.f;
+    const float P = expf(carry_p + excl_q);
+    const float suffix = later + wave_excl_rscan_add(gw, lane);
     if (ok) {
       const float dalpha = g * P - suffix / q;
       // alpha = 1 - exp(-relu(sg) dist): d alpha / d sg = dist * exp(-sg dist) for sg > 0
       a.d_raw[(ray * S + i) * a.ld_draw + 3] = sg > 0.f ? dalpha * dist * expf(-sg * dist) : 0.f;
     }
-    carry_p *= __shfl(incl_q, 63, 64);
+    carry_p += __shfl(incl_q, 63, 64);
   }
 }
 

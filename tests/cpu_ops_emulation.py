@@ -248,12 +248,17 @@ def jitter_u(jit, s):
 
 
 def mip_composite_fwd(raw_rgb, raw_density, noise, s_vals, dirs, near, far, transform_idx, white, rgb_padding, density_bias, row_index=None):
-    assert row_index is None
     n, P = s_vals.shape
+    if row_index is not None:    # compacted rows: sample (ray, i) reads row row_index[ray, i]; -1 = not evaluated (density 0, no colour)
+        ri = row_index.reshape(-1).long()
+        raw_density = raw_density.reshape(-1, 1)[ri.clamp_min(0)]
+        raw_rgb = None if raw_rgb is None else raw_rgb.reshape(-1, 3)[ri.clamp_min(0)]
     rd = raw_density.reshape(n, P - 1, 1)
     if noise is not None:
         rd = rd + noise.reshape(n, P - 1, 1)
     rgb, den = om.activate(None if raw_rgb is None else raw_rgb.reshape(n, P - 1, 3), rd, rgb_padding, density_bias)
+    if row_index is not None:
+        den = torch.where((ri >= 0).reshape(n, P - 1, 1), den, torch.zeros_like(den))
     c, d, a, w, _ = om.volumetric_rendering(rgb, den, s_vals, dirs, near[:, None], far[:, None], white, None, transform_idx)
     return c, d, a, w
 
@@ -272,7 +277,7 @@ def mip_composite_bwd(raw_rgb, raw_density, noise, s_vals, dirs, near, far, tran
         loss.backward()
     d_raw_density.copy_(rd.grad)
     if rr is not None:
-        d_raw_rgb.copy_(rr.grad)
+        d_raw_rgb.copy_(rr.grad if rr.grad is not None else torch.zeros_like(rr))     # no gradient reaches the colour without g_rgb
     if g_dirs is not None:
         g_dirs.copy_(dd.grad if dd.grad is not None else torch.zeros_like(dd))
 
