@@ -1143,6 +1143,53 @@ int snerf_mesh_render_pinhole(const void* ws, int F, float fx, float fy, float c
 /* bytes of scratch the validity rule of snerf_mesh_render_pinhole needs (0 for H or W <= 0) */
 long snerf_mesh_render_scratch_bytes(int H, int W);
 
+/* Projected mesh shadows of S-NeRF++ stage 3 (csrc/shadow.hip): s-nerfpp/stage3_code/mesh_shadow.py:21-113 generate_one_shadow for one
+ * frame and one instance, with the helpers of stage3_code/utils.py, as three separately callable stages that share one scratch buffer
+ * ws (>= snerf_shadow_ws_bytes(H, W, N, r, iter) bytes of device memory, 8-byte aligned; 0 = refused shape).  Images and masks are
+ * [H,W,3] uint8; a mask is set where channel 0 is > 0 and is written as 0 / 255 on all three channels (the reference's masks carry one
+ * plane three times).  No entry synchronises, allocates or reads a device value on the host; results do not depend on launch order.
+ *
+ * snerf_shadow_project: utils.py:339-354 process_mesh, :130-154 project_to_ground, :157-168 project, :171-192 points_to_mask.  vertices
+ * [N,3] in device memory, fp32 (vertices_f64 = 0) or fp64 (1); all arithmetic is fp64, never contracted.  xf: 28 doubles in HOST memory,
+ * read before the call returns: the row-major 3 x 4 placement (Rz(theta) | bbox_center + Rz mesh_bias), the light vector (3), the
+ * ground height, the row-major 3 x 4 world-to-pixel matrix P (c2w^-1)[:3].  ground_mode: 0 = the given height; 1 = the reference's
+ * `if not ground_height` (None and 0.0 alike): the smallest z of the placed points, found by a two-stage reduction (no atomics); 2 = no
+ * ground projection (the reference's check = True, mesh_shadow.py:70-71).  A point is moved by -light (z - ground) / light_z,
+ * projected, divided by its third coordinate (no test of its sign), truncated and kept if
+ * 0 < x < W and 0 < y < H (strict: column 0 and row 0 are never set).  Divergence: a quotient that is not finite, negative or >= 65536
+ * is dropped, where the reference's float -> uint16 cast wraps it.  The splat (plain byte stores of 255 into a zeroed plane of ws) is
+ * the input of snerf_shadow_close(mask_in = NULL); mask_out (optional) receives it as an [H,W,3] mask.  N = 0 gives an empty mask.
+ *
+ * snerf_shadow_close: utils.py:195-211 interpolate = zero-pad by (H, W), cv2.morphologyEx(MORPH_CLOSE, MORPH_RECT (r, r), iterations =
+ * iter), crop.  PARITY UNPINNED (cv2 is not available to the build): OpenCV's definition is followed -- dst(x, y) = max (min for the
+ * erosion) over 0 <= x', y' < r of src(x + x' - r / 2, y + y' - r / 2), pixels outside the padded image never win, iter dilations and
+ * then iter erosions, both with the same un-reflected window (an even r shifts the result).  Runs on bit-packed rows over the image
+ * extended by min(iter (r / 2), pad) per side.  mask_in NULL: the splat of the last snerf_shadow_project on this ws.  The closed mask
+ * stays in ws for snerf_shadow_fuse(shadow_mask = NULL); mask_out (optional) receives it.  mask_out == mask_in is allowed (the input
+ * is packed before anything is written); a partial overlap is refused.  iter = 0 copies.
+ *
+ * snerf_shadow_fuse: mesh_shadow.py:89-107 blur_shadow, in place on im.  shadow_mask NULL: the closed mask of the last
+ * snerf_shadow_close on this ws.  An empty mask leaves im untouched.  Otherwise kw = max(1, (xmax - xmin) / 5), kh likewise from the
+ * mask's bounding box (two-stage reduction; written to ws), count = the kw x kh window sum of the 0 / 1 mask with anchor (kw / 2,
+ * kh / 2) and BORDER_REFLECT_101 (cv2.blur's definition: PARITY UNPINNED; int32, prefix sums), and per pixel and channel, each step
+ * one rounded fp64 operation: b = count * (1.0 / (kw kh)); occ = 255 where b > 0 and not total_mask > 0 (utils.py:214-225
+ * check_the_occlusion, per channel), else 0; m = (b * occ) / 255.0; im = (uint8)(im * (1.0 - light_scale * m)), truncating.  check = 1
+ * is the reference's check = True (utils.py:248-269 shadow_fuse(im, mask, 1, blur = None)): im[mask > 0] = 0, total_mask unused.
+ *
+ * snerf_shadow_ws_offset(H, W, which): byte offset in ws of (0) eight int32 = any, kw, kh, xmin, xmax, ymin, ymax, 0 and (1) the
+ * counts [H,W] int32, both as the last snerf_shadow_fuse with a non-empty mask left them; -1 for a refused shape or selector.
+ * Bad arguments return 1 before any launch: a null vertices (N > 0) / xf / im / total_mask (check = 0) / ws, H or W < 1, H W or the
+ * rows / words of the extended bit plane beyond 2^31 - 1, N < 0 or beyond 2^31 - 1, r < 1, iter < 0, vertices_f64 or check other
+ * than 0 / 1, ground_mode outside 0..2, light_scale outside [0, 1], a misaligned or short ws (project and fuse need snerf_shadow_ws_bytes(H, W, N, 1, 0), close its own r and iter), an
+ * output that overlaps ws or an input, except mask_out == mask_in of snerf_shadow_close. */
+long snerf_shadow_ws_bytes(int H, int W, long N, int r, int iter);
+long snerf_shadow_ws_offset(int H, int W, int which);
+int snerf_shadow_project(const void* vertices, int vertices_f64, long N, const double* xf, int ground_mode, int H, int W, void* mask_out,
+                         void* ws, long ws_bytes, void* stream);
+int snerf_shadow_close(const void* mask_in, int H, int W, int r, int iter, void* mask_out, void* ws, long ws_bytes, void* stream);
+int snerf_shadow_fuse(void* im, const void* total_mask, const void* shadow_mask, int H, int W, double light_scale, int check, void* ws,
+                      long ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2196,3 +2196,61 @@ def mesh_render_pinhole(ws, F, fx, fy, cx, cy, H, W, faces=None, vertex_color=No
               int(bool(validate)), _p(scratch), 0 if scratch is None else scratch.numel(), _p(image), _p(image_f), _p(mask), _p(depth), _p(face_id),
               _stream())
     return image, image_f, mask, depth, face_id
+
+
+def shadow_ws_bytes(H, W, N=0, r=20, iter=3):
+    """bytes of device scratch the three shadow stages share (snerf_shadow_ws_bytes; raises for a shape or parameter the library refuses)"""
+    n = int(_lib.query("snerf_shadow_ws_bytes", int(H), int(W), int(N), int(r), int(iter)))
+    if n <= 0:
+        raise _lib.SnerfHipError(f"snerf_shadow_ws_bytes refuses H={H} W={W} N={N} r={r} iter={iter}")
+    return n
+
+
+def shadow_ws_views(ws, H, W):
+    """(info, counts): int32 views into ws at snerf_shadow_ws_offset(H, W, 0 / 1) -- info = (any, kw, kh, xmin, xmax, ymin, ymax, 0) and
+    counts [H,W], as the last shadow_fuse with a non-empty mask left them (what the tests compare with the CPU model)"""
+    o_info, o_counts = (int(_lib.query("snerf_shadow_ws_offset", int(H), int(W), k)) for k in (0, 1))
+    assert o_info >= 0 and o_counts >= 0, "snerf_shadow_ws_offset refuses this shape"
+    return ws[o_info:o_info + 32].view(torch.int32), ws[o_counts:o_counts + 4 * H * W].view(torch.int32).view(H, W)
+
+
+def _shadow_ws(ws):
+    assert ws is not None and ws.is_cuda and ws.dtype == torch.uint8 and ws.is_contiguous(), "ws: a contiguous uint8 CUDA tensor (shadow_ws_bytes)"
+    return ws
+
+
+def _shadow_u8(t, H, W, what):
+    assert t is None or (t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous() and tuple(t.shape) == (H, W, 3)), f"{what}: [H,W,3] uint8 CUDA tensor"
+    return t
+
+
+def shadow_project(vertices, xf, ground_mode, H, W, ws, mask_out=None):
+    """snerf_shadow_project: vertices [N,3] fp32 or fp64 on the device, xf = 28 HOST doubles (placement 3 x 4, light vector, ground
+    height, world-to-pixel 3 x 4; a ctypes array or anything numpy converts), ground_mode 0 = that height, 1 = the smallest placed z, 2 = no
+    ground projection -> the splat mask in ws (the input of shadow_close(None,
+    ...)), and in mask_out [H,W,3] uint8 when given.  No host read of device memory."""
+    assert vertices.is_cuda and vertices.dtype in (torch.float32, torch.float64) and vertices.is_contiguous() and vertices.dim() == 2 and \
+        vertices.shape[1] == 3, "vertices [N,3] fp32 / fp64 on the device"
+    if not isinstance(xf, ctypes.Array):
+        import numpy as np
+        xf = (ctypes.c_double * 28)(*np.asarray(xf, dtype=np.float64).reshape(28).tolist())
+    assert len(xf) == 28
+    _lib.call("snerf_shadow_project", _p(vertices), int(vertices.dtype == torch.float64), vertices.shape[0], ctypes.addressof(xf), int(ground_mode),
+              int(H), int(W), _p(_shadow_u8(mask_out, H, W, "mask_out")), _p(_shadow_ws(ws)), ws.numel(), _stream())
+    return mask_out
+
+
+def shadow_close(mask_in, H, W, r, iter, ws, mask_out=None):
+    """snerf_shadow_close: the closing of utils.py:195-211 interpolate on mask_in [H,W,3] uint8 (None: the splat shadow_project left in
+    ws) -> the closed mask in ws (the input of shadow_fuse(..., None, ...)), and in mask_out when given (mask_out may be mask_in)."""
+    _lib.call("snerf_shadow_close", _p(_shadow_u8(mask_in, H, W, "mask_in")), int(H), int(W), int(r), int(iter), _p(_shadow_u8(mask_out, H, W, "mask_out")),
+              _p(_shadow_ws(ws)), ws.numel(), _stream())
+    return mask_out
+
+
+def shadow_fuse(im, total_mask, shadow_mask, H, W, light_scale, check, ws):
+    """snerf_shadow_fuse: in place on im [H,W,3] uint8 -- mesh_shadow.py:89-107 blur_shadow with shadow_mask [H,W,3] uint8 (None: the
+    closed mask shadow_close left in ws), or with check the blanking im[mask > 0] = 0 (total_mask may then be None)."""
+    _lib.call("snerf_shadow_fuse", _p(_shadow_u8(im, H, W, "im")), _p(_shadow_u8(total_mask, H, W, "total_mask")),
+              _p(_shadow_u8(shadow_mask, H, W, "shadow_mask")), int(H), int(W), float(light_scale), int(bool(check)), _p(_shadow_ws(ws)), ws.numel(), _stream())
+    return im
