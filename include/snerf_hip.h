@@ -632,6 +632,15 @@ int snerf_fg_bound(const void* mask_im, int H, int W, int r, void* bound_im, voi
 int snerf_fg_accumulate(void* total_mask, void* total_bound, const void* bound, const void* mask, long nbytes, void* stream);
 /* utils_render.py:327-335 fuse_bound_and_im: im[bound > 0] = 0, per byte, in place. */
 int snerf_fg_blank(void* im, const void* bound, long nbytes, void* stream);
+/* Pairwise overlap statistics of N masks, the input of utils_render.py:691-808 occlution_order (:745-753).  masks: a HOST array of N
+ * DEVICE pointers to [H,W,3] uint8 masks (copied into the kernel arguments: no staging copy, no stacked masks; 16-byte aligned masks
+ * are read with 16-byte loads, others byte by byte); stats: device int64 [N,N,3], ZEROED BY THE CALLER, to which the entry adds.  For
+ * every pair a < b, stats[a][b] = (count, sum of row, sum of col) over all (row, col, channel) triples with mask_a > 0 and mask_b > 0
+ * there: what np.where(intersection_mask > 0) enumerates -- bytes, not pixels, so masks whose channels differ are counted as the
+ * reference counts them.  Entries with a >= b are not touched.  Integer sums through 32-bit LDS partials and 64-bit atomics: the result
+ * does not depend on their order and is bit-reproducible.  Bad arguments (N outside [2, 32], H or W outside [1, 65535], a null masks,
+ * mask or stats pointer) return 1 before any launch. */
+int snerf_fg_overlap(const void* const* masks, int N, int H, int W, long* stats, void* stream);
 
 /* Hash-grid weight decay (s-nerfpp/zipnerf/internal/train_utils.py:184-203 hash_decay_loss; torch_scatter.segment_coo(param**2, idx,
  * reduce='mean').mean() per encoder): table / grad fp32 [rows, C] (grad accumulated: += 2 mult p / (rows_l L C)), offsets device int32

@@ -3,7 +3,8 @@
 //   snerf_fg_bound        <- utils_render.py:306-324 get_bound_im (cv2.dilate XOR cv2.erode, rect kernel) + ip_utils.py:10-19 set_diff
 //   snerf_fg_accumulate   <- utils_render.py:338-361 fuse_bound + generate_images.py:161 mask union
 //   snerf_fg_blank        <- utils_render.py:327-335 fuse_bound_and_im
-// One lane per pixel, HBM-bound: every image is read once and written once.
+//   snerf_fg_overlap      <- utils_render.py:745-753: (count, sum row, sum col) of np.where(mask_a & mask_b) for every pair of N masks
+// One lane per pixel, HBM-bound: every image is read once and written once (snerf_fg_overlap: 16 bytes per lane, every mask read once).
 #include "common.h"
 
 struct FgPaste {
@@ -112,5 +113,103 @@ extern "C" int snerf_fg_blank(void* im, const void* bound, long nbytes, void* st
   if (im == nullptr || bound == nullptr) return SNERF_ERR_ARG;
   hipLaunchKernelGGL(fg_blank_kernel, dim3((unsigned)((nbytes + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (unsigned char*)im,
                      (const unsigned char*)bound, nbytes);
+  return snerf_check_launch();
+}
+
+// ---- pairwise overlap statistics of N masks (the input of the reference's occlusion order) ------------------------------------------------
+// Each mask is 3 H W flat bytes.  A lane owns runs of 16 consecutive bytes: one 16-byte load per mask (byte loads when a mask is not
+// 16-byte aligned, and in the last, partial run), then per byte position the N-bit word of the masks that are > 0 there.  A word with
+// fewer than two bits names no pair, and a run without such a word -- nearly every run of a real frame -- ends there.  Otherwise (row, col)
+// of the run's first byte is divided out once and carried along the run; equal consecutive words are merged in registers and
+// every pair of set bits of a merged word adds (count, sum row, sum col) to the block's N x N x 3 table of 32-bit LDS slots, laid out
+// like the output.  A block covers FG_OV_BLOCK_BYTES bytes, so a slot holds at most FG_OV_BLOCK_BYTES * 65534 < 2^32: no partial wraps.
+// At the end the non-zero slots go to the int64 output with 64-bit atomics: integer sums, so the result does not depend on their order.
+#define FG_OV_MAX_N 32
+#define FG_OV_RUN 16
+#define FG_OV_BLOCK_BYTES 8192
+static_assert((unsigned long long)FG_OV_BLOCK_BYTES * 65535ull < (1ull << 32), "a 32-bit LDS partial must not wrap");
+static_assert(FG_OV_BLOCK_BYTES % (256 * FG_OV_RUN) == 0, "whole passes of the 256 lanes");
+
+struct FgOverlap {
+  const unsigned char* mask[FG_OV_MAX_N];
+  int N, W, vec; long total; unsigned long long* out;
+};
+
+__device__ __forceinline__ void fg_overlap_flush(unsigned* table, int N, unsigned word, unsigned cnt, unsigned srow, unsigned scol) {
+  for (unsigned wa = word; wa != 0; wa &= wa - 1) {
+    const int a = __ffs(wa) - 1;
+    for (unsigned wb = wa & (wa - 1); wb != 0; wb &= wb - 1) {
+      unsigned* slot = table + 3 * (a * N + (__ffs(wb) - 1));
+      atomicAdd(slot, cnt); atomicAdd(slot + 1, srow); atomicAdd(slot + 2, scol);
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void fg_overlap_kernel(FgOverlap a) {
+  __shared__ unsigned table[3 * FG_OV_MAX_N * FG_OV_MAX_N];
+  const int slots = 3 * a.N * a.N;
+  for (int i = threadIdx.x; i < slots; i += 256) table[i] = 0;
+  __syncthreads();
+  const long base = (long)blockIdx.x * FG_OV_BLOCK_BYTES;
+  for (int pass = 0; pass < FG_OV_BLOCK_BYTES / (256 * FG_OV_RUN); ++pass) {
+    const long start = base + ((long)pass * 256 + threadIdx.x) * FG_OV_RUN;
+    if (start >= a.total) break;
+    const bool whole = start + FG_OV_RUN <= a.total;
+    unsigned word[FG_OV_RUN];
+#pragma unroll
+    for (int j = 0; j < FG_OV_RUN; ++j) word[j] = 0;
+    for (int k = 0; k < a.N; ++k) {
+      const unsigned char* m = a.mask[k] + start;
+      unsigned v[4] = {0, 0, 0, 0};
+      if (whole && a.vec) {
+        const uint4 q = *reinterpret_cast<const uint4*>(m);
+        v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+      } else {
+        const int n = whole ? FG_OV_RUN : (int)(a.total - start);
+        for (int j = 0; j < n; ++j) v[j >> 2] |= (unsigned)m[j] << (8 * (j & 3));
+      }
+#pragma unroll
+      for (int j = 0; j < FG_OV_RUN; ++j) word[j] |= (((v[j >> 2] >> (8 * (j & 3))) & 0xffu) != 0 ? 1u : 0u) << k;
+    }
+    unsigned pairs = 0;
+#pragma unroll
+    for (int j = 0; j < FG_OV_RUN; ++j) pairs |= word[j] & (word[j] - 1);
+    if (pairs == 0) continue;
+    const long p = start / 3;
+    int c = (int)(start - 3 * p);
+    unsigned row = (unsigned)(p / a.W), col = (unsigned)(p - (long)row * a.W);
+    unsigned cur = 0, cnt = 0, srow = 0, scol = 0;
+#pragma unroll
+    for (int j = 0; j < FG_OV_RUN; ++j) {
+      const unsigned w = (word[j] & (word[j] - 1)) != 0 ? word[j] : 0u;        // (past the end of a partial run: 0)
+      if (w != cur) {
+        if (cur != 0) fg_overlap_flush(table, a.N, cur, cnt, srow, scol);
+        cur = w; cnt = 0; srow = 0; scol = 0;
+      }
+      cnt += 1; srow += row; scol += col;
+      if (++c == 3) {
+        c = 0;
+        if (++col == (unsigned)a.W) { col = 0; ++row; }
+      }
+    }
+    if (cur != 0) fg_overlap_flush(table, a.N, cur, cnt, srow, scol);
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < slots; i += 256) {
+    const unsigned v = table[i];
+    if (v != 0) atomicAdd(a.out + i, (unsigned long long)v);
+  }
+}
+
+extern "C" int snerf_fg_overlap(const void* const* masks, int N, int H, int W, long* stats, void* stream) {
+  if (masks == nullptr || stats == nullptr || N < 2 || N > FG_OV_MAX_N || H < 1 || H > 65535 || W < 1 || W > 65535) return SNERF_ERR_ARG;
+  FgOverlap a;
+  a.N = N; a.W = W; a.vec = 1; a.total = 3l * H * W; a.out = (unsigned long long*)stats;
+  for (int k = 0; k < FG_OV_MAX_N; ++k) {
+    a.mask[k] = k < N ? (const unsigned char*)masks[k] : nullptr;
+    if (k < N && masks[k] == nullptr) return SNERF_ERR_ARG;
+    if (k < N && ((uintptr_t)masks[k] & 15) != 0) a.vec = 0;
+  }
+  hipLaunchKernelGGL(fg_overlap_kernel, dim3((unsigned)((a.total + FG_OV_BLOCK_BYTES - 1) / FG_OV_BLOCK_BYTES)), dim3(256), 0, (hipStream_t)stream, a);
   return snerf_check_launch();
 }

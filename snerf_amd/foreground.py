@@ -15,9 +15,18 @@ The instance's own `image` and `mask` (api_code/mesh_renderer.py:36-88, nvdiffra
 `composite_frame` may carry `render = (MeshRenderer, transform)` instead of `image` / `mask`, so mesh -> image + mask -> paste needs
 no host round trip either.  The placement of :14-34 is `meshrender.center_mesh_bottom`.
 
-Not here (they stay with the caller): mesh loading (trimesh, kaolin's .obj import), the kaolin camera algebra of
-mesh_renderer.py:187-221 (INTEGRATION.md gives the correspondence), the bounding-box export, and `handle_lighting` (cv2's 8-bit HSV
-round trip)."""
+The order in which the instances are pasted (utils_render.py:691-808 occlution_order, called from generate_images.py:76-81) is
+`occlusion_order`: pairwise overlap statistics of the instance masks in one launch (snerf_fg_overlap), one centroid ray per overlapping
+pair traced against both meshes, the reference's topological sort on the host after ONE small read; `composite_frame(order="occlusion")`
+runs it between rendering and pasting.  The KITTI-style label row of an instance (utils_render.py:543-640) is `bbox_result` /
+`save_bbox_results` (host, from the `occlusion` scalars composite_frame returns; `occlusion_level` is its threshold rule).
+
+Not here (they stay with the caller): mesh loading (trimesh, kaolin's .obj import) and `trimesh.bounds.oriented_bounds` (the `extents`
+of bbox_result: a per-mesh constant), the kaolin camera algebra of mesh_renderer.py:187-221 (INTEGRATION.md gives the correspondence),
+and `handle_lighting` (cv2's 8-bit HSV round trip)."""
+import ctypes
+import math
+
 import numpy as np
 import torch
 
@@ -121,15 +130,200 @@ def fuse_bound_and_im(fuse_im, bound_im):
     return fuse_im
 
 
-def composite_frame(bg_im, depth_mat, semantic_mat, instances):
-    """The instance loop of generate_images.py:80-166 for one frame.  `instances`: iterable (already in the reference's occlusion
-    order) of dict(image [H,W,3] u8, mask [H,W,3] u8, fg_depth [H,W] f32 or None, category, r (optional band width)); instead of
+def overlap_stats(masks):
+    """snerf_fg_overlap: masks = N (2 .. 32) contiguous [H,W,3] uint8 device tensors of one shape -> int64 [N,N,3] on the device; for a < b
+    (count, sum of row, sum of col) over np.where((mask_a > 0) & (mask_b > 0)) -- (row, col, channel) triples, not pixels --, zero for
+    a >= b.  One launch that reads every mask once; the masks are not stacked or copied.  No host read."""
+    masks = list(masks)
+    N = len(masks)
+    assert N >= 1, "overlap_stats: at least one mask"
+    H, W, _ = masks[0].shape
+    for m in masks:
+        _u8(m, (H, W, 3))
+        assert m.device == masks[0].device, "overlap_stats: all masks on one device"
+    stats = torch.zeros(N, N, 3, dtype=torch.int64, device=masks[0].device)
+    ptrs = (ctypes.c_void_p * N)(*[m.data_ptr() for m in masks])
+    _lib.call("snerf_fg_overlap", ptrs, N, H, W, _p(stats), _stream())
+    return stats
+
+
+T_MAX_ANY = float(np.finfo(np.float32).max)      # the largest t_max the tracer accepts: trimesh's intersects_first has no range limit
+
+
+def topological_order(before):
+    """utils_render.py:795-806 literally: before [N,N] (host), before[i, j] != 0 = "i is pasted before j".  Repeatedly the smallest index
+    not yet emitted whose column is all zero is emitted and its row cleared; RuntimeError on a cycle.  -> list of N indices."""
+    A = np.array(before, dtype=np.uint8)
+    n = A.shape[0]
+    result = []
+    while len(result) < n:
+        for i in range(n):
+            if i not in result and np.sum(A[:, i]) == 0:
+                result.append(i)
+                A[i, :] = 0
+                break
+        else:
+            raise RuntimeError("Occlusion judgment fails....")
+    return result
+
+
+def occlusion_order(masks, meshes, w2c, P, ray_frame="reference"):
+    """utils_render.py:691-808 occlution_order for one frame -> (order: list of N indices, the instances in the order they are to be
+    pasted, farthest first; before: host int8 [N,N], before[i, j] = 1 when i must be pasted before j).
+
+    masks: N [H,W,3] uint8 device masks; meshes: N pairs (meshtrace.RayTracer, transform or None), `transform` placing the tracer's mesh
+    into camera coordinates as composite_frame's `mesh=` takes it (without the diag(1, -1, -1) flip mesh_depth adds); w2c (4 x 4) and P
+    (3 x 3 intrinsic): HOST values.
+
+    Per pair a < b whose masks share a byte (snerf_fg_overlap; :745-751) the pixel (mean col, mean row, 1) of the shared (row, col,
+    channel) triples is sent through inv(P) (:753-754); both meshes are traced along that ONE ray (one trace_ids call per mesh, over
+    the rays of all its pairs, no range limit) and z = the z of the centre of the first-hit face under `transform` (:732-736)
+    decides: z_a < z_b is "a occludes b", b is pasted first; anything else (equal or NaN z included) pastes a first.  Pairs without overlap
+    get no edge.  The sort is the reference's loop (topological_order), on the host, after the one host read of this function.
+
+    On a miss trimesh returns -1 and the reference indexes `tri[-1]`: the centre of the LAST face of the mesh as the caller numbered
+    it decides.  The same happens here, in both ray frames.
+
+    ray_frame: the reference builds the ray in WORLD coordinates (origin c2w[:3, 3], direction towards c2w (inv(P) pixel, 1), normalised;
+    :752-760) and casts it against meshes it has already moved into CAMERA coordinates (:777).  ray_frame="reference" (the default)
+    reproduces that as written: unless w2c is near the identity most rays miss and the last-face z decides.  ray_frame="camera" casts
+    what was evidently meant, origin 0 and direction inv(P) pixel in the meshes' own frame.
+
+    Parity: trimesh is not part of the reference tree, so how `intersects_first` treats a ray through an edge or a degenerate face is
+    not pinned; the semantics are those of meshtrace (watertight, nearest t > 0).  The ray is formed in float64 on the device and
+    cast in fp32."""
+    assert ray_frame in ("reference", "camera"), "ray_frame: 'reference' or 'camera'"
+    masks, meshes = list(masks), list(meshes)
+    N = len(masks)
+    assert len(meshes) == N, "occlusion_order: one (tracer, transform) per mask"
+    if N < 2:
+        return list(range(N)), np.zeros((N, N), dtype=np.int8)
+    dev = masks[0].device
+    assert not any(torch.is_tensor(m) and m.is_cuda for m in (w2c, P)), "w2c, P: host values (a device matrix would cost a sync per call)"
+    c2w = np.linalg.inv(np.asarray(w2c, dtype=np.float64)[:4, :4])
+    host = np.concatenate([np.linalg.inv(np.asarray(P, dtype=np.float64)[:3, :3]).reshape(-1), c2w[:3].reshape(-1)])
+    host = torch.tensor(host, dtype=torch.float64).to(dev)                      # one upload: inv(P) and the top of c2w
+    Pinv, c2w_d = host[:9].view(3, 3), host[9:].view(3, 4)
+    stats = overlap_stats(masks).double()
+    count = stats[..., 0]
+    overlap = count > 0                                                        # [N,N], a < b only
+    pixel = torch.stack([stats[..., 2] / count, stats[..., 1] / count, torch.ones_like(count)], dim=-1)    # (j.mean(), i.mean(), 1)
+    point = pixel @ Pinv.T                                                     # [N,N,3]
+    if ray_frame == "reference":
+        origin = c2w_d[:, 3].expand(N, N, 3)
+        d = (point @ c2w_d[:, :3].T + c2w_d[:, 3]) - origin
+        d = d / torch.linalg.norm(d, dim=-1, keepdim=True)
+    else:
+        origin, d = torch.zeros(N, N, 3, dtype=torch.float64, device=dev), point
+    d = torch.where(overlap[..., None], d, torch.zeros_like(d))                # no overlap: a zero direction, which hits nothing
+    o32, d32 = origin.float(), d.float()                                       # (one origin for every pair)
+    d32 = d32 + d32.transpose(0, 1)                                            # the pair's ray at [a,b] and at [b,a]: the other half is zero
+    z = torch.zeros(N, N, dtype=torch.float64, device=dev)                     # z[k, j]: mesh k along the ray of the pair {k, j}
+    others = torch.tensor([[j for j in range(N) if j != k] for k in range(N)]).to(dev)                     # [N,N-1], one upload
+    for k, (tracer, transform) in enumerate(meshes):
+        face = tracer.trace_ids(o32[k, others[k]], d32[k, others[k]], transform, T_MAX_ANY)[3]
+        z[k, others[k]] = tracer.face_centers(face, transform)[:, 2]
+    a_occludes_b = z < z.transpose(0, 1)                                       # at [a,b], a < b: z_a < z_b
+    upper = overlap.triu(1)
+    before = ((upper & ~a_occludes_b) | (upper & a_occludes_b).transpose(0, 1)).to(torch.int8).cpu().numpy()     # the one host read
+    return topological_order(before), before
+
+
+def occlusion_level(occlusion_per):
+    """utils_render.py:561-568: the KITTI occlusion level 0 / 1 / 2 / 3 of an occluded share, thresholds .01, .5, .99"""
+    if occlusion_per < .01:
+        return 0
+    if occlusion_per < .5:
+        return 1
+    if occlusion_per < .99:
+        return 2
+    return 3
+
+
+CATEGORY_NAME = {"vehicle": "Car", "person": "Pedestrain", "object": "Object", "bicycle": "Bicycle", "motorcycle": "Motorcycle"}   # utils_render.py:579-581 (its spelling)
+_EXTENT_FIELDS = {"vehicle": ("height", "width", "length"), "bicycle": ("width", "height", "length"), "person": ("length", "width", "height"),
+                  "motorcycle": ("width", "height", "length")}                 # :605-612; "object" gets none
+
+
+def rot_y(w2c, theta):
+    """utils_render.py:590-600,623: Rotation.from_matrix(M).as_euler('yzx')[0] - pi / 2 for M = rot_w2c @ Rz(theta degrees) @ rot_axis.T, in
+    closed form: the first angle of scipy's extrinsic 'yzx' is atan2(M[0,2], M[0,0]) (away from the gimbal lock |M[0,1]| = 1)."""
+    t = math.radians(float(theta))
+    rz = np.array([[math.cos(t), -math.sin(t), 0.], [math.sin(t), math.cos(t), 0.], [0., 0., 1.]])
+    rot_axis = np.array([[1., 0., 0.], [0., 0., -1.], [0., 1., 0.]])
+    M = np.asarray(w2c, dtype=np.float64)[:3, :3] @ rz @ rot_axis.T
+    return math.atan2(M[0, 2], M[0, 0]) - math.pi / 2
+
+
+def bbox_result(w2c, bbox_center, theta, occlusion_per, category, extents):
+    """utils_render.py:583-626 get_bbox_result: the KITTI-style label of one instance in one frame, everything in camera coordinates.
+    w2c: 4 x 4 host matrix; bbox_center: the instance's position in the world; theta: its heading in degrees; occlusion_per: a host
+    float (composite_frame's `occlusion`); extents: the three `trimesh.bounds.oriented_bounds(mesh)[1]` values, a per-mesh constant the
+    caller computes when it loads the mesh, assigned to height / width / length per category as the reference does ("object": none)."""
+    w2c = np.asarray(w2c, dtype=np.float64)
+    centre = np.concatenate([np.asarray(bbox_center, dtype=np.float64).reshape(3), [1.]])
+    pos = (w2c @ centre)[:3]
+    res = {"category": CATEGORY_NAME[category], "occlution": occlusion_level(occlusion_per)}
+    for field, value in zip(_EXTENT_FIELDS.get(category, ()), extents if extents is not None else ()):
+        res[field] = float(value)
+    res["pos_x"], res["pos_y"], res["pos_z"] = (float(v) for v in pos)
+    for field in ("alpha", "xmin", "ymin", "xmax", "ymax", "truncated"):
+        res[field] = .0
+    res["rot_y"] = rot_y(w2c, theta)
+    res["confidence"] = 1
+    return res
+
+
+def save_bbox_results(path, results):
+    """utils_render.py:629-640 save_bbox_result_for_one_frame: one line per label, the reference's format string"""
+    with open(path, "w") as f:
+        for res in results:
+            f.write("%s %f %d %f %f %f %f %f %f %f %f %f %f %f %f %f" %
+                    (res["category"], res["truncated"], res["occlution"], res["alpha"], res["xmin"], res["ymin"], res["xmax"], res["ymax"],
+                     res["height"], res["width"], res["length"], res["pos_x"], res["pos_y"], res["pos_z"], res["rot_y"], res["confidence"]))
+            f.write("\n")
+
+
+def _ordered_by_occlusion(instances, depth_mat, w2c, intrinsic):
+    """composite_frame(order="occlusion"): render what is to be rendered, then -> (the instances in paste order, the order)"""
+    instances = [dict(inst) for inst in instances]
+    for i, inst in enumerate(instances):
+        if inst.get("mesh") is None:
+            raise ValueError(f"composite_frame(order='occlusion'): instance {i} ({inst.get('category', 'vehicle')}) has no mesh=(tracer, transform); "
+                             "the occlusion order casts a ray against the mesh of every instance, persons included")
+    if w2c is None or intrinsic is None:
+        raise ValueError("composite_frame(order='occlusion') needs w2c (4 x 4) and intrinsic (3 x 3), the frame's camera")
+    for inst in instances:
+        if inst.get("intrinsic") is None:
+            inst["intrinsic"] = intrinsic
+        if inst.get("render") is not None:
+            renderer, transform = inst.pop("render")
+            fx, fy, cx, cy = _intrinsic(inst["intrinsic"])
+            inst["image"], inst["mask"] = renderer.render(fx, fy, cx, cy, depth_mat.shape[0], depth_mat.shape[1], transform=transform)[:2]
+    order, _ = occlusion_order([inst["mask"] for inst in instances], [inst["mesh"] for inst in instances], w2c, intrinsic)
+    return [instances[i] for i in order], order
+
+
+def composite_frame(bg_im, depth_mat, semantic_mat, instances, order="given", w2c=None, intrinsic=None):
+    """The instance loop of generate_images.py:80-166 for one frame.  `instances`: iterable of dict(image [H,W,3] u8, mask [H,W,3] u8,
+    fg_depth [H,W] f32 or None, category, r (optional band width)); instead of
     fg_depth an instance may carry mesh = (meshtrace.RayTracer, transform or None) and intrinsic (3 x 3, host): its depth is then
     mesh_depth(tracer, intrinsic, H, W, mask, transform), traced here.  Instead of image and mask an instance may carry render =
     (meshrender.MeshRenderer, transform or None) and intrinsic: both are then rendered here, at the frame's size, with the reference's
     frame-validity rule.
+    order="given" (the default): the instances are pasted as they come, already in the reference's occlusion order.  order="occlusion":
+    EVERY instance carries mesh = (tracer, transform), persons too (the reference loads a mesh for each), and the frame's `w2c` (4 x 4,
+    host) and `intrinsic` (3 x 3, host; also that of an instance without its own) are given; the instances with render = are rendered
+    first, all of them, `occlusion_order(masks, meshes, w2c, intrinsic)` sorts them (generate_images.py:76-81) and the loop runs in that
+    order.  The result then has `order`, indices into `instances` as given; a missing mesh is a ValueError that names the instance.
     In place on bg_im / depth_mat / semantic_mat; returns dict(fuse, mask, bound, occluded_mask, depth, semantic, occlusion [per
-    instance], instance_masks, instance_bounds) = the images the reference saves per frame (:153-154,186-196)."""
+    instance], instance_masks, instance_bounds) = the images the reference saves per frame (:153-154,186-196); the per-instance lists are
+    in the order of processing."""
+    if order not in ("given", "occlusion"):
+        raise ValueError(f"composite_frame: order must be 'given' or 'occlusion', not {order!r}")
+    paste_order = None
+    if order == "occlusion":
+        instances, paste_order = _ordered_by_occlusion(instances, depth_mat, w2c, intrinsic)
     total_mask, total_bound, total_occluded = torch.zeros_like(bg_im), torch.zeros_like(bg_im), torch.zeros_like(bg_im)
     occ, masks, bounds = [], [], []
     for inst in instances:
@@ -157,5 +351,8 @@ def composite_frame(bg_im, depth_mat, semantic_mat, instances):
             total_occluded = torch.where((tested > 0) | (total_occluded > 0), 255, 0).to(torch.uint8)
         masks.append(mask_d); bounds.append(bound)
     fuse_bound_and_im(bg_im, total_bound)
-    return dict(fuse=bg_im, mask=total_mask, bound=total_bound, occluded_mask=total_occluded, depth=depth_mat, semantic=semantic_mat, occlusion=occ,
-                instance_masks=masks, instance_bounds=bounds)
+    out = dict(fuse=bg_im, mask=total_mask, bound=total_bound, occluded_mask=total_occluded, depth=depth_mat, semantic=semantic_mat, occlusion=occ,
+               instance_masks=masks, instance_bounds=bounds)
+    if paste_order is not None:
+        out["order"] = paste_order
+    return out

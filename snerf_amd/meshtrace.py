@@ -98,6 +98,25 @@ class RayTracer:
         return ops.mesh_trace_pinhole(self.ws, self.n_faces, fx, fy, cx, cy, pixel_center, H, W, mask, t_max, miss_value, want_hit, flags,
                                       device=self.device)
 
+    def face_centers(self, face_id, transform=None):
+        """-> float64 [..., 3]: trimesh's `triangles_center[face_id]` of the mesh under `transform`, the mean of the three transformed
+        vertices, for face ids in the CONSTRUCTOR's numbering (what trace_ids returns).  A negative id counts from the end as a numpy
+        index does, so the -1 of a miss names the last face (the reference's `tri[tri_index]` at stage1_code/utils_render.py:733-735).
+        No host read; a mesh without faces gives NaN."""
+        fid = face_id.to(device=self.device, dtype=torch.int64)
+        if self.n_faces == 0:
+            return torch.full(tuple(fid.shape) + (3,), float("nan"), dtype=torch.float64, device=self.device)
+        if getattr(self, "_position_of", None) is None:          # the caller's face index -> its position in the ordered arrays
+            self._position_of = torch.empty(self.n_faces, dtype=torch.int64, device=self.device)
+            self._position_of[self.face_ids.long()] = torch.arange(self.n_faces, device=self.device)
+        fid = torch.where(fid < 0, fid + self.n_faces, fid)
+        tri = self.vertices.double()[self.faces[self._position_of[fid]].long()]             # [..., 3 corners, 3]
+        t = _as_transform(transform, self.device)
+        if t is not None:
+            t = t.double()
+            tri = tri @ t[:, :3].T + t[:, 3]
+        return tri.mean(dim=-2)
+
 
 def _as_rays(r, device):
     t = r if torch.is_tensor(r) else torch.tensor(np.asarray(r, dtype=np.float32))
