@@ -33,6 +33,7 @@ import torch
 from torch import nn
 
 from . import ops
+from .batching import DrawCounter
 from .mlp import ClassicNeRFNet, ParamArena
 
 
@@ -657,7 +658,7 @@ def lrate_decay(lrate, lrate_decay, global_step):
     return lrate * 0.1 ** (global_step / (lrate_decay * 1000))
 
 
-class RayBatcher:
+class RayBatcher(DrawCounter):
     """Device-resident form of the stock `use_batching` loader of the classic training loop: the rays of ALL training images are visited
     in a shuffled order, `N_rand` per step.  Images, camera-to-world matrices, the per-image (focal, cx, cy) table and i_train live on
     the device; `next()` / `next_into(buf)` draws, casts and gathers one batch in ONE launch (`snerf_classic_train_batch`) with no host
@@ -677,10 +678,6 @@ class RayBatcher:
     def __init__(self, images, poses, focal, i_train, N_rand, near=0., far=1., ndc=True, use_viewdirs=False, ori_points=None, seed=0,
                  rank=0, world=1, device=None):
         from .sample_utils import _stack
-        from .trainer import shard_bounds
-        if not 0 <= int(seed) < (1 << 63):
-            raise ValueError("seed must be in [0, 2^63)")
-        device = torch.device(device if device is not None else "cuda")
         img = _stack(images)
         if img.dim() != 4 or img.shape[-1] != 3 or img.shape[0] == 0 or img.shape[1] == 0 or img.shape[2] == 0:
             raise ValueError("images: [n, H, W, 3] with n, H, W >= 1")
@@ -705,11 +702,11 @@ class RayBatcher:
             if op.shape[0] != n:
                 raise ValueError("ori_points: one (cx, cy) per image")
             K[:, 1:] = op
-        world, rank, N_rand = int(world), int(rank), int(N_rand)
-        if world < 1 or not 0 <= rank < world:
-            raise ValueError("rank in [0, world)")
-        if N_rand < world:
-            raise ValueError(f"N_rand = {N_rand}: at least one ray per rank ({world})")
+        N_rand = int(N_rand)
+        if N_rand < max(int(world), 1):
+            raise ValueError(f"N_rand = {N_rand}: at least one ray per rank ({int(world)})")
+        super().__init__(N_rand, seed, rank, world, device)     # (the last check; the first thing on the device)
+        device = self.device
         self.images = img.to(device, torch.uint8 if img.dtype == torch.uint8 else torch.float32).contiguous()
         self.c2w = P[:, :3, :4].to(device).contiguous()
         self.intrinsics = torch.as_tensor(K).to(device)
@@ -718,21 +715,6 @@ class RayBatcher:
         self.n_images, self.H, self.W, self.N_rand = n, H, W, N_rand
         self.T = int(it.size) * H * W
         self.near, self.far, self.ndc, self.use_viewdirs = float(near), float(far), bool(ndc), bool(use_viewdirs)
-        self.rank, self.world = rank, world
-        self.i0, self.i1 = shard_bounds(N_rand, rank, world)
-        self.seed, self.device = int(seed), device
-        self.counter = torch.zeros(2, dtype=torch.int64, device=device)        # {step, workgroup ticket}: advanced by the launch
-        self._step = 0
-
-    @property
-    def step(self):
-        """the step of the next draw (host mirror of the device counter; `advance_host` after graph replays of `next_into`)"""
-        return self._step
-
-    @property
-    def n_rows(self):
-        """rows of this rank's batch"""
-        return self.i1 - self.i0
 
     def rays_of_step(self, s):
         """ray indices in [0, T) of this rank's rows of step s -- on the host, no sync"""
@@ -745,17 +727,6 @@ class RayBatcher:
         hw = self.H * self.W
         return np.stack([self.i_train_host[q // hw], (q % hw) // self.W, (q % hw) % self.W], -1).astype(np.int64)
 
-    def state_dict(self):
-        return {"seed": self.seed, "step": self._step}
-
-    def load_state_dict(self, sd):
-        self.seed, self._step = int(sd["seed"]), int(sd["step"])
-        self.counter.copy_(torch.tensor([self._step, 0], dtype=torch.int64))
-
-    def advance_host(self, k=1):
-        """tell the host mirror that k draws ran inside graph replays"""
-        self._step += int(k)
-
     def buffers(self):
         """fresh output tensors of one batch (this rank's rows)"""
         m = self.n_rows
@@ -767,12 +738,7 @@ class RayBatcher:
         -> (ray_batch, target_rgb), the tensors of `buf`"""
         ops.classic_train_batch(self.images, self.c2w, self.intrinsics, self.i_train, self.seed, self.counter, self.N_rand, self.i0, self.i1,
                                 self.ndc, self.near, self.far, self.use_viewdirs, buf["rays"], buf["rgb"])
-        self._step += 1
-        return buf["rays"], buf["rgb"]
-
-    def next(self):
-        """-> (ray_batch, target_rgb) of the next step in new tensors (they stay valid)"""
-        return self.next_into(self.buffers())
+        return self._drawn((buf["rays"], buf["rgb"]))
 
 
 def strip_module_prefix(state_dict):

@@ -8,6 +8,7 @@ import numpy as np
 import torch
 
 from . import ops
+from .batching import DrawCounter, shard_bounds
 
 Rays = collections.namedtuple('Rays', ('origins', 'directions', 'viewdirs', 'radii', 'lossmult', 'near', 'far', 'app'))
 
@@ -156,7 +157,6 @@ def classic_rays_of_step(s, n_rand, T, seed, rank=0, world=1):
     the global batch sits at position p = s n_rand + r of the endless ray stream, in epoch e = p // T, and is ray
     keyed_perm(p % T, T, CLASSIC_BATCH_TAG, e, seed): every epoch visits each of the T rays once, in an order of its own; a batch may
     straddle an epoch boundary.  -> int64 [rows of shard_bounds(n_rand, rank, world)]"""
-    from .trainer import shard_bounds
     i0, i1 = shard_bounds(int(n_rand), int(rank), int(world))
     out = np.empty(i1 - i0, dtype=np.int64)
     for k, r in enumerate(range(i0, i1)):
@@ -219,7 +219,7 @@ def _stack(x, dtype=None):
     return torch.as_tensor(np.asarray(x, dtype=dtype) if dtype is not None else np.asarray(x))
 
 
-class ImageRayBatcher:
+class ImageRayBatcher(DrawCounter):
     """Device-resident form of SingleImage + sample_single_img (s-nerf/dataloader/rayset.py:124-151, the `no_batching` loader that
     `pose_refine = True` selects): the training images, depth maps, poses and intrinsics live on the device and `next()` draws, casts and
     gathers one batch in ONE launch (`snerf_mip_image_batch`), with no host work, no upload and no sync per step.
@@ -241,9 +241,6 @@ class ImageRayBatcher:
         _check(args)
         if getattr(args, "smooth_loss", False) and not self.draws_patches:
             raise NotImplementedError("smooth_loss: ImageRayBatcher draws no patches; PatchRayBatcher does")
-        if not 0 <= int(seed) < (1 << 63):
-            raise ValueError("seed must be in [0, 2^63)")
-        device = torch.device(device if device is not None else "cuda")
         img = _stack(images)
         if img.dim() != 4 or img.shape[-1] != 3 or img.shape[0] == 0:
             raise ValueError("images: [N, H, W, 3] with N >= 1")
@@ -280,6 +277,8 @@ class ImageRayBatcher:
         else:
             nf = [(near * 0.9, far * 1.1)] * N
         cam = np.zeros(N) if camera_index is None else np.asarray(camera_index.cpu() if torch.is_tensor(camera_index) else camera_index, dtype=np.float64).reshape(-1)
+        super().__init__(n, seed, rank, world, device)                          # (the last check; the first thing on the device)
+        device = self.device
         f32 = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float32)).to(device)
         self.images = img.to(device, torch.uint8 if img.dtype == torch.uint8 else torch.float32).contiguous()
         self.depths = dep.to(device).contiguous()
@@ -290,37 +289,10 @@ class ImageRayBatcher:
         self.i_train_host = it
         self.i_train = torch.as_tensor(it, dtype=torch.int32).to(device)
         self.N, self.H, self.W, self.batch_n = N, H, W, n
-        from .trainer import shard_bounds
-        self.rank, self.world = int(rank), int(world)
-        self.i0, self.i1 = shard_bounds(n, self.rank, self.world)
-        self.seed, self.device = int(seed), device
-        self.counter = torch.zeros(2, dtype=torch.int64, device=device)        # {step, workgroup ticket}: advanced by the launch
-        self._step = 0
-
-    @property
-    def step(self):
-        """the step of the next draw (host mirror of the device counter; `advance_host` after graph replays of `next_into`)"""
-        return self._step
 
     def image_of_step(self, s):
         """index (into the images) of the image step s trains on -- on the host, no sync (pose refinement: pose_param_net(img_i))"""
         return image_of_step(self.i_train_host, self.seed, s)
-
-    def state_dict(self):
-        return {"seed": self.seed, "step": self._step}
-
-    def load_state_dict(self, sd):
-        self.seed, self._step = int(sd["seed"]), int(sd["step"])
-        self.counter.copy_(torch.tensor([self._step, 0], dtype=torch.int64))
-
-    def advance_host(self, k=1):
-        """tell the host mirror that k draws ran inside graph replays"""
-        self._step += int(k)
-
-    @property
-    def n_rows(self):
-        """rows of this rank's batch"""
-        return self.i1 - self.i0
 
     def buffers(self):
         """fresh output tensors of one batch (this rank's rows)"""
@@ -335,12 +307,7 @@ class ImageRayBatcher:
         -> (rays, target_rgb, target_depth, sel_coords, img_i, extras) as views of `buf`"""
         ops.mip_image_batch(self.images, self.depths, self.poses, self.intrinsics, self.near, self.far, self.app, self.extras, self.i_train,
                             self.seed, self.counter, self.batch_n, self.i0, self.i1, buf)
-        self._step += 1
-        return self.view(buf)
-
-    def next(self):
-        """-> (rays, target_rgb, target_depth, sel_coords, img_i, extras) of the next step in new tensors (they stay valid)"""
-        return self.next_into(self.buffers())
+        return self._drawn(self.view(buf))
 
     @staticmethod
     def view(buf):
@@ -378,7 +345,6 @@ class PatchRayBatcher(ImageRayBatcher):
                                  "(or 2^32 and more of them)")
         super().__init__(args, images, depth_gts, poses, intrinsics, i_train, near, far, camera_index=camera_index, batch_n=batch_n,
                          extras=extras, seed=seed, rank=rank, world=world, device=device)
-        from .trainer import shard_bounds
         self.n_patch, self.patch_sz = n_patch, p
         self.k0, self.k1 = shard_bounds(n_patch, self.rank, self.world)
 
@@ -404,5 +370,4 @@ class PatchRayBatcher(ImageRayBatcher):
         ops.mip_image_patch_batch(self.images, self.depths, self.poses, self.intrinsics, self.near, self.far, self.app, self.extras,
                                   self.i_train, self.seed, self.counter, self.batch_n, self.i0, self.i1, self.n_patch, self.patch_sz,
                                   self.k0, self.k1, buf)
-        self._step += 1
-        return self.view(buf)
+        return self._drawn(self.view(buf))

@@ -16,6 +16,7 @@ import torch
 import torch.distributed as dist
 
 from . import ops
+from .batching import shard_batch, shard_bounds, shard_rays      # (re-exported: trainer.shard_bounds and its siblings)
 
 
 class _GradExchange:
@@ -82,8 +83,10 @@ class _AdamState:
     the reference's training loop resumes here and the other way round
     (`torch.optim.Adam(model.parameters()).load_state_dict(trainer.state_dict())`).
     The class that trains a buffer supplies `_buffers()` -> (parameters, gradients), `_layout()` -> [(name, offset, count, shape)] of the
-    parameters in the buffer, and `what`, the buffer's name in messages."""
+    parameters in the buffer, and `what`, the buffer's name in messages.  `named`: the checkpoint also names the parameters
+    (`param_names`) and is refused for a buffer with other names; without it the checkpoint is torch's plain layout."""
     step_dev = lr_dev = _graph = None               # (step_dev / lr_dev: int32 [1] / fp32 [1] on the device once a captured step holds the Adam)
+    named = False
 
     def _moments(self):
         return self.m, self.v
@@ -122,11 +125,16 @@ class _AdamState:
                  for i, (_, lo, cnt, shape) in enumerate(layout)}
         group = {"lr": self.lr, "betas": tuple(self.betas), "eps": self.eps, "weight_decay": 0, "amsgrad": False, "maximize": False,
                  "foreach": None, "capturable": False, "differentiable": False, "fused": None, "params": list(range(len(layout)))}
-        return {"state": state, "param_groups": [group]}
+        sd = {"state": state, "param_groups": [group]}
+        if self.named:
+            sd["param_names"] = [n for n, *_ in layout]
+        return sd
 
     def load_state_dict(self, sd):
         """every check comes before the first write: a refused state leaves the moments, t, lr / betas / eps and the device step word alone"""
         layout = self._layout()
+        if self.named and "param_names" in sd and list(sd["param_names"]) != [n for n, *_ in layout]:
+            raise ValueError("optimizer state was saved for other parameter names")
         groups = sd["param_groups"]
         order = [i for g in groups for i in g["params"]]
         if len(order) != len(layout):
@@ -164,10 +172,76 @@ class _AdamState:
             self.step_dev.fill_(self.t)
 
 
+class _CapturedStep:
+    """hipGraph capture and replay of a trainer's whole step: what MipTrainer and ClassicTrainer share.  The trainer's `capture()` does
+    its refusals and wires the batch tensors, then hands `_capture` the two bodies; it supplies `_trained()` (the _AdamStates of the
+    step's Adam launches), `_counted()` where other objects hold the step counts, `_bump_restored()` and `_after_graph()`."""
+    _batcher = None
+
+    def _counted(self):
+        """the objects whose `t` one step advances by one"""
+        return self._trained()
+
+    def _capture(self, warmup, batcher, buf, step, forward_backward):
+        """`step()` / `forward_backward()` -> (loss, outs) on the capture batch; `batcher.next_into(buf)` runs ahead of either.  The
+        `warmup` steps are real steps on a side stream, with the trained states and the batcher's place snapshotted before and restored
+        after them; then the graph records `step` (world 1, step counts and learning rates armed in device memory) or
+        `forward_backward` (world > 1: `replay()` follows the graph with `_after_graph()`).  -> the graph's loss tensor"""
+        dev = self.m.device
+        trained = self._trained()
+        snaps = [x.snapshot() for x in trained]
+        if self.world == 1:
+            for x in trained:
+                x.arm()
+        self._batcher = batcher
+        b_snap = None if batcher is None else batcher.snapshot()
+
+        def draw():
+            if batcher is not None:
+                batcher.next_into(buf)
+        side = torch.cuda.Stream(device=dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side):                    # warm-up on a side stream
+            for _ in range(warmup):
+                draw()
+                step()
+        torch.cuda.current_stream(dev).wait_stream(side)
+        for x, snap in zip(trained, snaps):
+            x.restore(snap)
+        if batcher is not None:                          # capturing uses up no draws
+            batcher.restore(b_snap)
+        self._bump_restored()                            # (the restored parameters are new values to the packed operands)
+        self._graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self._graph):
+            draw()
+            self._graph_loss, self._graph_outs = step() if self.world == 1 else forward_backward()
+        if batcher is not None:
+            batcher.advance_host(-1)                     # capturing records the draw and the step, it does not run them
+        if self.world == 1:
+            for x in self._counted():
+                x.t -= 1
+        return self._graph_loss
+
+    def replay(self):
+        """One captured step.  -> (loss, outs): the same device tensors every time, overwritten by each replay."""
+        if self._batcher is not None:
+            self._batcher.advance_host(1)                # the graph's first node drew the batch and advanced the device counter
+        if self.world == 1:
+            for x in self._trained():
+                x.lr_dev.fill_(x.lr)                     # the graph reads the learning rates from the device
+            self._graph.replay()
+            for x in self._counted():
+                x.t += 1
+        else:
+            self._graph.replay()                         # forward + loss tail + backward of this rank's shard
+            self._after_graph()                          # the gradient exchange and the Adam launches
+        return self._graph_loss, self._graph_outs
+
+
 class _ArenaAdam(_AdamState):
     """_AdamState over a model's flat arena, in the order of `model.parameters()`: what MipTrainer and ZipTrainer share.  The checkpoint
     also names the parameters (`param_names`) and is refused for a model with other names."""
-    what = "model"
+    what, named = "model", True
     side = ()                                       # (the side tables trained beside the model: MipTrainer's)
     _step_dev, _lr_dev = property(lambda self: self.step_dev), property(lambda self: self.lr_dev)
 
@@ -193,16 +267,6 @@ class _ArenaAdam(_AdamState):
     def _layout(self):
         a = self.model.arena
         return [(n, *a._offs[n], a.shapes[n]) for n, _ in self.model.named_parameters()]
-
-    def state_dict(self):
-        sd = super().state_dict()
-        sd["param_names"] = [n for n, *_ in self._layout()]
-        return sd
-
-    def load_state_dict(self, sd):
-        if "param_names" in sd and list(sd["param_names"]) != [n for n, *_ in self._layout()]:
-            raise ValueError("optimizer state was saved for other parameter names")
-        super().load_state_dict(sd)
 
     def _arena_adam(self, grad_scale, **hygiene):
         """one fused Adam launch over the flat arena; folds `grad_scale` (the data-parallel mean, the loss scale), the gradient hygiene and
@@ -432,7 +496,7 @@ class MipLossRules:
         return self._dev[key]
 
 
-class MipTrainer(_ArenaAdam):
+class MipTrainer(_CapturedStep, _ArenaAdam):
     rules = None                                     # (class default: loss_and_grads also serves trainers assembled without __init__)
     smooth_patch_sz = None
 
@@ -796,9 +860,8 @@ class MipTrainer(_ArenaAdam):
         With `smooth_patch_sz` (a sample_utils.PatchRayBatcher only): the captured step takes `n_rgb` from the batcher's `n_rgb_rows`
         and, with `smooth_skymask`, the sky of the patch rows from the batcher's extra map `smooth_sky_extra`; the trainer-owned target
         copies, ops.smooth_loss and its finish launch are nodes of the graph.  Nothing on the host depends on the batch."""
-        a = self.model.arena
-        dev = a.flat.device
         indexed = bool(self.side) or self.rules is not None
+        buf = None
         # every refusal first: a refused capture leaves the trainer as it was
         if self.smooth_patch_sz is not None:
             if not getattr(batcher, "draws_patches", False) or batcher.patch_sz != self.smooth_patch_sz:
@@ -828,88 +891,20 @@ class MipTrainer(_ArenaAdam):
         if indexed and not (torch.is_tensor(img_i) and img_i.is_cuda):
             raise ValueError("capture() with a pose_net or loss_rules: img_i= must be an int64 [1] device tensor (a python int would be frozen into the graph)")
         self._set_viewc(viewc)                           # (fn = 0: the centre is a kernel argument, i.e. a constant of the captured graph)
-        trained = self._trained()
-        snaps = [x.snapshot() for x in trained]
-        if self.world == 1:
-            for x in trained:
-                x.arm()
-        self._batcher = batcher
         if batcher is not None:
             self.batch = batch
-            b_snap = (batcher.counter.clone(), batcher.step)
         step = dict(rays=rays, target_rgb=target_rgb, target_depth=target_depth, conf=conf, randomized=randomized, img_i=img_i, **tail)
+        return self._capture(warmup, batcher, buf, lambda: self.step(**step),
+                             lambda: self._forward_backward(s_rand=None, u=None, ray_grads=False, on_done=None, **step))
 
-        def draw():
-            if batcher is not None:
-                batcher.next_into(buf)
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):                    # warm-up on a side stream
-            for _ in range(warmup):
-                draw()
-                self.step(**step)
-        torch.cuda.current_stream(dev).wait_stream(side)
-        for x, snap in zip(trained, snaps):
-            x.restore(snap)
-        if batcher is not None:                          # capturing uses up no draws
-            batcher.counter.copy_(b_snap[0])
-        if not self.freeze_model:                        # (the restored parameters are new values to the packed operands)
-            a.bump()
-        self._graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self._graph):
-            draw()
-            if self.world == 1:
-                self._graph_loss, self._graph_outs = self.step(**step)
-            else:
-                self._graph_loss, self._graph_outs = self._forward_backward(s_rand=None, u=None, ray_grads=False, on_done=None, **step)
-        if batcher is not None:
-            batcher._step = b_snap[1]
-        if self.world == 1:
-            for x in trained:
-                x.t -= 1                                 # capturing records the step, it does not run it
-        return self._graph_loss
+    def _bump_restored(self):
+        if not self.freeze_model:
+            self.model.arena.bump()
 
-    def replay(self):
-        """One captured step.  -> (loss, outs): the same device tensors every time, overwritten by each replay."""
-        if getattr(self, "_batcher", None) is not None:
-            self._batcher.advance_host(1)                # the graph's first node drew the batch and advanced the device counter
-        if self.world == 1:
-            for x in self._trained():
-                x.lr_dev.fill_(x.lr)                     # the graph reads the learning rates from the device
-            for table in self.side:
-                table.t += 1
-            self._graph.replay()
-            if not self.freeze_model:
-                self.t += 1
-        else:
-            self._graph.replay()                         # forward + loss tail + backward of this rank's shard
-            if not self.freeze_model:
-                _GradExchange(self.model.arena, self.world, self.pg).finish()   # one all-reduce of the flat gradient arena
-            self._update()
-        return self._graph_loss, self._graph_outs
-
-
-def shard_bounds(n: int, rank: int, world: int):
-    """[start, end) of rank's contiguous share of n rays; the first n % world ranks take one extra ray, nothing is dropped."""
-    per, rem = divmod(n, world)
-    start = rank * per + min(rank, rem)
-    return start, start + per + (1 if rank < rem else 0)
-
-
-def shard_rays(rays, rank: int, world: int):
-    """Contiguous split of a ray batch (namedtuple of [N,.] tensors) across ranks; see shard_bounds."""
-    a, b = shard_bounds(rays[0].shape[0], rank, world)
-    return type(rays)(*[r[a:b] for r in rays])
-
-
-def shard_batch(rays, rank: int, world: int, *per_ray):
-    """shard_rays for the rays AND every per-ray target (target_rgb, target_depth, conf, ...; None passes through) with the same
-    bounds, so that a caller cannot slice them inconsistently.  -> (rays_shard, *target_shards)"""
-    a, b = shard_bounds(rays[0].shape[0], rank, world)
-    for t in per_ray:
-        if t is not None and t.shape[0] != rays[0].shape[0]:
-            raise ValueError("per-ray tensor does not match the ray batch")
-    return (type(rays)(*[r[a:b] for r in rays]),) + tuple(None if t is None else t[a:b] for t in per_ray)
+    def _after_graph(self):
+        if not self.freeze_model:
+            _GradExchange(self.model.arena, self.world, self.pg).finish()   # one all-reduce of the flat gradient arena
+        self._update()
 
 
 class _TableShards:
@@ -1369,7 +1364,7 @@ class _NetAdam(_AdamState):
         return self.net.arena.flat, self.net.arena.grad
 
 
-class ClassicTrainer(_AdamState):
+class ClassicTrainer(_CapturedStep, _AdamState):
     """Train step of the classic render_rays path (path B; the stock loop around s-nerf/model/render.py:281-409: render_rays,
     img2mse on the fine and the coarse colour map, loss.backward(), optimizer.step()) without the autograd round trip: the operators
     of classic.render_rays called directly, ONE loss-tail pair of launches (ops.classic_loss_tail: loss, psnr and d loss / d rgb), the
@@ -1386,7 +1381,7 @@ class ClassicTrainer(_AdamState):
     `state_dict()` / `load_state_dict()`: torch.optim.Adam's layout over create_nerf's grad_vars order -- the coarse network's
     parameters, then the fine one's -- with one step count: the `optimizer_state_dict` of the reference's checkpoints
     (render.py:165-278; classic.create_nerf)."""
-    what = "classic"
+    what, named = "classic", True
 
     def __init__(self, network_fn, network_query_fn=None, N_samples=64, N_importance=0, network_fine=None, lr=5e-4, betas=(0.9, 0.999), eps=1e-8,
                  perturb=1., lindisp=False, white_bkgd=False, raw_noise_std=0., nonfinite="zero", loss_scale=1.0, process_group=None,
@@ -1426,7 +1421,6 @@ class ClassicTrainer(_AdamState):
         for net in nets:
             net.arena.grad.zero_()
         self._const, self._ws = {}, None
-        self._batcher = None
 
     # ---- the optimiser state ------------------------------------------------------------------------------------------------------
     def _layout(self):
@@ -1437,14 +1431,7 @@ class ClassicTrainer(_AdamState):
             out += [(tag + n, base + a._offs[n][0], a._offs[n][1], a.shapes[n]) for n, _ in x.net.named_parameters()]
         return out
 
-    def state_dict(self):
-        sd = super().state_dict()
-        sd["param_names"] = [n for n, *_ in self._layout()]
-        return sd
-
     def load_state_dict(self, sd):
-        if "param_names" in sd and list(sd["param_names"]) != [n for n, *_ in self._layout()]:
-            raise ValueError("optimizer state was saved for other parameter names")
         super().load_state_dict(sd)
         for x in self.nets:
             if x.step_dev is not None:
@@ -1592,59 +1579,24 @@ class ClassicTrainer(_AdamState):
         `replay()` follows it with the all-reduces and the Adam launches."""
         if batcher is None and (ray_batch is None or target_rgb is None):
             raise ValueError("ClassicTrainer.capture: give ray_batch= and target_rgb=, or batcher=")
-        dev = self.network_fn.arena.flat.device
         buf = None
         if batcher is not None:
             buf = batcher.buffers()
             ray_batch, target_rgb = buf["rays"], buf["rgb"]
-        snaps = [x.snapshot() for x in self.nets]
-        if self.world == 1:
-            for x in self.nets:
-                x.arm()
-        self._batcher, self.batch = batcher, (ray_batch, target_rgb)
-        if batcher is not None:
-            b_snap = (batcher.counter.clone(), batcher.step)
+        self.batch = (ray_batch, target_rgb)
+        return self._capture(warmup, batcher, buf, lambda: self.step(ray_batch, target_rgb), lambda: self._forward_backward(ray_batch, target_rgb))
 
-        def draw():
-            if batcher is not None:
-                batcher.next_into(buf)
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):                    # warm-up on a side stream
-            for _ in range(warmup):
-                draw()
-                self.step(ray_batch, target_rgb)
-        torch.cuda.current_stream(dev).wait_stream(side)
-        for x, snap in zip(self.nets, snaps):
-            x.restore(snap)
-            x.net.arena.bump()                           # (the restored parameters are new values to the packed operands)
-        if batcher is not None:                          # capturing uses up no draws
-            batcher.counter.copy_(b_snap[0])
-        self._graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self._graph):
-            draw()
-            if self.world == 1:
-                self._graph_loss, self._graph_outs = self.step(ray_batch, target_rgb)
-            else:
-                self._graph_loss, self._graph_outs = self._forward_backward(ray_batch, target_rgb)
-        if batcher is not None:
-            batcher._step = b_snap[1]
-        if self.world == 1:
-            self.t -= 1                                  # capturing records the step, it does not run it
-        return self._graph_loss
+    def _trained(self):
+        return self.nets
 
-    def replay(self):
-        """One captured step.  -> (loss, out): the same device tensors every time, overwritten by each replay."""
-        if self._batcher is not None:
-            self._batcher.advance_host(1)                # the graph's first node drew the batch and advanced the device counter
-        if self.world == 1:
-            for x in self.nets:
-                x.lr_dev.fill_(self.lr)                  # the graph reads the learning rate from the device
-            self._graph.replay()
-            self.t += 1
-        else:
-            self._graph.replay()                         # forward + loss tail + backward of this rank's shard
-            for e in self._exchanges():
-                e.finish()                               # one all-reduce per gradient arena
-            self._update()
-        return self._graph_loss, self._graph_outs
+    def _counted(self):
+        return [self]                                    # (the nets' `t` is the trainer's: one count for both)
+
+    def _bump_restored(self):
+        for x in self.nets:
+            x.net.arena.bump()
+
+    def _after_graph(self):
+        for e in self._exchanges():
+            e.finish()                                   # one all-reduce per gradient arena
+        self._update()

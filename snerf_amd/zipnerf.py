@@ -23,6 +23,7 @@ import torch
 from torch import nn
 
 from . import ops
+from .batching import DrawCounter, shard_bounds
 from .classic import _ArenaModule, _dt
 from .mlp import ZipNerfNet, ZipPropNet
 
@@ -601,7 +602,7 @@ class _ZipFn(torch.autograd.Function):
         return (None,) * 7 + rays_g + grads
 
 
-class RayBatcher:
+class RayBatcher(DrawCounter):
     """Device-resident form of Dataset._next_train + _make_ray_batch (s-nerfpp/zipnerf/internal/datasets.py:442-566, patch_size 1): the
     training images (and optional depth, semantic labels, masks) live on the device and `next()` draws, casts and gathers one batch in
     ONE launch (`snerf_zip_ray_batch`): no numpy ray computation on the host, no upload, no sync.
@@ -624,9 +625,6 @@ class RayBatcher:
                                       "PatchRayBatcher draws the patch batches")
         if batching not in ('all_images', 'single_image'):
             raise ValueError(f"batching: 'all_images' or 'single_image', not {batching!r}")
-        if not 0 <= int(seed) < (1 << 63):
-            raise ValueError("seed must be in [0, 2^63)")
-        dev = torch.device(device)
         img = torch.as_tensor(images) if not torch.is_tensor(images) else images.detach()
         if img.dim() != 4 or img.shape[-1] != 3 or img.shape[0] == 0:
             raise ValueError("images: [N, H, W, 3] with N >= 1")
@@ -636,6 +634,8 @@ class RayBatcher:
             raise ValueError(f"border {border} leaves no pixel of a {H} x {W} image")
         if not 0 < int(batch_size) < (1 << 32):
             raise ValueError("batch_size must be in [1, 2^32)")
+        super().__init__(batch_size, seed, rank, world, device)
+        dev = self.device
         t = lambda a, dt: None if a is None else (torch.as_tensor(a) if not torch.is_tensor(a) else a.detach()).to(dev, dt).contiguous()
         self.images = img.to(dev, torch.uint8 if img.dtype == torch.uint8 else torch.float32).contiguous()
         self.pixtocams, self.camtoworlds = t(pixtocams, torch.float32).reshape(N, 3, 3), t(camtoworlds, torch.float32)[:, :3, :4].contiguous()
@@ -647,35 +647,10 @@ class RayBatcher:
                 raise ValueError(f"{name}: [N, H, W] = {(N, H, W)}, got {tuple(a.shape)}")
         if self.camtoworlds.shape[0] != N or (self.local2global is not None and self.local2global.numel() != N):
             raise ValueError("camtoworlds / local2global: one per image")
-        from .trainer import shard_bounds
         self.N, self.H, self.W, self.batch_size, self.border = N, H, W, int(batch_size), border
         self.near, self.far, self.single_image = float(near), float(far), batching == 'single_image'
-        self.rank, self.world = int(rank), int(world)
-        self.i0, self.i1 = shard_bounds(self.batch_size, self.rank, self.world)
-        self.seed, self.device = int(seed), dev
-        self.counter = torch.zeros(2, dtype=torch.int64, device=dev)           # {step, workgroup ticket}: advanced by the launch
-        self._step = 0
 
-    @property
-    def step(self):
-        """the step of the next draw (host mirror of the device counter; `advance_host` after graph replays of `next_into`)"""
-        return self._step
-
-    @property
-    def rows(self):
-        """rows of this rank's batch"""
-        return self.i1 - self.i0
-
-    def state_dict(self):
-        return {"seed": self.seed, "step": self._step}
-
-    def load_state_dict(self, sd):
-        self.seed, self._step = int(sd["seed"]), int(sd["step"])
-        self.counter.copy_(torch.tensor([self._step, 0], dtype=torch.int64))
-
-    def advance_host(self, k=1):
-        """tell the host mirror that k draws ran inside graph replays"""
-        self._step += int(k)
+    rows = property(lambda self: self.n_rows, doc="rows of this rank's batch (DrawCounter's n_rows, under the name the zip callers use)")
 
     def buffers(self):
         """fresh output tensors of one batch (this rank's rows)"""
@@ -698,12 +673,7 @@ class RayBatcher:
         """draw the next batch into `buf` (from `buffers()`) on the current stream; graph-capturable -> buf"""
         ops.zip_ray_batch(self.images, self.depths, self.semantics, self.masks, self.pixtocams, self.camtoworlds, self.local2global, self.near,
                           self.far, self.border, 1, self.single_image, self.seed, self.counter, self.batch_size, self.i0, self.i1, buf)
-        self._step += 1
-        return buf
-
-    def next(self):
-        """-> the batch dict of the next step in new tensors (they stay valid)"""
-        return self.next_into(self.buffers())
+        return self._drawn(buf)
 
 
 class PatchRayBatcher(RayBatcher):
@@ -729,7 +699,6 @@ class PatchRayBatcher(RayBatcher):
         if len(shape) == 4 and int(border) >= 0 and 2 * int(border) + p > min(shape[1:3]):      # (before anything goes to the device)
             raise ValueError(f"no {p} x {p} patch fits a {shape[1]} x {shape[2]} image inside a border of {int(border)}")
         super().__init__(images, pixtocams, camtoworlds, near, far, batch_size=n, border=border, patch_size=1, rank=rank, world=world, **kw)
-        from .trainer import shard_bounds
         self.patch_size, self.n_patch = p, (n // 4) // (p * p)
         self.k0, self.k1 = shard_bounds(self.n_patch, self.rank, self.world)
         first = self.n_patch * p * p
@@ -738,12 +707,11 @@ class PatchRayBatcher(RayBatcher):
         self.n_patch_rows = self.n_patch_local * p * p
 
     @property
-    def rows(self):
+    def n_rows(self):
         return self.n_patch_rows + (self.i1 - self.i0)
 
     def next_into(self, buf):
         ops.zip_ray_patch_batch(self.images, self.depths, self.semantics, self.masks, self.pixtocams, self.camtoworlds, self.local2global,
                                 self.near, self.far, self.border, self.patch_size, self.single_image, self.seed, self.counter, self.batch_size,
                                 self.k0, self.k1, self.i0, self.i1, buf)
-        self._step += 1
-        return buf
+        return self._drawn(buf)
