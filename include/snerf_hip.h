@@ -641,6 +641,51 @@ int snerf_fg_blank(void* im, const void* bound, long nbytes, void* stream);
  * does not depend on their order and is bit-reproducible.  Bad arguments (N outside [2, 32], H or W outside [1, 65535], a null masks,
  * mask or stats pointer) return 1 before any launch. */
 int snerf_fg_overlap(const void* const* masks, int N, int H, int W, long* stats, void* stream);
+/* The lighting match of stage 1 (utils_render.py:1008-1051 handle_lighting, called by fuse() on the whole frame after every paste, :300;
+ * lighting.hip).  Both entries are bit-exact against the numpy model in snerf_amd/foreground.py (rgb_to_hsv_u8_host, hsv_to_rgb_u8_host,
+ * handle_lighting_host, lighting_stats_host).
+ *
+ * snerf_fg_hsv: in place on P packed 3-byte pixels, any byte alignment of px, any P >= 1 (no limit but `long`).  to_rgb = 0 is OpenCV's
+ * 8-bit COLOR_RGB2HSV with H range 180, to_rgb = 1 its 8-bit COLOR_HSV2RGB, both restated from the scalar code of OpenCV's imgproc
+ * color_hsv (RGB2HSV_b; HSV2RGB_b over HSV2RGB_native):
+ *   RGB -> HSV, integers, shift 12: sdiv[i] = rint((255 << 12) / (1.0 i)), hdiv[i] = rint((180 << 12) / (6.0 i)), i = 1 .. 255, double
+ *     division, half to even, entry 0 = 0.  v = max(r, g, b), diff = v - min(r, g, b), s = (diff sdiv[v] + 2048) >> 12; h0 = g - b if
+ *     v == r, else b - r + 2 diff if v == g, else r - g + 4 diff; h = (h0 hdiv[diff] + 2048) >> 12 (arithmetic shift), + 180 if h < 0.
+ *   HSV -> RGB, fp32, every operation rounded on its own: hf = float(h) * (6.f / 180.f), sf = float(s) * (1.f / 255.f), vf = float(v) *
+ *     (1.f / 255.f) (the constants are fp32 divisions).  sf == 0: all three channels are vf.  Otherwise hf = fmodf(hf, 6.f), sector =
+ *     floor(hf), hf -= sector (a sector outside 0 .. 5 becomes sector 0 with hf = 0); tab = {vf, vf (1 - sf), vf (1 - sf hf),
+ *     vf (1 - sf (1 - hf))}; (b, g, r) = tab[{1,3,0}, {1,0,2}, {3,0,1}, {0,2,1}, {0,1,3}, {2,1,0}][sector].  Each channel is
+ *     rint(x * 255.f) (half to even) saturated to 0 .. 255.  H = 180 .. 255 is legal input and follows the same formula.
+ * Refused (1, before any launch): a null px, P < 1, to_rgb outside 0 / 1.
+ *
+ * snerf_fg_lighting: im [H,W,3] u8, changed in place; mask [H,W,3] u8 of which only channel 0 is read, as mask[..., 0] > 0 (a 1 counts,
+ * channels 1 and 2 do not).  On V = max(r, g, b), the V channel of the frame's HSV image:
+ *   fg = the pixels with mask[..., 0] > 0, (i_min, i_max, j_min, j_max) their bounding rows and columns, i_len = i_max - i_min, j_len =
+ *     j_max - j_min; the box grows to rows [max(0, i_min - i_len / 2 - 1), min(H - 1, i_max + i_len / 2 + 1)] and the same for the columns
+ *     with W; bg = the pixels with mask[..., 0] == 0 inside the grown box, bounds inclusive.
+ *   fg_mean = sum_v_fg / n_fg, bg_mean = sum_v_bg / n_bg: double divisions of exact integer sums (numpy's float64 mean of uint8 data).
+ *   V' = (uint8) trunc(clip((double(V) - fg_mean) + bg_mean, 0, 255)) on fg, two double additions in this order -- unless all fg V are
+ *     equal (`if not fg_var < 1e-7`), decided as n_fg sum_v2_fg == sum_v_fg^2 in int64: then V stays.  The smallest non-zero variance
+ *     of n bytes is (n - 1) / n^2 = 1.19e-7 > 1e-7 at n = 2^23, so up to H W = 2^23 the integer test and numpy's agree for every input
+ *     and both sides fit in int64; hence the size limit.
+ *   keep_background = 0 (the reference): EVERY pixel of the frame is rewritten as hsv2rgb(rgb2hsv(.)) with the V above, also when the
+ *     mask is empty (:1018-1019) or no shift applies.  keep_background = 1 (an extension): pixels with mask[..., 0] == 0 keep their
+ *     bytes, fg pixels get exactly the keep_background = 0 result.
+ *   Deviation: a mask that fills its whole grown box leaves n_bg = 0; the reference then casts the NaN mean of an empty array to uint8
+ *     (undefined).  Here V stays unchanged in that case.
+ * stats: device long[9], scratch and output, initialised by the entry itself (an init launch on `stream`): {i_min, i_max, j_min,
+ * j_max, n_fg, sum_v_fg, sum_v2_fg, n_bg, sum_v_bg}; the box is that of the RAW mask, before it grows.  An empty mask leaves n_fg = 0
+ * and the sentinels (i_min, i_max, j_min, j_max) = (H, -1, W, -1); n_bg and sum_v_bg are then 0 too.  The init launch and three
+ * kernels (fg statistics; bg statistics, whose workgroups read the box from stats on the device and exit outside its rows; apply); no
+ * host read, no sync, capturable in a graph.  Integer sums through wave and workgroup partials and 64-bit integer atomics: no
+ * floating-point atomics, the result does not depend on the order.  Any byte alignment of im and mask.
+ * Refused (1, before any launch): a null im / mask / stats, H or W < 1, H * W > 2^23, keep_background outside 0 / 1.
+ *
+ * PARITY: cv2 is installed neither where this was written nor where it was run, so the two conversions follow OpenCV's published scalar
+ * code and are UNPINNED against the library -- in particular whether a SIMD build of HSV2RGB fuses v * (1 - s * h).  Everything after
+ * the conversions (box, means, shift, clip, cast) is pinned: it is the reference's own numpy. */
+int snerf_fg_hsv(void* px, long P, int to_rgb, void* stream);
+int snerf_fg_lighting(void* im, const void* mask, int H, int W, int keep_background, long* stats, void* stream);
 
 /* Hash-grid weight decay (s-nerfpp/zipnerf/internal/train_utils.py:184-203 hash_decay_loss; torch_scatter.segment_coo(param**2, idx,
  * reduce='mean').mean() per encoder): table / grad fp32 [rows, C] (grad accumulated: += 2 mult p / (rows_l L C)), offsets device int32

@@ -21,9 +21,22 @@ pair traced against both meshes, the reference's topological sort on the host af
 runs it between rendering and pasting.  The KITTI-style label row of an instance (utils_render.py:543-640) is `bbox_result` /
 `save_bbox_results` (host, from the `occlusion` scalars composite_frame returns; `occlusion_level` is its threshold rule).
 
+The lighting match (utils_render.py:1008-1051 handle_lighting, which fuse() runs on the whole frame after every paste, :300) is
+`handle_lighting`: cv2's 8-bit RGB -> HSV, the instance's V shifted by the difference between the mean V of the unmasked pixels in a box
+half as large again around the mask and the mean V of the mask, and HSV -> RGB, in one init launch and three kernels without a host read
+(snerf_fg_lighting; the conversions alone: `rgb_to_hsv_u8` / `hsv_to_rgb_u8`, snerf_fg_hsv).  `composite_frame(lighting="frame")` runs
+it after each paste as the reference does, `lighting="masked"` confines it to the instance's pixels, and the default leaves it out.  The
+numpy model the kernels are compared with bit for bit is here too (`handle_lighting_host`, `lighting_stats_host`, `rgb_to_hsv_u8_host`,
+`hsv_to_rgb_u8_host`); numpy arrays given to the three public functions go through it, so the reference's own call
+`handle_lighting(im_mat, mask_mat)` works without cv2.
+PARITY: cv2 is installed neither where this was written nor where it was run, so the two conversions follow OpenCV's published scalar
+code (imgproc color_hsv: RGB2HSV_b with H range 180, HSV2RGB_b over HSV2RGB_native) and are UNPINNED against the library -- in particular
+whether a SIMD build of HSV2RGB fuses v * (1 - s * h).  Everything after the conversions (box, means, shift, clip, cast) is pinned: it
+is the reference's own numpy.  One documented deviation: a mask that fills its whole expanded box leaves no background pixel; the
+reference casts the NaN mean of an empty array to uint8 (undefined), here V stays unchanged.
+
 Not here (they stay with the caller): mesh loading (trimesh, kaolin's .obj import) and `trimesh.bounds.oriented_bounds` (the `extents`
-of bbox_result: a per-mesh constant), the kaolin camera algebra of mesh_renderer.py:187-221 (INTEGRATION.md gives the correspondence),
-and `handle_lighting` (cv2's 8-bit HSV round trip)."""
+of bbox_result: a per-mesh constant) and the kaolin camera algebra of mesh_renderer.py:187-221 (INTEGRATION.md gives the correspondence)."""
 import ctypes
 import math
 
@@ -128,6 +141,134 @@ def fuse_bound_and_im(fuse_im, bound_im):
     _u8(fuse_im); _u8(bound_im, fuse_im.shape)
     _lib.call("snerf_fg_blank", _p(fuse_im), _p(bound_im), fuse_im.numel(), _stream())
     return fuse_im
+
+
+# ---- the lighting match: utils_render.py:1008-1051 handle_lighting ------------------------------------------------------------------
+_HSV_SHIFT = 12
+_SDIV = np.concatenate([[0], np.rint((255 << _HSV_SHIFT) / (1.0 * np.arange(1, 256)))]).astype(np.int32)    # color_hsv: sdiv_table, hdiv_table180
+_HDIV = np.concatenate([[0], np.rint((180 << _HSV_SHIFT) / (6.0 * np.arange(1, 256)))]).astype(np.int32)
+LIGHTING_MAX_PIXELS = 1 << 23      # up to here "all fg V equal" in integers is numpy's `fg_var < 1e-7` for every input (snerf_hip.h)
+
+
+def _px_host(px):
+    px = np.asarray(px)
+    assert px.dtype == np.uint8 and px.ndim >= 1 and px.shape[-1] == 3, "expected a uint8 array [..., 3]"
+    return px
+
+
+def rgb_to_hsv_u8_host(px):
+    """numpy model of snerf_fg_hsv(to_rgb=0): OpenCV's 8-bit COLOR_RGB2HSV (H range 180), integers with shift 12 -> new uint8 array"""
+    px = _px_host(px).astype(np.int32)
+    r, g, b = px[..., 0], px[..., 1], px[..., 2]
+    v = np.maximum(np.maximum(r, g), b)
+    diff = v - np.minimum(np.minimum(r, g), b)
+    s = (diff * _SDIV[v] + (1 << (_HSV_SHIFT - 1))) >> _HSV_SHIFT
+    h0 = np.where(v == r, g - b, np.where(v == g, b - r + 2 * diff, r - g + 4 * diff))
+    h = (h0 * _HDIV[diff] + (1 << (_HSV_SHIFT - 1))) >> _HSV_SHIFT                              # arithmetic shift (int32)
+    h = h + np.where(h < 0, 180, 0)
+    return np.stack([h, s, v], axis=-1).astype(np.uint8)
+
+
+def hsv_to_rgb_u8_host(px):
+    """numpy model of snerf_fg_hsv(to_rgb=1): OpenCV's 8-bit COLOR_HSV2RGB, fp32 with every operation rounded on its own (numpy keeps
+    float32 operands float32) -> new uint8 array.  H = 180 .. 255 follows the same formula."""
+    px = _px_host(px)
+    f32, one = np.float32, np.float32(1)
+    hf = px[..., 0].astype(f32) * (f32(6) / f32(180))
+    sf = px[..., 1].astype(f32) * (one / f32(255))
+    vf = px[..., 2].astype(f32) * (one / f32(255))
+    hf = np.fmod(hf, f32(6))
+    sector = np.floor(hf)
+    hf = hf - sector
+    sector = sector.astype(np.int32)
+    bad = (sector < 0) | (sector >= 6)
+    sector = np.where(bad, 0, sector)
+    hf = np.where(bad, f32(0), hf)
+    tab = np.stack([vf, vf * (one - sf), vf * (one - sf * hf), vf * (one - sf * (one - hf))], axis=-1)
+    idx = np.array([[1, 3, 0], [1, 0, 2], [3, 0, 1], [0, 2, 1], [0, 1, 3], [2, 1, 0]])[sector]  # [..., (b, g, r)]
+    bgr = np.take_along_axis(tab, idx, axis=-1)
+    bgr = np.where((sf == 0)[..., None], vf[..., None], bgr)
+    assert bgr.dtype == np.float32
+    out = np.clip(np.rint(bgr * f32(255)), 0, 255).astype(np.uint8)
+    return out[..., ::-1].copy()
+
+
+def _lighting_stats(v, fg, H, W):
+    """v [H,W] uint8 = the V channel, fg [H,W] bool -> the nine python ints of snerf_fg_lighting's stats"""
+    ii, jj = np.nonzero(fg)
+    if ii.size == 0:
+        return [H, -1, W, -1, 0, 0, 0, 0, 0]
+    i_min, i_max, j_min, j_max = int(ii.min()), int(ii.max()), int(jj.min()), int(jj.max())
+    i_len, j_len = i_max - i_min, j_max - j_min
+    i0, i1 = max(0, i_min - i_len // 2 - 1), min(H - 1, i_max + i_len // 2 + 1)
+    j0, j1 = max(0, j_min - j_len // 2 - 1), min(W - 1, j_max + j_len // 2 + 1)
+    box, bg = v[i0:i1 + 1, j0:j1 + 1].astype(np.int64), ~fg[i0:i1 + 1, j0:j1 + 1]
+    vf = v[fg].astype(np.int64)
+    return [i_min, i_max, j_min, j_max, int(vf.size), int(vf.sum()), int((vf * vf).sum()), int(bg.sum()), int(box[bg].sum())]
+
+
+def lighting_stats_host(im, mask):
+    """The nine integers snerf_fg_lighting leaves in `stats`: (i_min, i_max, j_min, j_max) of the raw mask (sentinels (H, -1, W, -1) when
+    it is empty), n_fg, sum_v_fg, sum_v2_fg, n_bg, sum_v_bg (the last two over the expanded box; 0 for an empty mask) -> int64 [9]"""
+    im, mask = _px_host(im), _px_host(mask)
+    H, W, _ = im.shape
+    return np.array(_lighting_stats(im.max(axis=-1), mask[..., 0] > 0, H, W), dtype=np.int64)
+
+
+def handle_lighting_host(im, mask, keep_background=False):
+    """numpy model of snerf_fg_lighting = utils_render.py:1008-1051 with the conversions above in cv2's place -> new uint8 [H,W,3]"""
+    im, mask = _px_host(im), _px_host(mask)
+    H, W, _ = im.shape
+    assert mask.shape == im.shape and H * W <= LIGHTING_MAX_PIXELS, "mask and frame [H,W,3], at most 2^23 pixels"
+    hsv = rgb_to_hsv_u8_host(im)
+    fg = mask[..., 0] > 0
+    n_fg, s1, s2, n_bg, s_bg = _lighting_stats(hsv[..., 2], fg, H, W)[4:]
+    if n_fg > 0 and n_bg > 0 and n_fg * s2 != s1 * s1:               # `if not fg_var < 1e-7`, in integers; n_bg == 0: the deviation
+        fg_mean, bg_mean = np.float64(s1) / np.float64(n_fg), np.float64(s_bg) / np.float64(n_bg)
+        v = hsv[..., 2][fg] - fg_mean + bg_mean
+        hsv[..., 2][fg] = np.clip(v, 0, 255).astype(np.uint8)
+    out = hsv_to_rgb_u8_host(hsv)
+    if keep_background:
+        out[~fg] = im[~fg]
+    return out
+
+
+def _hsv_u8(px, to_rgb):
+    if isinstance(px, np.ndarray):
+        return hsv_to_rgb_u8_host(px) if to_rgb else rgb_to_hsv_u8_host(px)
+    _u8(px)
+    assert px.dim() >= 1 and px.shape[-1] == 3 and px.numel() > 0, "expected a non-empty uint8 tensor [..., 3]"
+    _lib.call("snerf_fg_hsv", _p(px), px.numel() // 3, int(to_rgb), _stream())
+    return px
+
+
+def rgb_to_hsv_u8(px):
+    """cv2.cvtColor(px, cv2.COLOR_RGB2HSV) of 8-bit pixels [..., 3] (H in 0 .. 179).  A device tensor is converted in place (snerf_fg_hsv,
+    any byte offset of a contiguous view) and returned; a numpy array goes through the host model and a new array is returned."""
+    return _hsv_u8(px, False)
+
+
+def hsv_to_rgb_u8(px):
+    """cv2.cvtColor(px, cv2.COLOR_HSV2RGB) of 8-bit pixels [..., 3]; device tensor in place, numpy array -> new array (see rgb_to_hsv_u8)"""
+    return _hsv_u8(px, True)
+
+
+def handle_lighting(im, mask, keep_background=False, stats=None):
+    """utils_render.py:1008-1051 handle_lighting(im_mat, mask_mat).  Device tensors im [H,W,3] u8 and mask [H,W,3] u8 (channel 0 > 0 is
+    the instance): in place on im, which is returned; one init launch and three kernels, no host read (snerf_fg_lighting).  `stats`: an
+    optional preallocated int64 [9] device tensor (needed under graph capture), left holding (i_min, i_max, j_min, j_max, n_fg, sum_v_fg,
+    sum_v2_fg, n_bg, sum_v_bg) as lighting_stats_host gives them.  keep_background=True (an extension) leaves the pixels outside the
+    mask untouched; the reference rewrites the whole frame through the lossy 8-bit HSV round trip.  H * W <= 2^23.
+    numpy arrays: the reference's own call, through handle_lighting_host -> a new array."""
+    if isinstance(im, np.ndarray):
+        return handle_lighting_host(im, np.asarray(mask), keep_background)
+    H, W, _ = im.shape
+    _u8(im, (H, W, 3)); _u8(mask, (H, W, 3))
+    if stats is None:
+        stats = torch.empty(9, dtype=torch.int64, device=im.device)
+    assert stats.is_cuda and stats.dtype == torch.int64 and stats.is_contiguous() and stats.numel() == 9, "stats: an int64 [9] device tensor"
+    _lib.call("snerf_fg_lighting", _p(im), _p(mask), H, W, int(bool(keep_background)), _p(stats), _stream())
+    return im
 
 
 def overlap_stats(masks):
@@ -304,7 +445,7 @@ def _ordered_by_occlusion(instances, depth_mat, w2c, intrinsic):
     return [instances[i] for i in order], order
 
 
-def composite_frame(bg_im, depth_mat, semantic_mat, instances, order="given", w2c=None, intrinsic=None):
+def composite_frame(bg_im, depth_mat, semantic_mat, instances, order="given", w2c=None, intrinsic=None, lighting=None):
     """The instance loop of generate_images.py:80-166 for one frame.  `instances`: iterable of dict(image [H,W,3] u8, mask [H,W,3] u8,
     fg_depth [H,W] f32 or None, category, r (optional band width)); instead of
     fg_depth an instance may carry mesh = (meshtrace.RayTracer, transform or None) and intrinsic (3 x 3, host): its depth is then
@@ -316,11 +457,16 @@ def composite_frame(bg_im, depth_mat, semantic_mat, instances, order="given", w2
     host) and `intrinsic` (3 x 3, host; also that of an instance without its own) are given; the instances with render = are rendered
     first, all of them, `occlusion_order(masks, meshes, w2c, intrinsic)` sorts them (generate_images.py:76-81) and the loop runs in that
     order.  The result then has `order`, indices into `instances` as given; a missing mesh is a ValueError that names the instance.
+    lighting=None (the default): no lighting match.  lighting="frame": `handle_lighting(bg_im, tested)` directly after each paste, for every
+    category, with the depth-tested mask, as fuse() does (utils_render.py:300): the whole frame goes through the 8-bit HSV round trip once
+    per instance.  lighting="masked": the same with keep_background=True.  Anything else is a ValueError.
     In place on bg_im / depth_mat / semantic_mat; returns dict(fuse, mask, bound, occluded_mask, depth, semantic, occlusion [per
     instance], instance_masks, instance_bounds) = the images the reference saves per frame (:153-154,186-196); the per-instance lists are
     in the order of processing."""
     if order not in ("given", "occlusion"):
         raise ValueError(f"composite_frame: order must be 'given' or 'occlusion', not {order!r}")
+    if lighting not in (None, "frame", "masked"):
+        raise ValueError(f"composite_frame: lighting must be None, 'frame' or 'masked', not {lighting!r}")
     paste_order = None
     if order == "occlusion":
         instances, paste_order = _ordered_by_occlusion(instances, depth_mat, w2c, intrinsic)
@@ -345,6 +491,8 @@ def composite_frame(bg_im, depth_mat, semantic_mat, instances, order="given", w2
             tracer, transform = inst["mesh"]
             fg_depth = mesh_depth(tracer, inst["intrinsic"], depth_mat.shape[0], depth_mat.shape[1], mask, transform)
         occ.append(handle_occlusion_paste(bg_im, image, tested, depth_mat, semantic_mat, fg_depth, cat))
+        if lighting is not None:
+            handle_lighting(bg_im, tested, keep_background=lighting == "masked")
         bound, mask_d = get_bound_im(mask, r, return_mask_diff=True)
         accumulate(total_mask, total_bound, bound, mask_d)
         if cat == "vehicle":
