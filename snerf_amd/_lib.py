@@ -81,7 +81,12 @@ def load_io():
 
 
 class SnerfHipError(RuntimeError):
-    pass
+    """the library refused the call (status 1) or a launch failed (status 2)"""
+
+
+class SnerfArgumentError(ValueError, AssertionError):
+    """the Python layer refused an argument before any launch.  ValueError is the package's convention for caller errors; AssertionError
+    keeps callers that caught the `assert` statements these checks once were."""
 
 
 _STATUS = {1: "bad argument", 2: "kernel launch failure"}

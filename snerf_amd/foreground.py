@@ -44,26 +44,20 @@ import numpy as np
 import torch
 
 from . import _lib
-from .ops import _p, _stream
+from .ops import _dev, _p, _require, _stream
 
 SEMANTIC_ID = {"vehicle": 13, "person": 11, "object": 0, "bicycle": 18, "motorcycle": 17}     # utils_render.py:934-936
-
-
-def _u8(t, shape=None):
-    assert t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous() and (shape is None or tuple(t.shape) == tuple(shape)), \
-        "expected a contiguous uint8 CUDA tensor" + ("" if shape is None else f" of shape {tuple(shape)}")
-    return t
 
 
 def handle_occlusion_paste(bg_im, vehicle_im, mask_im, depth_mat, semantic_mat, fg_depth, category="vehicle"):
     """In place on bg_im [H,W,3] u8, mask_im [H,W,3] u8, depth_mat [H,W] f32, semantic_mat [H,W] u8; `fg_depth` [H,W] f32 = mesh depth
     per pixel (None for category "person").  Returns occlusion_per as a device scalar (no host sync)."""
     H, W = depth_mat.shape
-    _u8(bg_im, (H, W, 3)); _u8(vehicle_im, (H, W, 3)); _u8(mask_im, (H, W, 3)); _u8(semantic_mat, (H, W))
-    assert depth_mat.dtype == torch.float32 and depth_mat.is_contiguous() and depth_mat.is_cuda
+    _dev("bg_im vehicle_im mask_im", bg_im, vehicle_im, mask_im, dtype=torch.uint8, shape=(H, W, 3))
+    _dev("semantic_mat", semantic_mat, dtype=torch.uint8, shape=(H, W)); _dev("depth_mat", depth_mat)
     person = category == "person"
     if not person:
-        assert fg_depth is not None and fg_depth.dtype == torch.float32 and fg_depth.is_contiguous() and tuple(fg_depth.shape) == (H, W)
+        _dev("fg_depth", fg_depth, shape=(H, W))
     cnt = torch.empty(2, dtype=torch.int32, device=bg_im.device)
     _lib.call("snerf_fg_paste", _p(bg_im), _p(vehicle_im), _p(mask_im), _p(depth_mat), _p(semantic_mat), _p(None if person else fg_depth), H * W,
               SEMANTIC_ID[category], int(person), _p(cnt), _stream())
@@ -73,7 +67,7 @@ def handle_occlusion_paste(bg_im, vehicle_im, mask_im, depth_mat, semantic_mat, 
 
 def _intrinsic(intrinsic):
     """(fx, fy, cx, cy) as python floats from a 3 x 3 (or larger) intrinsic matrix held on the HOST (numpy, nested lists, a CPU tensor)"""
-    assert not (torch.is_tensor(intrinsic) and intrinsic.is_cuda), "intrinsic: host values (a device matrix would cost a sync per call)"
+    _require(not (torch.is_tensor(intrinsic) and intrinsic.is_cuda), "intrinsic: host values (a device matrix would cost a sync per call)")
     K = np.asarray(intrinsic, dtype=np.float64)
     return float(K[0, 0]), float(K[1, 1]), float(K[0, 2]), float(K[1, 2])
 
@@ -88,7 +82,7 @@ def mesh_depth(tracer, intrinsic, H, W, mask_im, transform=None):
     the ray misses or the depth is >= 99 (`depth[depth >= 99.] = .1`), 0 outside the mask.  `transform` (3 x 4 or 4 x 4, host or device)
     is what places the tracer's mesh into `mesh_in_cam_coord`; the reference's diag(1, -1, -1) flip is composed in here.  No host sync."""
     from . import meshtrace
-    _u8(mask_im, (H, W, 3))
+    _dev("mask_im", mask_im, dtype=torch.uint8, shape=(H, W, 3))
     fx, fy, cx, cy = _intrinsic(intrinsic)
     flip = _FLIP_ON.get(tracer.device)
     if flip is None:
@@ -121,7 +115,7 @@ def bound_radius(mask_im, category="vehicle"):
 def get_bound_im(mask_im, r, return_mask_diff=False):
     """-> bound_im [H,W,3] u8 (and, with return_mask_diff, set_diff(mask_im, bound_im) from the same launch)."""
     H, W, _ = mask_im.shape
-    _u8(mask_im, (H, W, 3))
+    _dev("mask_im", mask_im, dtype=torch.uint8, shape=(H, W, 3))
     bound = torch.empty_like(mask_im)
     diff = torch.empty_like(mask_im) if return_mask_diff else None
     _lib.call("snerf_fg_bound", _p(mask_im), H, W, max(1, int(r)), _p(bound), _p(diff), _stream())
@@ -131,14 +125,13 @@ def get_bound_im(mask_im, r, return_mask_diff=False):
 def accumulate(total_mask, total_bound, bound_im, mask_im):
     """In place: total_bound <- fuse_bound(total_mask, total_bound, bound_im, mask_im); total_mask <- mask_im | total_mask.
     Zero-initialised totals reproduce the reference's first-instance special case."""
-    for t in (total_mask, total_bound, bound_im, mask_im):
-        _u8(t, total_mask.shape)
+    _dev("total_mask total_bound bound_im mask_im", total_mask, total_bound, bound_im, mask_im, dtype=torch.uint8, shape=tuple(total_mask.shape))
     _lib.call("snerf_fg_accumulate", _p(total_mask), _p(total_bound), _p(bound_im), _p(mask_im), total_mask.numel(), _stream())
 
 
 def fuse_bound_and_im(fuse_im, bound_im):
     """In place: fuse_im[bound_im > 0] = 0."""
-    _u8(fuse_im); _u8(bound_im, fuse_im.shape)
+    _dev("fuse_im bound_im", fuse_im, bound_im, dtype=torch.uint8, shape=tuple(fuse_im.shape))
     _lib.call("snerf_fg_blank", _p(fuse_im), _p(bound_im), fuse_im.numel(), _stream())
     return fuse_im
 
@@ -152,7 +145,7 @@ LIGHTING_MAX_PIXELS = 1 << 23      # up to here "all fg V equal" in integers is 
 
 def _px_host(px):
     px = np.asarray(px)
-    assert px.dtype == np.uint8 and px.ndim >= 1 and px.shape[-1] == 3, "expected a uint8 array [..., 3]"
+    _require(px.dtype == np.uint8 and px.ndim >= 1 and px.shape[-1] == 3, "expected a uint8 array [..., 3]")
     return px
 
 
@@ -188,7 +181,8 @@ def hsv_to_rgb_u8_host(px):
     idx = np.array([[1, 3, 0], [1, 0, 2], [3, 0, 1], [0, 2, 1], [0, 1, 3], [2, 1, 0]])[sector]  # [..., (b, g, r)]
     bgr = np.take_along_axis(tab, idx, axis=-1)
     bgr = np.where((sf == 0)[..., None], vf[..., None], bgr)
-    assert bgr.dtype == np.float32
+    if bgr.dtype != np.float32:
+        raise RuntimeError("hsv_to_rgb_u8_host: an operation left float32 (the model rounds every operation in fp32)")
     out = np.clip(np.rint(bgr * f32(255)), 0, 255).astype(np.uint8)
     return out[..., ::-1].copy()
 
@@ -219,7 +213,7 @@ def handle_lighting_host(im, mask, keep_background=False):
     """numpy model of snerf_fg_lighting = utils_render.py:1008-1051 with the conversions above in cv2's place -> new uint8 [H,W,3]"""
     im, mask = _px_host(im), _px_host(mask)
     H, W, _ = im.shape
-    assert mask.shape == im.shape and H * W <= LIGHTING_MAX_PIXELS, "mask and frame [H,W,3], at most 2^23 pixels"
+    _require(mask.shape == im.shape and H * W <= LIGHTING_MAX_PIXELS, "mask and frame [H,W,3], at most 2^23 pixels")
     hsv = rgb_to_hsv_u8_host(im)
     fg = mask[..., 0] > 0
     n_fg, s1, s2, n_bg, s_bg = _lighting_stats(hsv[..., 2], fg, H, W)[4:]
@@ -236,8 +230,8 @@ def handle_lighting_host(im, mask, keep_background=False):
 def _hsv_u8(px, to_rgb):
     if isinstance(px, np.ndarray):
         return hsv_to_rgb_u8_host(px) if to_rgb else rgb_to_hsv_u8_host(px)
-    _u8(px)
-    assert px.dim() >= 1 and px.shape[-1] == 3 and px.numel() > 0, "expected a non-empty uint8 tensor [..., 3]"
+    _dev("px", px, dtype=torch.uint8)
+    _require(px.dim() >= 1 and px.shape[-1] == 3 and px.numel() > 0, "expected a non-empty uint8 tensor [..., 3]")
     _lib.call("snerf_fg_hsv", _p(px), px.numel() // 3, int(to_rgb), _stream())
     return px
 
@@ -263,10 +257,11 @@ def handle_lighting(im, mask, keep_background=False, stats=None):
     if isinstance(im, np.ndarray):
         return handle_lighting_host(im, np.asarray(mask), keep_background)
     H, W, _ = im.shape
-    _u8(im, (H, W, 3)); _u8(mask, (H, W, 3))
+    _dev("im mask", im, mask, dtype=torch.uint8, shape=(H, W, 3))
     if stats is None:
         stats = torch.empty(9, dtype=torch.int64, device=im.device)
-    assert stats.is_cuda and stats.dtype == torch.int64 and stats.is_contiguous() and stats.numel() == 9, "stats: an int64 [9] device tensor"
+    _dev("stats", stats, dtype=torch.int64, msg="stats: an int64 [9] device tensor")
+    _require(stats.numel() == 9, "stats: an int64 [9] device tensor")
     _lib.call("snerf_fg_lighting", _p(im), _p(mask), H, W, int(bool(keep_background)), _p(stats), _stream())
     return im
 
@@ -277,11 +272,10 @@ def overlap_stats(masks):
     a >= b.  One launch that reads every mask once; the masks are not stacked or copied.  No host read."""
     masks = list(masks)
     N = len(masks)
-    assert N >= 1, "overlap_stats: at least one mask"
+    _require(N >= 1, "overlap_stats: at least one mask")
     H, W, _ = masks[0].shape
-    for m in masks:
-        _u8(m, (H, W, 3))
-        assert m.device == masks[0].device, "overlap_stats: all masks on one device"
+    _dev("masks", *masks, dtype=torch.uint8, shape=(H, W, 3))
+    _require(all(m.device == masks[0].device for m in masks), "overlap_stats: all masks on one device")
     stats = torch.zeros(N, N, 3, dtype=torch.int64, device=masks[0].device)
     ptrs = (ctypes.c_void_p * N)(*[m.data_ptr() for m in masks])
     _lib.call("snerf_fg_overlap", ptrs, N, H, W, _p(stats), _stream())
@@ -333,14 +327,14 @@ def occlusion_order(masks, meshes, w2c, P, ray_frame="reference"):
     Parity: trimesh is not part of the reference tree, so how `intersects_first` treats a ray through an edge or a degenerate face is
     not pinned; the semantics are those of meshtrace (watertight, nearest t > 0).  The ray is formed in float64 on the device and
     cast in fp32."""
-    assert ray_frame in ("reference", "camera"), "ray_frame: 'reference' or 'camera'"
+    _require(ray_frame in ("reference", "camera"), "ray_frame: 'reference' or 'camera'")
     masks, meshes = list(masks), list(meshes)
     N = len(masks)
-    assert len(meshes) == N, "occlusion_order: one (tracer, transform) per mask"
+    _require(len(meshes) == N, "occlusion_order: one (tracer, transform) per mask")
     if N < 2:
         return list(range(N)), np.zeros((N, N), dtype=np.int8)
     dev = masks[0].device
-    assert not any(torch.is_tensor(m) and m.is_cuda for m in (w2c, P)), "w2c, P: host values (a device matrix would cost a sync per call)"
+    _require(not any(torch.is_tensor(m) and m.is_cuda for m in (w2c, P)), "w2c, P: host values (a device matrix would cost a sync per call)")
     c2w = np.linalg.inv(np.asarray(w2c, dtype=np.float64)[:4, :4])
     host = np.concatenate([np.linalg.inv(np.asarray(P, dtype=np.float64)[:3, :3]).reshape(-1), c2w[:3].reshape(-1)])
     host = torch.tensor(host, dtype=torch.float64).to(dev)                      # one upload: inv(P) and the top of c2w
@@ -425,6 +419,15 @@ def save_bbox_results(path, results):
             f.write("\n")
 
 
+def _image_and_mask(inst, depth_mat):
+    """the instance's image and mask: given, or rendered here at the frame's size from render = (MeshRenderer, transform)"""
+    if inst.get("render") is None:
+        return inst["image"], inst["mask"]
+    renderer, transform = inst["render"]
+    fx, fy, cx, cy = _intrinsic(inst["intrinsic"])
+    return renderer.render(fx, fy, cx, cy, depth_mat.shape[0], depth_mat.shape[1], transform=transform)[:2]
+
+
 def _ordered_by_occlusion(instances, depth_mat, w2c, intrinsic):
     """composite_frame(order="occlusion"): render what is to be rendered, then -> (the instances in paste order, the order)"""
     instances = [dict(inst) for inst in instances]
@@ -437,10 +440,8 @@ def _ordered_by_occlusion(instances, depth_mat, w2c, intrinsic):
     for inst in instances:
         if inst.get("intrinsic") is None:
             inst["intrinsic"] = intrinsic
-        if inst.get("render") is not None:
-            renderer, transform = inst.pop("render")
-            fx, fy, cx, cy = _intrinsic(inst["intrinsic"])
-            inst["image"], inst["mask"] = renderer.render(fx, fy, cx, cy, depth_mat.shape[0], depth_mat.shape[1], transform=transform)[:2]
+        inst["image"], inst["mask"] = _image_and_mask(inst, depth_mat)
+        inst.pop("render", None)                       # rendered: the paste loop takes the image and the mask as given
     order, _ = occlusion_order([inst["mask"] for inst in instances], [inst["mesh"] for inst in instances], w2c, intrinsic)
     return [instances[i] for i in order], order
 
@@ -474,12 +475,7 @@ def composite_frame(bg_im, depth_mat, semantic_mat, instances, order="given", w2
     occ, masks, bounds = [], [], []
     for inst in instances:
         cat = inst.get("category", "vehicle")
-        if inst.get("render") is not None:
-            renderer, transform = inst["render"]
-            fx, fy, cx, cy = _intrinsic(inst["intrinsic"])
-            image, mask = renderer.render(fx, fy, cx, cy, depth_mat.shape[0], depth_mat.shape[1], transform=transform)[:2]
-        else:
-            image, mask = inst["image"], inst["mask"]
+        image, mask = _image_and_mask(inst, depth_mat)
         r = inst.get("r")
         if r is None:
             r = bound_radius(mask, cat)

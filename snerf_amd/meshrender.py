@@ -104,7 +104,7 @@ class MeshRenderer:
         numbering, -1 on a miss).  `transform`: the tracer's 3 x 4 / 4 x 4 map from mesh to camera coordinates (-z forward, +y up, host or
         device).  `validate`: an invalid frame (mesh_renderer.py:44-53) comes back empty.  No host sync."""
         unknown = set(want) - {"image_f", "depth", "face_id"}
-        assert not unknown, f"want: unknown outputs {sorted(unknown)}"
+        ops._require(not unknown, "want: unknown outputs %s", sorted(unknown))
         ws = self.tracer.prepare(transform)
         image, image_f, mask, depth, face_id = ops.mesh_render_pinhole(
             ws, self.tracer.n_faces, fx, fy, cx, cy, H, W, faces=self.tracer.faces if self.vertex_color is not None else None,

@@ -50,7 +50,7 @@ def _as_transform(transform, device):
         return None
     t = transform if torch.is_tensor(transform) else torch.tensor(np.asarray(transform, dtype=np.float32))
     t = t.to(device=device, dtype=torch.float32)
-    assert tuple(t.shape) in ((3, 4), (4, 4)), "transform: a 3 x 4 (or 4 x 4 affine) matrix"
+    ops._require(tuple(t.shape) in ((3, 4), (4, 4)), "transform: a 3 x 4 (or 4 x 4 affine) matrix")
     return t[:3].contiguous()
 
 

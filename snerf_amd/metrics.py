@@ -46,7 +46,7 @@ def dssim_to_ssim(dssim):
 def gray_weights(gray):
     """"cv4" | "cv3" | (wr, wg, wb, shift) -> the tuple of four ints"""
     w = GRAY_WEIGHTS[gray] if isinstance(gray, str) else tuple(int(v) for v in gray)
-    assert len(w) == 4 and 1 <= w[3] <= 20 and min(w[:3]) >= 0 and sum(w[:3]) <= 1 << w[3], "gray: (wr, wg, wb, shift)"
+    ops._require(len(w) == 4 and 1 <= w[3] <= 20 and min(w[:3]) >= 0 and sum(w[:3]) <= 1 << w[3], "gray: (wr, wg, wb, shift)")
     return w
 
 
@@ -77,7 +77,7 @@ def ssim_host(gx, gy):
     """skimage's structural_similarity(gx, gy, data_range=255) with its defaults on two grey images [H,W] of integers in 0..255: 7 x 7
     uniform window, K1 = 0.01, K2 = 0.03, sample covariance, border of 3 cropped.  Integer window sums, then float64."""
     gx, gy = np.asarray(gx).astype(np.int64), np.asarray(gy).astype(np.int64)
-    assert gx.shape == gy.shape and gx.ndim == 2 and min(gx.shape) >= SSIM_WIN, "the 7 x 7 window must fit"
+    ops._require(gx.shape == gy.shape and gx.ndim == 2 and min(gx.shape) >= SSIM_WIN, "the 7 x 7 window must fit")
     NP = float(SSIM_WIN * SSIM_WIN)
     cov = NP / (NP - 1.)
     sx, sy = _window_sums(gx).astype(np.float64), _window_sums(gy).astype(np.float64)
@@ -97,7 +97,7 @@ def frame_metrics_host(pred, gt, gray="cv4"):
     """The host model of snerf_frame_metrics: pred [H,W,3] or [F,H,W,3] floats, gt of the same shape, floats or uint8 -> float64 [F,5]
     in the order of ops.FRAME_METRIC_NAMES (numpy arrays or tensors in, a numpy array out)."""
     pred, gt = _np(pred), _np(gt)
-    assert pred.ndim in (3, 4) and pred.shape[-1] == 3 and gt.shape == pred.shape, "pred [H,W,3] or [F,H,W,3], gt of the same shape"
+    ops._require(pred.ndim in (3, 4) and pred.shape[-1] == 3 and gt.shape == pred.shape, "pred [H,W,3] or [F,H,W,3], gt of the same shape")
     if pred.ndim == 3:
         pred, gt = pred[None], gt[None]
     pred = pred.astype(np.float32, copy=False)
@@ -147,7 +147,7 @@ class MetricHarness:
         self.gray = gray
 
     def __call__(self, rgb_pred, rgb_gt, name_fn=lambda s: s):
-        assert rgb_pred.ndim == 3, "one frame [H,W,3]"
+        ops._require(rgb_pred.ndim == 3, "one frame [H,W,3]")
         if torch.is_tensor(rgb_pred) and rgb_pred.is_cuda:
             psnr, ssim = frame_metrics(rgb_pred, rgb_gt, self.gray)[0, _PSNR_U8:_SSIM + 1].tolist()
         else:
@@ -190,7 +190,7 @@ class EvalMeter:
         """one host read -> {'psnr', 'psnr_u8', 'ssim'}: means over the frames of the per-frame values (eval.py:170's
         np.array(PSNR).mean(), not the PSNR of the mean MSE; one frame with psnr_u8 = inf makes that mean inf), and 'frames': the
         table, float64 [n,5] in the order of ops.FRAME_METRIC_NAMES"""
-        assert self.n > 0, "no frame added"
+        ops._require(self.n > 0, "no frame added")
         frames = self.table[:self.n].cpu().numpy()
         col = lambda name: float(frames[:, ops.FRAME_METRIC_NAMES.index(name)].mean())
         return {"psnr": col("psnr_f"), "psnr_u8": col("psnr_u8"), "ssim": col("ssim"), "frames": frames}

@@ -28,7 +28,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .foreground import _u8
+from .ops import _dev, _require, _ws
 
 
 def process_placement(bbox_center, theta, mesh_bias):
@@ -46,7 +46,7 @@ def light_vector(pitch_angle, yaw_angle):
 
 
 def _host(a, what):
-    assert not (torch.is_tensor(a) and a.is_cuda), f"{what}: host values (a device matrix would cost a sync per call)"
+    _require(not (torch.is_tensor(a) and a.is_cuda), "%s: host values (a device matrix would cost a sync per call)", what)
     return np.asarray(a, dtype=np.float64)
 
 
@@ -78,8 +78,7 @@ def project_shadow_mask(vertices, bbox_center, theta, mesh_bias, pitch_angle, ya
     """steps 1-4 of generate_one_shadow -> the [H,W,3] uint8 splat mask of vertices [N,3] (fp32 or fp64).  With check the ground
     projection is skipped (mesh_shadow.py:70-71)."""
     v = _vertices(vertices, None if ws is None else ws.device)
-    if ws is None:
-        ws = torch.empty(ops.shadow_ws_bytes(H, W, v.shape[0], 1, 0), dtype=torch.uint8, device=v.device)
+    ws = _ws(ws, lambda: ops.shadow_ws_bytes(H, W, v.shape[0], 1, 0), torch.uint8, v.device, ops._SHADOW_WS)
     xf = (ctypes.c_double * 28)()
     mode = _pack_xf(xf, process_placement(bbox_center, theta, mesh_bias), light_vector(pitch_angle, yaw_angle), ground_height, world_to_pixel(c2w, P), check)
     mask = torch.empty(H, W, 3, dtype=torch.uint8, device=v.device)
@@ -89,7 +88,7 @@ def project_shadow_mask(vertices, bbox_center, theta, mesh_bias, pitch_angle, ya
 def interpolate(mask, r=20, iter=3):
     """utils.py:195-211 -> a new [H,W,3] uint8 mask"""
     H, W, _ = mask.shape
-    _u8(mask, (H, W, 3))
+    _dev("mask", mask, dtype=torch.uint8, shape=(H, W, 3))
     ws = torch.empty(ops.shadow_ws_bytes(H, W, 0, r, iter), dtype=torch.uint8, device=mask.device)
     return ops.shadow_close(mask, H, W, r, iter, ws, torch.empty_like(mask))
 
@@ -97,9 +96,8 @@ def interpolate(mask, r=20, iter=3):
 def blur_shadow(im, total_mask, shadow_mask, light_scale=.55, ws=None):
     """mesh_shadow.py:89-107, in place on im [H,W,3] uint8"""
     H, W, _ = im.shape
-    _u8(im, (H, W, 3)); _u8(total_mask, (H, W, 3)); _u8(shadow_mask, (H, W, 3))
-    if ws is None:
-        ws = torch.empty(ops.shadow_ws_bytes(H, W, 0, 1, 0), dtype=torch.uint8, device=im.device)
+    _dev("im total_mask shadow_mask", im, total_mask, shadow_mask, dtype=torch.uint8, shape=(H, W, 3))
+    ws = _ws(ws, lambda: ops.shadow_ws_bytes(H, W, 0, 1, 0), torch.uint8, im.device, ops._SHADOW_WS)
     return ops.shadow_fuse(im, total_mask, shadow_mask, H, W, light_scale, False, ws)
 
 
@@ -119,10 +117,11 @@ class ShadowCaster:
         keyword names for the rest (host values).  check: the closed projection of the placed mesh blanks the image instead.
         Instances are cast one after the other on the same im, so shadows multiply.  No host read, no allocation."""
         H, W = self.H, self.W
-        _u8(im, (H, W, 3))
+        _dev("im", im, dtype=torch.uint8, shape=(H, W, 3))
         if not check:
-            _u8(total_mask, (H, W, 3))
-        assert torch.is_tensor(vertices) and vertices.is_cuda and vertices.shape[0] <= self.max_vertices, "vertices: a device tensor of at most max_vertices rows"
+            _dev("total_mask", total_mask, dtype=torch.uint8, shape=(H, W, 3))
+        _require(torch.is_tensor(vertices) and vertices.is_cuda and vertices.shape[0] <= self.max_vertices,
+                 "vertices: a device tensor of at most max_vertices rows")
         mode = _pack_xf(self._xf, process_placement(bbox_center, theta, mesh_bias), light_vector(pitch_angle, yaw_angle), ground_height,
                         world_to_pixel(c2w, P), check)
         ops.shadow_project(vertices, self._xf, mode, H, W, self.ws)
